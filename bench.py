@@ -9,6 +9,10 @@ cropped sRGB) over one batch of `--frames` synthetic 4K mosaics per GPU (weak sc
 N=8).  Inputs are resident in HBM before the timed region.  At N>1 every rank's sRGB frames are all-gathered to all ranks
 over RCCL/xGMI on a side stream, overlapped with the next step's forward; the last gather is inside the timed
 region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds, after the timed steps, what takes work of its own: one
+HIP-event profiling step (roofline), the PMC traffic summary, the CPU baseline and PSNR against the CPU oracle, and at cfg3 on one GPU the codec_leg
+and cfg2_leg keys.  --dump-outputs DIR writes what the last timed step returned (rank 0) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -147,6 +151,33 @@ def load_pmc_summary():
             pmc["_file"] = name
             return pmc
     return None
+
+
+DUMP_BYTES = 32 << 20                                  # --dump-outputs: the whole dump stays well under 64 MB
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: every tensor of `outputs` (a dict, nested dicts named by dotted keys; a tensor met twice is written once) as out_dir/<name>.npy in
+    float32.  DUMP_BYTES is shared evenly: an output larger than its share is written flattened, as the elements at seeded uniform positions in ascending
+    order -- the same positions in every run with the same arguments, so that two builds can be compared output for output."""
+    import numpy as np
+    flat, seen = {}, set()
+
+    def walk(prefix, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                walk(f"{prefix}.{k}" if prefix else str(k), x)
+        elif isinstance(v, torch.Tensor) and id(v) not in seen:
+            seen.add(id(v))
+            flat[prefix] = v.detach()
+    walk("", outputs)
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BYTES // 4 // max(1, len(flat))
+    for i, (name, t) in enumerate(flat.items()):
+        if t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=torch.Generator().manual_seed(i)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 from torch.utils._python_dispatch import TorchDispatchMode
@@ -291,15 +322,22 @@ def main():
     ap.add_argument("--model", default="LiteISPNet_GFM_LSC_GMA", choices=["LiteISPNet_GFM_LSC_GMA", "LiteISPNet_GFM_LSC", "LiteISPNet", "ISPUNet_GFM_LSC", "raw_compression_tcm_final"],
                     help="default = cfg3: the flagship net plus one GroupMix GMA_Block(80,8) at H/2 (build-defined placement); "
                          "raw_compression_tcm_final = the RAW codec's forward (likelihood path), SURVEY cfg5's codec leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything that takes work of its own: the roofline (one HIP-event profiling step) and PMC traffic, the CPU baseline "
+                         "with the PSNR against the CPU oracle, and at cfg3 on one GPU the codec_leg and cfg2_leg keys")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32; a fixed seeded sample of an output "
+                                                          "larger than its share of 32 MiB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the PSNR legs")
     ap.add_argument("--sample-power", action="store_true", help="diagnostic: one rocm-smi sample (socket W, shader clock) from a side thread INSIDE the timed region (rank 0)")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the all-gather of the output frames (replicas only)")
-    ap.add_argument("--no-codec-leg", action="store_true", help="default cfg3 run: skip the extra codec_leg key (raw_compression_tcm_final at 4 frames)")
+    ap.add_argument("--no-codec-leg", action="store_true", help="with --full at cfg3: skip the extra codec_leg and cfg2_leg keys")
     ap.add_argument("--layer-by-layer-tail", action="store_true", help="A/B: the tail as the module list's two launches (ops.FOLD_TAIL = False) instead of the folded 5x5 conv")
     ap.add_argument("--staged-gate", action="store_true", help="A/B: round 3's RCAB schedule (CALayer gate folded into the next conv's staging, ops.EARLY_GATE = False)")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="no GPU work: the launch / rendezvous / barrier / max-over-ranks skeleton with a trivial CPU step over gloo; prints a line marked as a self-test (tests only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from realcamnet_amd import shard
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:     # plain `python bench.py --gpus N`: become the N-rank torchrun job (does not return)
@@ -323,7 +361,7 @@ def main():
     torch.manual_seed(0)                                   # random-init weights of the named architecture
     codec = args.model == "raw_compression_tcm_final"
     net = (M.raw2bit.raw_compression_tcm_final() if codec else getattr(M, args.model)()).eval()
-    sd_cpu = {k: v.clone() for k, v in net.state_dict().items()}
+    sd_cpu = {k: v.clone() for k, v in net.state_dict().items()} if args.full else None      # the CPU legs' weights
     net = net.to(device=dev, dtype=dt)
 
     B, H2, W2 = args.frames, args.height, args.width
@@ -377,13 +415,16 @@ def main():
     assert out.shape == (B, 3, H2, W2) and gathered.shape == (total_frames if gather is not None else B, 3, H2, W2)
     if gather is not None:                                 # the gathered payload is this rank's own frames where they belong
         assert torch.equal(gathered[s:e], out)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"srgb": gathered})
 
-    # dominant kernel (MFMA conv): HIP-event time of every launch on its stream, one extra step
-    ops.prof_enable(True)
-    step()
-    n_launch, conv_ms, conv_flops = ops.prof_collect()
-    rows = ops.prof_rows()
-    ops.prof_enable(False)
+    if args.full:
+        # dominant kernel (MFMA conv): HIP-event time of every launch on its stream, one extra step
+        ops.prof_enable(True)
+        step()
+        n_launch, conv_ms, conv_flops = ops.prof_collect()
+        rows = ops.prof_rows()
+        ops.prof_enable(False)
 
     if rank != 0:
         return
@@ -392,8 +433,6 @@ def main():
         cfg_name = "cfg2"
     mp_per_step = total_frames * H2 * W2 / 1e6
     value = mp_per_step * args.steps / elapsed
-    achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-    peak = PEAK_TFLOPS[args.dtype]
     res = {
         "metric": "megapixels/sec RAW->sRGB at 4K" if (H2, W2) == (2160, 3840) else f"megapixels/sec RAW->sRGB at {W2}x{H2}", "value": round(value, 2), "unit": "MP/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -406,70 +445,74 @@ def main():
                                   "stream overlapped with the next step's forward") if gather is not None else "none",
                    **({"schedule": ("tail as two launches; " if args.layer_by_layer_tail else "") + ("CALayer gate staged in the next conv" if args.staged_gate else "")}
                       if (args.layer_by_layer_tail or args.staged_gate) else {})},
-        "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4), "traffic": None,
-                     "kernel": "conv_mfma_kernel (all instantiations)", "launches_per_step": int(n_launch),
-                     "kernel_ms_per_step": round(conv_ms, 3), "flops_per_step": conv_flops},
     }
-    # what bounds what: the family's frac above is priced against the MFMA peak, but the layer shape with the most time is HBM-paced -- name it, with both
-    # of its fractions (flat scalar keys: the driver's parser keeps those)
-    rf = res["roofline"]
-    fa = flops_algorithmic(args.model, B, H2, W2)
-    if fa is not None:
-        rf["flops_algorithmic"] = fa
-        rf["frac_algorithmic_whole_step"] = round(fa / (elapsed / args.steps) / 1e12 / peak, 4)
-        rf["flops_note"] = ("flops_per_step = executed by the conv launches (the folded 5x5 tail executes 4.6x fewer than the two convolutions it replaces; a Winograd F(2x2,3x3) "
-                            "launch -- the fp32 3x3 layers with 64 | cout -- executes 4/9 of its layer's multiplications, so frac_algorithmic_whole_step can exceed frac and, in fp32, 1); "
-                            "flops_algorithmic = SURVEY 8(d): reference net at the padded size + GroupMix block")
-    if rows:
-        d0 = rows[0]
-        es = 2 if args.dtype == "bf16" else 4
-        rf["dominant_kernel"] = f"conv {d0['ksize']}x{d0['ksize']} {d0['cin']}->{d0['cout']} ({d0['launches']} launches per step)"
-        rf["dominant_ms_per_step"] = round(d0["ms"], 3)
-        rf["dominant_tflops"] = round(d0["flops"] / (d0["ms"] * 1e-3) / 1e12, 1)
-        rf["dominant_mfma_frac"] = round(d0["flops"] / (d0["ms"] * 1e-3) / 1e12 / peak, 4)
-        rf["dominant_hbm_TBps"] = round(d0["bytes"] / (d0["ms"] * 1e-3) / 1e12, 2)
-        rf["dominant_hbm_frac_of_8TBps"] = round(d0["bytes"] / (d0["ms"] * 1e-3) / 8e12, 4)
-        rf["dominant_bound"] = "hbm" if rf["dominant_hbm_frac_of_8TBps"] > rf["dominant_mfma_frac"] else "mfma"
-        rf["by_shape_top4"] = "; ".join(f"{r['cin']}->{r['cout']} k{r['ksize']}: {r['ms']:.2f} ms, {r['flops'] / (r['ms'] * 1e-3) / 1e12:.0f} TF/s, "
-                                        f"{r['bytes'] / (r['ms'] * 1e-3) / 1e12:.2f} TB/s" for r in rows[:4])
     if power is not None:
         res["power"] = power
-        rf["power_note"] = (f"rocm-smi mid-run: socket {power.get('socket_W')} W (its reading averages over a window that includes the non-conv kernels) of a "
-                            f"{power.get('cap_W')} W cap, sclk {power.get('sclk_MHz')} MHz of 2400; the conv kernels alone sit AT the cap (profiles/r05_power_wall.md)")
-    # HBM traffic comes from PMC counters, which cannot be read inside a timed run: tools/pmc_bench.sh collects them in separate
-    # rocprofv3 --pmc passes of this same default command and commits the summary under profiles/.  The summary carries the digest of
-    # the kernel sources it was measured on; a file taken on other sources is ignored (traffic stays null) rather than replayed.
-    pmc = load_pmc_summary() if (cfg_name == "cfg3" and args.dtype == "bf16" and B == 8) else None
-    if pmc is not None:
-        res["roofline"]["traffic"] = round(pmc["conv_kernels_all"]["hbm_bytes_per_dispatch"])
-        res["roofline"]["traffic_note"] = ("HBM bytes per conv launch (mean over the step's conv launches), FETCH_SIZE x2 + WRITE_SIZE from "
-                                           f"profiles/{pmc['_file']} (same kernel-source digest {pmc['source_digest'][:12]} as this build)")
-        # the mean hides very different layers: also the three kernels that move the most, per launch and per forward (same PMC passes)
-        fw = pmc.get("forwards", 3)
-        top = sorted(((k, v["dispatches"], v["fetch_bytes_per_dispatch"] + v["write_bytes_per_dispatch"]) for k, v in pmc["kernels"].items()),
-                     key=lambda t: -t[1] * t[2])[:3]
-        res["roofline"]["traffic_by_kernel"] = [{"kernel": k.split("(")[0][-70:], "launches_per_forward": round(n / fw, 1), "hbm_bytes_per_launch": round(bpl),
-                                                 "hbm_GB_per_forward": round(n * bpl / fw / 1e9, 1)} for k, n, bpl in top]
-        res["roofline"]["traffic_top3"] = "; ".join(f"{k.split('(')[0].split('::')[-1][:40]} x{n / fw:.0f}: {n * bpl / fw / 1e9:.1f} GB per forward" for k, n, bpl in top)
-        step_bytes = (pmc["all_kernels_total_bytes"]["fetch"] + pmc["all_kernels_total_bytes"]["write"]) / pmc.get("forwards", 3)
-        res["hbm_whole_step"] = {"bytes_per_step": round(step_bytes), "achieved_TBps": round(step_bytes / (elapsed / args.steps) / 1e12, 2),
-                                 "copy_rate_TBps": pmc.get("copy_rate_TBps", 5.9), "peak_TBps": 8.0}
-    else:
-        res["roofline"]["traffic_note"] = "null: no PMC summary under profiles/ was taken on this build's kernel sources (tools/pmc_bench.sh)"
-    if world == 1 and cfg_name == "cfg3" and not args.no_codec_leg:
-        del out, gathered
-        torch.cuda.empty_cache()
-        res["codec_leg"] = codec_leg(dev, dt, H2, W2, frames=args.frames, steps=4, with_psnr=not args.no_cpu_baseline)     # cfg5: the same frames per GPU as the headline (8)
-        res["cfg2_leg"] = cfg2_leg(dev, with_psnr=not args.no_cpu_baseline)
-    if world == 1 and not args.no_cpu_baseline:
-        info, (m_c, c_c, co_c, ref) = cpu_baseline(args.model, sd_cpu, (H2, W2))
-        with torch.no_grad():
-            y = net.forward_mosaic(m_c.to(dev, dt), c_c.to(dev, dt), co_c.to(dev, dt))
-        torch.cuda.synchronize()
-        res["cpu_baseline"] = info
-        import liteisp_oracle as O
-        res["psnr_db_vs_cpu_fp32"] = round(O.psnr(y.float().cpu(), ref), 2)
+    if args.full:
+        achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+        peak = PEAK_TFLOPS[args.dtype]
+        res["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
+                           "frac": round(achieved / peak, 4), "traffic": None,
+                           "kernel": "conv_mfma_kernel (all instantiations)", "launches_per_step": int(n_launch),
+                           "kernel_ms_per_step": round(conv_ms, 3), "flops_per_step": conv_flops}
+        # what bounds what: the family's frac above is priced against the MFMA peak, but the layer shape with the most time is HBM-paced -- name it, with both
+        # of its fractions (flat scalar keys: the driver's parser keeps those)
+        rf = res["roofline"]
+        fa = flops_algorithmic(args.model, B, H2, W2)
+        if fa is not None:
+            rf["flops_algorithmic"] = fa
+            rf["frac_algorithmic_whole_step"] = round(fa / (elapsed / args.steps) / 1e12 / peak, 4)
+            rf["flops_note"] = ("flops_per_step = executed by the conv launches (the folded 5x5 tail executes 4.6x fewer than the two convolutions it replaces; a Winograd F(2x2,3x3) "
+                                "launch -- the fp32 3x3 layers with 64 | cout -- executes 4/9 of its layer's multiplications, so frac_algorithmic_whole_step can exceed frac and, in fp32, 1); "
+                                "flops_algorithmic = SURVEY 8(d): reference net at the padded size + GroupMix block")
+        if rows:
+            d0 = rows[0]
+            es = 2 if args.dtype == "bf16" else 4
+            rf["dominant_kernel"] = f"conv {d0['ksize']}x{d0['ksize']} {d0['cin']}->{d0['cout']} ({d0['launches']} launches per step)"
+            rf["dominant_ms_per_step"] = round(d0["ms"], 3)
+            rf["dominant_tflops"] = round(d0["flops"] / (d0["ms"] * 1e-3) / 1e12, 1)
+            rf["dominant_mfma_frac"] = round(d0["flops"] / (d0["ms"] * 1e-3) / 1e12 / peak, 4)
+            rf["dominant_hbm_TBps"] = round(d0["bytes"] / (d0["ms"] * 1e-3) / 1e12, 2)
+            rf["dominant_hbm_frac_of_8TBps"] = round(d0["bytes"] / (d0["ms"] * 1e-3) / 8e12, 4)
+            rf["dominant_bound"] = "hbm" if rf["dominant_hbm_frac_of_8TBps"] > rf["dominant_mfma_frac"] else "mfma"
+            rf["by_shape_top4"] = "; ".join(f"{r['cin']}->{r['cout']} k{r['ksize']}: {r['ms']:.2f} ms, {r['flops'] / (r['ms'] * 1e-3) / 1e12:.0f} TF/s, "
+                                            f"{r['bytes'] / (r['ms'] * 1e-3) / 1e12:.2f} TB/s" for r in rows[:4])
+        if power is not None:
+            rf["power_note"] = (f"rocm-smi mid-run: socket {power.get('socket_W')} W (its reading averages over a window that includes the non-conv kernels) of a "
+                                f"{power.get('cap_W')} W cap, sclk {power.get('sclk_MHz')} MHz of 2400; the conv kernels alone sit AT the cap (profiles/r05_power_wall.md)")
+        # HBM traffic comes from PMC counters, which cannot be read inside a timed run: tools/pmc_bench.sh collects them in separate
+        # rocprofv3 --pmc passes of this same default command and commits the summary under profiles/.  The summary carries the digest of
+        # the kernel sources it was measured on; a file taken on other sources is ignored (traffic stays null) rather than replayed.
+        pmc = load_pmc_summary() if (cfg_name == "cfg3" and args.dtype == "bf16" and B == 8) else None
+        if pmc is not None:
+            res["roofline"]["traffic"] = round(pmc["conv_kernels_all"]["hbm_bytes_per_dispatch"])
+            res["roofline"]["traffic_note"] = ("HBM bytes per conv launch (mean over the step's conv launches), FETCH_SIZE x2 + WRITE_SIZE from "
+                                               f"profiles/{pmc['_file']} (same kernel-source digest {pmc['source_digest'][:12]} as this build)")
+            # the mean hides very different layers: also the three kernels that move the most, per launch and per forward (same PMC passes)
+            fw = pmc.get("forwards", 3)
+            top = sorted(((k, v["dispatches"], v["fetch_bytes_per_dispatch"] + v["write_bytes_per_dispatch"]) for k, v in pmc["kernels"].items()),
+                         key=lambda t: -t[1] * t[2])[:3]
+            res["roofline"]["traffic_by_kernel"] = [{"kernel": k.split("(")[0][-70:], "launches_per_forward": round(n / fw, 1), "hbm_bytes_per_launch": round(bpl),
+                                                     "hbm_GB_per_forward": round(n * bpl / fw / 1e9, 1)} for k, n, bpl in top]
+            res["roofline"]["traffic_top3"] = "; ".join(f"{k.split('(')[0].split('::')[-1][:40]} x{n / fw:.0f}: {n * bpl / fw / 1e9:.1f} GB per forward" for k, n, bpl in top)
+            step_bytes = (pmc["all_kernels_total_bytes"]["fetch"] + pmc["all_kernels_total_bytes"]["write"]) / pmc.get("forwards", 3)
+            res["hbm_whole_step"] = {"bytes_per_step": round(step_bytes), "achieved_TBps": round(step_bytes / (elapsed / args.steps) / 1e12, 2),
+                                     "copy_rate_TBps": pmc.get("copy_rate_TBps", 5.9), "peak_TBps": 8.0}
+        else:
+            res["roofline"]["traffic_note"] = "null: no PMC summary under profiles/ was taken on this build's kernel sources (tools/pmc_bench.sh)"
+        if world == 1 and cfg_name == "cfg3" and not args.no_codec_leg:
+            del out, gathered
+            torch.cuda.empty_cache()
+            res["codec_leg"] = codec_leg(dev, dt, H2, W2, frames=args.frames, steps=4, with_psnr=not args.no_cpu_baseline)     # cfg5: the same frames per GPU as the headline (8)
+            res["cfg2_leg"] = cfg2_leg(dev, with_psnr=not args.no_cpu_baseline)
+        if world == 1 and not args.no_cpu_baseline:
+            info, (m_c, c_c, co_c, ref) = cpu_baseline(args.model, sd_cpu, (H2, W2))
+            with torch.no_grad():
+                y = net.forward_mosaic(m_c.to(dev, dt), c_c.to(dev, dt), co_c.to(dev, dt))
+            torch.cuda.synchronize()
+            res["cpu_baseline"] = info
+            import liteisp_oracle as O
+            res["psnr_db_vs_cpu_fp32"] = round(O.psnr(y.float().cpu(), ref), 2)
     print(json.dumps(res), flush=True)
 
 
@@ -516,16 +559,17 @@ def bench_codec(args, net, sd_cpu, step, inputs, rank, world, dev, dt):
         out = step()
     torch.cuda.synchronize(); shard.barrier(); torch.cuda.synchronize()
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, dev)
-    ops.prof_enable(True)
-    step()
-    n_launch, conv_ms, conv_flops = ops.prof_collect()
-    ops.prof_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    if args.full:
+        ops.prof_enable(True)
+        step()
+        n_launch, conv_ms, conv_flops = ops.prof_collect()
+        ops.prof_enable(False)
     if rank != 0:
         return
     total_frames = B * world
     value = total_frames * H2 * W2 / 1e6 * args.steps / elapsed
-    achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-    peak = PEAK_TFLOPS[args.dtype]
     hp, wp = out["lsc"].shape[-2:]
     res = {"metric": f"megapixels/sec RAW mosaic {W2}x{H2} -> raw_compression_tcm_final.forward (likelihood path)", "value": round(value, 2), "unit": "MP/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
@@ -533,14 +577,17 @@ def bench_codec(args, net, sd_cpu, step, inputs, rank, world, dev, dt):
            "data": "synthetic (uniform[0,1) mosaics, seed-0 random-init weights)",
            "config": {"workload": f"cfg5 codec leg: {W2}x{H2} Bayer mosaic -> unshuffle + pad128 (packed {wp}x{hp}) -> raw_compression_tcm_final "
                                   f"(N=64, M=320, 5 slices) -> x_hat {2 * wp}x{2 * hp} + likelihoods, {B} frames/GPU, {args.dtype} storage / fp32 accumulate",
-                      "frames_per_gpu": B, "global_frames": total_frames, "parallelism": f"frame-shard x{world}"},
-           "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                        "traffic": None, "kernel": "conv_mfma_kernel (all instantiations)", "launches_per_step": int(n_launch),
-                        "kernel_ms_per_step": round(conv_ms, 3), "flops_per_step": conv_flops,
-                        "flops_note": ("necessary MACs: stride-2 convolutions (bf16: a 2x2 window over the space-to-depth map) are counted at their "
-                                       "9 real (tap, phase) blocks, not the 16 executed" if args.dtype == "bf16" else
-                                       "fp32 stride-2 convolutions run as a 3x3 embedding over the space-to-depth map and are counted as executed (4x)")}}
-    if world == 1 and not args.no_cpu_baseline:
+                      "frames_per_gpu": B, "global_frames": total_frames, "parallelism": f"frame-shard x{world}"}}
+    if args.full:
+        achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+        peak = PEAK_TFLOPS[args.dtype]
+        res["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                           "traffic": None, "kernel": "conv_mfma_kernel (all instantiations)", "launches_per_step": int(n_launch),
+                           "kernel_ms_per_step": round(conv_ms, 3), "flops_per_step": conv_flops,
+                           "flops_note": ("necessary MACs: stride-2 convolutions (bf16: a 2x2 window over the space-to-depth map) are counted at their "
+                                          "9 real (tap, phase) blocks, not the 16 executed" if args.dtype == "bf16" else
+                                          "fp32 stride-2 convolutions run as a 3x3 embedding over the space-to-depth map and are counted as executed (4x)")}
+    if args.full and world == 1 and not args.no_cpu_baseline:
         import liteisp_oracle as O                      # the oracle: checker and CPU baseline only
         import raw2bit_oracle as RO
         g = torch.Generator().manual_seed(1234)

@@ -1035,12 +1035,12 @@ def test_lsc_chain_in_registers_vs_layer_by_layer(hip, shape, width):
 
 
 def test_bench_prints_one_contract_json_line(hip):
-    """bench.py on a tiny workload: exactly one JSON line on stdout with the driver's contract keys, the roofline object
+    """bench.py --full on a tiny workload: exactly one JSON line on stdout with the driver's contract keys, the roofline object
     and (with the CPU leg on) the cpu_baseline object."""
     import json, subprocess
     from conftest import ROOT
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "1", "--height", "128", "--width", "192",
-                        "--steps", "2", "--warmup", "1", "--model", "LiteISPNet_GFM_LSC"], capture_output=True, text=True, timeout=600)
+                        "--steps", "2", "--warmup", "1", "--model", "LiteISPNet_GFM_LSC", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -1063,6 +1063,35 @@ def test_bench_prints_one_contract_json_line(hip):
     assert d["psnr_db_vs_cpu_fp32"] >= 55.0
 
 
+@pytest.mark.parametrize("model, size, names", [("LiteISPNet_GFM_LSC", (128, 192), {"srgb"}),
+                                                 ("raw_compression_tcm_final", (512, 512), {"x_hat", "likelihoods.y", "likelihoods.z", "para.y", "lsc"})])
+def test_plain_bench_prints_the_headline_only_and_dumps_what_the_last_step_returned(hip, tmp_path, model, size, names):
+    """bench.py without --full: the contract keys and none of --full's extra figures; --dump-outputs writes the timed path's outputs as float32 .npy files
+    (whole here: the tiny workload fits the budget)."""
+    import json, subprocess
+    import numpy as np
+    from conftest import ROOT
+    H2, W2 = size
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "1", "--height", str(H2), "--width", str(W2), "--steps", "3",
+                        "--warmup", "1", "--model", model, "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "steps", "warmup"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "MP/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - H2 * W2 / 1e6 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"] + 0.01
+    assert not set(d) & {"roofline", "cpu_baseline", "psnr_db_vs_cpu_fp32", "codec_leg", "cfg2_leg", "hbm_whole_step"}, sorted(d)
+    dumped = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert names <= set(dumped), sorted(dumped)
+    assert all(a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all() for a in dumped.values())
+    if model == "LiteISPNet_GFM_LSC":
+        assert dumped["srgb"].shape == (1, 3, H2, W2)
+    else:
+        assert dumped["x_hat"].shape[:2] == (1, 3) and "y" not in dumped          # the dict's second name for para.y is written once
+
+
 def test_bench_under_torchrun_gathers_over_rccl(hip):
     """One rank under torch.distributed.run: the process group is RCCL ("nccl"), every step's frames go through
     OverlappedGather (side stream, all_gather_into_tensor) and the gathered payload equals the local output."""
@@ -1078,12 +1107,12 @@ def test_bench_under_torchrun_gathers_over_rccl(hip):
 
 
 def test_bench_codec_leg_prints_one_contract_json_line(hip):
-    """bench.py --model raw_compression_tcm_final on a 512x512 mosaic: same contract keys; the latent before rounding must agree
+    """bench.py --full --model raw_compression_tcm_final on a 512x512 mosaic: same contract keys; the latent before rounding must agree
     with the CPU oracle (downstream of round() isolated flips are expected in bf16, so x_hat is only required to be sane)."""
     import json, subprocess
     from conftest import ROOT
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "1", "--height", "512", "--width", "512", "--steps", "1",
-                        "--warmup", "1", "--model", "raw_compression_tcm_final"], capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--model", "raw_compression_tcm_final", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout

@@ -8,7 +8,7 @@ tag = sys.argv[1]
 COUNTERS = ["SQ_VALU_MFMA_BUSY_CYCLES", "SQ_BUSY_CU_CYCLES", "SQ_LDS_BANK_CONFLICT", "SQ_LDS_IDX_ACTIVE"]
 data, calls = collections.defaultdict(dict), collections.defaultdict(int)
 for c in COUNTERS:
-    path = f"gpurun_out/pmcm_{tag}_{c}/pmc_results.db"
+    path = f"{os.environ.get('OUT', 'out')}/pmcm_{tag}_{c}/pmc_results.db"      # tools/pmc_mfma.sh's output directory
     if not os.path.exists(path):
         continue
     db = sqlite3.connect(path)

@@ -6,14 +6,14 @@ tag = sys.argv[1]
 RND = sys.argv[2] if len(sys.argv) > 2 else "r03"
 OUT = sys.argv[3] if len(sys.argv) > 3 else "profiles"      # the GPU box writes under gpurun_out/ (the only directory that travels back)
 os.makedirs(OUT, exist_ok=True)
-G = "gpurun_out"
+G = os.environ.get("OUT", "out")                           # tools/final_profiles.sh's output directory
 last = lambda p: open(p).read().strip().splitlines()[-1]
 shutil.copy(f"{G}/pmc_{tag}.json", f"{OUT}/{RND}_pmc_bench.json")
 trace, default = last(f"{G}/bench_trace_{tag}.json"), last(f"{G}/bench_default_{tag}.json")
 summ = subprocess.run([sys.executable, "tools/rocpd_summary.py", f"{G}/prof_{tag}/trace_results.db", "--last-forwards", "4"], capture_output=True, text=True).stdout
-open(f"{OUT}/{RND}_bench_kernel_stats.md", "w").write(f"""# {RND} — kernel trace of `python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-codec-leg` (cfg3, 1x MI355X)
+open(f"{OUT}/{RND}_bench_kernel_stats.md", "w").write(f"""# {RND} — kernel trace of `python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-codec-leg` (cfg3, 1x MI355X)
 
-Command: `rocprofv3 --kernel-trace --stats -d gpurun_out/prof_{tag} -o trace -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline`
+Command: `rocprofv3 --kernel-trace --stats -d {G}/prof_{tag} -o trace -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline`
 (5 forwards in the trace: 1 warm-up + 3 timed + 1 HIP-event profiling pass; the table counts the LAST FOUR -- steady state, the first forward's weight
 packing is out). Summarised from the rocpd database (kept: `gpurun_out/keep_{tag}/bench_trace_results.db`) with `tools/rocpd_summary.py --last-forwards 4`. The conv kernels (`conv_mfma_*`) sum to the `kernel_ms_per_step` that `bench.py` measures live with
 HIP events on the launch stream.
@@ -24,7 +24,7 @@ HIP events on the launch stream.
 
 {summ}
 """)
-open(f"{OUT}/{RND}_bench_default.md", "w").write(f"""# {RND} — default `python bench.py` (steps 5, warm-up 2, CPU baseline leg on), 1x MI355X
+open(f"{OUT}/{RND}_bench_default.md", "w").write(f"""# {RND} — `python bench.py --full` (steps 5, warm-up 2, CPU baseline leg on), 1x MI355X
 
 ```json
 {default}
@@ -58,7 +58,7 @@ tot = (d["all_kernels_total_bytes"]["fetch"] + d["all_kernels_total_bytes"]["wri
 rate = tot / dj["ms_per_step"]
 open(f"{OUT}/{RND}_pmc_bench.md", "w").write(f"""# {RND} — HBM traffic of the bench command from PMC counters (cfg3, 1x MI355X)
 
-`tools/pmc_bench.sh`: two passes of `rocprofv3 --pmc <counter> --kernel-trace -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-codec-leg`
+`tools/pmc_bench.sh`: two passes of `rocprofv3 --pmc <counter> --kernel-trace -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-codec-leg`
 (FETCH_SIZE and WRITE_SIZE do not fit one pass; no other trace domains), 3 forwards per pass, summarised per kernel by
 `tools/pmc_bench_summary.py` into `profiles/{RND}_pmc_bench.json` (which `bench.py` reads for `roofline.traffic` and
 `hbm_whole_step`). Units: FETCH_SIZE KiB x 1024 x 2 (gfx950: a 16-byte-per-lane streaming read is tallied at half, MI355X guide
@@ -74,7 +74,7 @@ Conv kernels: {d['conv_kernels_all']['dispatches']} dispatches, {d['conv_kernels
 """)
 codec = last(f"{G}/bench_codec_{tag}.json")
 csumm = subprocess.run([sys.executable, "tools/rocpd_summary.py", f"{G}/prof_codec_{tag}/trace_results.db", "--last-forwards", "2"], capture_output=True, text=True).stdout
-open(f"{OUT}/{RND}_rawcodec_kernel_stats.md", "w").write(f"""# {RND} — RAW codec leg: `python bench.py --model raw_compression_tcm_final --frames 8` (cfg5 shape on one GPU, bf16, 1x MI355X)
+open(f"{OUT}/{RND}_rawcodec_kernel_stats.md", "w").write(f"""# {RND} — RAW codec leg: `python bench.py --full --model raw_compression_tcm_final --frames 8` (cfg5 shape on one GPU, bf16, 1x MI355X)
 
 Default run (steps 5, warm-up 2, CPU baseline leg on):
 
@@ -82,7 +82,7 @@ Default run (steps 5, warm-up 2, CPU baseline leg on):
 {codec}
 ```
 
-Kernel trace: `rocprofv3 --kernel-trace --stats -- python bench.py --model raw_compression_tcm_final --frames 8 --steps 2 --warmup 1 --no-cpu-baseline`
+Kernel trace: `rocprofv3 --kernel-trace --stats -- python bench.py --full --model raw_compression_tcm_final --frames 8 --steps 2 --warmup 1 --no-cpu-baseline`
 (3 forwards of 8 frames in the trace; the table counts the LAST TWO -- steady state, weight packing and its copies are out), summarised with
 `tools/rocpd_summary.py --last-forwards 2`:
 
@@ -150,7 +150,7 @@ mf = f"{G}/pmc_mfma_{tag}.md"
 if os.path.exists(mf):
     open(f"{OUT}/{RND}_pmc_mfma_lds.md", "w").write(f"""# {RND} — matrix-pipe and LDS counters of the bench command (cfg3), `tools/pmc_mfma.sh`
 
-One `rocprofv3 --pmc <counter> --kernel-trace` pass per counter over `python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-codec-leg` (3 forwards; never combined
+One `rocprofv3 --pmc <counter> --kernel-trace` pass per counter over `python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-codec-leg` (3 forwards; never combined
 with other trace domains).  `SQ_VALU_MFMA_BUSY_CYCLES / (4 x SQ_BUSY_CU_CYCLES)` = fraction of the CUs' busy time in which a SIMD's matrix pipe is busy.
 
 {open(mf).read().strip()}
