@@ -11,7 +11,11 @@
  *   - plain pointers + sizes only; every pointer named d_* / in desc structs is DEVICE memory on
  *     the current HIP device unless the comment says "host".
  *   - activations are NHWC ("pixel-major"): element (b,y,x,c) at ((b*H + y)*W + x)*C + c.
- *   - dtype: RC_F32 (float) or RC_BF16 (bfloat16 storage, fp32 accumulate).
+ *   - dtype: RC_F32 (float) or RC_BF16 (bfloat16 storage, fp32 accumulate).  (ABI 15) RC_F16 (IEEE half storage, fp32
+ *     accumulate, values beyond +-65504 become inf) wherever the ISP path accepts RC_BF16: the bayer / ingest / layout
+ *     plumbing, rc_conv2d (not ksize 2, not the 32x32x16 forms) and its packers, the DWT, tail-fold, gate / FiLM / SFT,
+ *     resampling and colour-prior entry points.  Entry points off that path (codecs, GroupMix, Winograd, rc_conv_pair,
+ *     the register-resident layer chains) return RC_ERR_UNSUPPORTED / RC_ERR_INVALID ("bad dtype") for it.
  *   - all launches are asynchronous on `stream` (a hipStream_t passed as void*); no host sync, no
  *     allocation -> HIP-graph capturable.
  *   - return value: 0 on success, negative rc_status otherwise; rc_last_error() gives the text.
@@ -27,7 +31,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 14
+#define RC_ABI_VERSION 15
 
 typedef enum rc_status {
     RC_OK = 0,
@@ -36,7 +40,8 @@ typedef enum rc_status {
     RC_ERR_UNSUPPORTED = -3  /* valid request, but no kernel instantiation covers it */
 } rc_status;
 
-typedef enum rc_dtype { RC_F32 = 0, RC_BF16 = 1, RC_U16 = 2 /* sensor counts: rc_raw_ingest's mosaic only */ } rc_dtype;
+typedef enum rc_dtype { RC_F32 = 0, RC_BF16 = 1, RC_U16 = 2 /* sensor counts: rc_raw_ingest's mosaic only */,
+                        RC_F16 = 3 /* (ABI 15) IEEE binary16 storage, fp32 accumulate: the ISP path's entry points only */ } rc_dtype;
 
 typedef enum rc_act { RC_ACT_NONE = 0, RC_ACT_RELU = 1, RC_ACT_LEAKY = 2 /* slope in act_slope */,
                       RC_ACT_GELU = 3 /* exact erf GELU: nn.GELU() in groupmix.Mlp */,
@@ -50,13 +55,13 @@ typedef enum rc_out_mode {
     RC_OUT_NCHW = 2,           /* planar out[b][cout][y][x], cropped to (out_h,out_w); the network's
                                   final tensor (reference forward returns NCHW)                   */
     RC_OUT_PIXEL_SHUFFLE2_NCHW = 3, /* nn.PixelShuffle(2) + planar store: out[b][c][2y+i][2x+j] <- conv channel 4c+2i+j, cropped to
-                                  (out_h,out_w) <= (2 height, 2 width); out_dtype fp32 or bf16.  The folded tail's store
+                                  (out_h,out_w) <= (2 height, 2 width); out_dtype fp32 or the activation dtype.  The folded tail's store
                                   (rc_tail_fold_weights)                                          */
     RC_OUT_NHWC_DWT = 4        /* (ABI 14) the convolution followed by networks.DWTForward (models/networks.py:224-235, the `conv -> DWT`
                                   end of LiteISP's down1, models/LiteISP.py:1950-1953) in ONE launch: out is NHWC (height/2, width/2, 4 cout),
                                   out[b][y][x][4c+k] = sum_ij haar[k][i][j] * bf16(conv[b][2y+i][2x+j][c]) with the reference's frozen taps
                                   haar = .5 * {++++, ++--, +-+-, +--+}; the full-resolution map is never written.  Bit-identical to rc_conv2d
-                                  (RC_OUT_NHWC) + rc_dwt_forward with those taps.  bf16, ksize 3, one Cin chunk and one cout tile of 32 or
+                                  (RC_OUT_NHWC) + rc_dwt_forward with those taps.  bf16 or fp16 (rounded to that type), ksize 3, one Cin chunk and one cout tile of 32 or
                                   48 channels (the layers of the wave-autonomous kernel), even height / width, act NONE / RELU / LEAKY, or act NONE with a
                                   residual (NHWC, the conv's own shape: an RCAGroup's closing conv + group skip in front of the DWT, LiteISP down2);
                                   no film / mul_plus1 / gate / chan_sums: anything else is RC_ERR_UNSUPPORTED */
@@ -106,14 +111,14 @@ int rc_nhwc_to_nchw(const void* d_src, int src_dtype, void* d_dst, int dst_dtype
  */
 typedef struct rc_conv_desc {
     int32_t batch, height, width;   /* input spatial size == conv output size                     */
-    int32_t cin, cout, ksize;       /* ksize: 1 or 3 (zero padding ksize/2); 5 (cout <= 16; bf16 with cin % 48 == 0 or cin % 32 == 0, fp32 with cin % 16 == 0:
+    int32_t cin, cout, ksize;       /* ksize: 1 or 3 (zero padding ksize/2); 5 (cout <= 16; bf16 / fp16 with cin % 48 == 0 or cin % 32 == 0, fp32 with cin % 16 == 0:
                                        the folded tail, rc_tail_fold_weights);
-                                       2 (bf16, cin % 16 == 0, RC_OUT_NHWC only): the 2x2 window
+                                       2 (bf16 only, cin % 16 == 0, RC_OUT_NHWC only): the 2x2 window
                                        at pixel offsets {-1, 0}^2, weights (cout, cin, 2, 2) -- the non-zero taps of a stride-2 3x3
                                        convolution (compressai conv3x3(stride=2), ResidualBlockWithStride; models/tcm.py:336-345) taken
                                        over the rc_space_to_depth2 map of its input (9 of the 16 (tap, phase) weight blocks non-zero;
                                        the 3x3 embedding of the same convolution carries 36 blocks) */
-    int32_t dtype;                  /* rc_dtype of activations + packed weights                   */
+    int32_t dtype;                  /* rc_dtype of activations + packed weights: RC_F32, RC_BF16, RC_F16 */
     /* input x.  in_gate==NULL: x = in0.
      * in_gate!=NULL (CALayer gate + RCAB skip, networks.py:270,311): x = in0*gate[b][c] + in1 and,
      * if in_store!=NULL, x is also written there (it is the next block's skip tensor).           */
@@ -137,7 +142,7 @@ typedef struct rc_conv_desc {
     const void* residual;           /* NHWC (B,H,W,cout), activation dtype                        */
     void* out;
     int32_t out_mode;               /* rc_out_mode                                                */
-    int32_t out_dtype;              /* rc_dtype of `out` (RC_OUT_NCHW may emit fp32 from a bf16 net;
+    int32_t out_dtype;              /* rc_dtype of `out` (RC_OUT_NCHW may emit fp32 from a bf16 / fp16 net;
                                        other modes require out_dtype == dtype)                    */
     int32_t out_h, out_w;           /* RC_OUT_NCHW crop size (<= height,width), RC_OUT_PIXEL_SHUFFLE2_NCHW crop size (<= 2 height, 2 width); else ignored */
     /* optional per-channel partial sums of v (the value stored), for CALayer's global mean
@@ -207,7 +212,7 @@ size_t rc_conv_desc_size(void);
  * folded weights are structurally zero).  It does 19 200 instead of 88 128 MACs per packed pixel and the 2H x 2W x C intermediate map (6.4 GB
  * written + 7.7 GB read per 8 frames of 4K) never exists.
  *   rc_tail_fold_weights (host): w1 (4C,C,3,3), b1 (4C) or NULL, w2 (O,C,3,3), b2 (O) or NULL -> wc (4O,C,5,5), bc (4O); accumulated in
- *     double.  Run the result as rc_conv2d ksize 5 (4O <= 16; bf16 C = 48 k / 32 k, fp32 C = 16 k) with RC_OUT_PIXEL_SHUFFLE2_NCHW.
+ *     double.  Run the result as rc_conv2d ksize 5 (4O <= 16; bf16 / fp16 C = 48 k / 32 k, fp32 C = 16 k) with RC_OUT_PIXEL_SHUFFLE2_NCHW.
  * The fold is exact everywhere except the outermost ring of output pixels (the second convolution zero-pads the shuffled map; the fold sees
  * conv1 evaluated beyond the edge there).  The ring is recomputed with the two original convolutions on four thin strips:
  *   rc_tail_ring_gather : x NHWC (B,H,W,C) -> rows (2B,2,W,C) = [x[:,0:2], x[:,H-2:H]], cols (2B,2,H,C) = [x[:,:,0:2], x[:,:,W-2:W]] TRANSPOSED

@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from . import networks as N
 from . import ops
-from .groupmix import GMA_Block
+from .groupmix import GMA_Block, SUPPORTED_DTYPES
 from ._lib import RC_OUT_NCHW, RC_OUT_PIXEL_SHUFFLE2
 
 
@@ -719,6 +719,11 @@ class LiteISPNet_GFM_LSC_GMA(LiteISPNet_GFM_LSC):
         self.gma_in = N.Conv2d(c1, gma_dim, 1, 1, 0)
         self.gma = GMA_Block(gma_dim, gma_heads)
         self.gma_out = N.Conv2d(gma_dim, c1, 1, 1, 0)
+
+    def _act_dtype(self) -> torch.dtype:
+        dt = super()._act_dtype()
+        ops.require_dtype(self.head.weight, SUPPORTED_DTYPES, type(self).__name__)     # the GroupMix block has no fp16 kernels: refused before any launch
+        return dt
 
     def _refine_d1(self, d1):
         return self.gma._nhwc(d1, pre=self.gma_in, post=(self.gma_out, d1))          # gma_in + ConvPosEnc in the block's first launch, gma_out(GMA(.)) + d1 in its last

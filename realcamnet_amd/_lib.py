@@ -14,10 +14,10 @@ PKG = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["RC_HIP_LIB"]) if os.environ.get("RC_HIP_LIB") else PKG / "librealcam_hip.so"   # override: kernel experiments only
 HEADER = PKG.parent / "include" / "realcam_hip.h"
 
-RC_F32, RC_BF16, RC_U16 = 0, 1, 2
+RC_F32, RC_BF16, RC_U16, RC_F16 = 0, 1, 2, 3
 RC_ACT_NONE, RC_ACT_RELU, RC_ACT_LEAKY, RC_ACT_GELU, RC_ACT_RELU_POST = 0, 1, 2, 3, 4
 RC_OUT_NHWC, RC_OUT_PIXEL_SHUFFLE2, RC_OUT_NCHW, RC_OUT_PIXEL_SHUFFLE2_NCHW, RC_OUT_NHWC_DWT = 0, 1, 2, 3, 4
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class ConvDesc(C.Structure):

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/realcam_hip.h"
 
@@ -31,10 +32,14 @@ typedef __bf16 bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16_t;
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 template <typename T> struct dtype_of;
 template <> struct dtype_of<float> { static constexpr int value = RC_F32; };
 template <> struct dtype_of<bf16_t> { static constexpr int value = RC_BF16; };
+template <> struct dtype_of<f16_t> { static constexpr int value = RC_F16; };
 
 __host__ __device__ inline size_t dtype_size(int dt) { return dt == RC_F32 ? 4 : 2; }
 
@@ -86,6 +91,47 @@ template <> struct Vec16<bf16_t> {
     }
 };
 
+template <> struct Vec16<f16_t> {
+    static constexpr int N = 8;
+    __device__ static __forceinline__ float lo(uint32_t w) { return static_cast<float>(__builtin_bit_cast(f16_t, static_cast<uint16_t>(w))); }
+    __device__ static __forceinline__ float hi(uint32_t w) { return static_cast<float>(__builtin_bit_cast(f16_t, static_cast<uint16_t>(w >> 16))); }
+    __device__ static __forceinline__ void unpack(const uint4& raw, float* f) {
+        const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            f[2 * i] = lo(w[i]);
+            f[2 * i + 1] = hi(w[i]);
+        }
+    }
+    __device__ static __forceinline__ uint32_t rne(float v) {  // fp32 -> fp16 bits, round-nearest-even, overflow -> inf
+        return static_cast<uint32_t>(__builtin_bit_cast(uint16_t, static_cast<f16_t>(v)));
+    }
+    // two values per v_cvt_pk_f16_f32 (round-nearest-even; NOT v_cvt_pkrtz_f16_f32, which truncates).  The same HAZARD rule as
+    // Vec16<bf16_t>::rne2: never pass an MFMA accumulator or a transcendental result straight in.
+    __device__ static __forceinline__ uint32_t rne2(float lo, float hi) {
+        uint32_t r;
+        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+        return r;
+    }
+    __device__ static __forceinline__ uint4 pack(const float* f) {
+        uint32_t w[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[i] = rne2(f[2 * i], f[2 * i + 1]);
+        return make_uint4(w[0], w[1], w[2], w[3]);
+    }
+};
+
+// The two 16-bit values of a 32-bit word of T (bf16_t / f16_t) as floats, and back: the storage-type-generic forms of the
+// bf16 shift / mask idiom (`w << 16`, `w & 0xffff0000`), which the bf16 instantiations keep instruction for instruction.
+template <typename T> __device__ __forceinline__ float lo16(uint32_t w) {
+    if constexpr (__is_same(T, bf16_t)) return __uint_as_float(w << 16);
+    else return Vec16<T>::lo(w);
+}
+template <typename T> __device__ __forceinline__ float hi16(uint32_t w) {
+    if constexpr (__is_same(T, bf16_t)) return __uint_as_float(w & 0xffff0000u);
+    else return Vec16<T>::hi(w);
+}
+
 __host__ inline uint16_t host_f32_to_bf16(float f) {  // round-nearest-even, NaN preserved
     uint32_t u;
     __builtin_memcpy(&u, &f, 4);
@@ -93,6 +139,30 @@ __host__ inline uint16_t host_f32_to_bf16(float f) {  // round-nearest-even, NaN
     u += 0x7fffu + ((u >> 16) & 1u);
     return static_cast<uint16_t>(u >> 16);
 }
+
+__host__ inline uint16_t host_f32_to_f16(float f) {  // round-nearest-even, subnormals, overflow -> inf, NaN kept quiet (torch.Tensor.half())
+    uint32_t u;
+    __builtin_memcpy(&u, &f, 4);
+    const uint32_t sign = (u >> 16) & 0x8000u;
+    const uint32_t a = u & 0x7fffffffu;
+    if (a > 0x7f800000u) return static_cast<uint16_t>(sign | 0x7e00u | ((a >> 13) & 0x3ffu));     // NaN: quiet, payload's top bits
+    if (a >= 0x477ff000u) return static_cast<uint16_t>(sign | 0x7c00u);                           // >= 65520 (and inf): inf
+    if (a < 0x38800000u) {                                                                         // below 2^-14: fp16 subnormal or zero
+        if (a < 0x33000000u) return static_cast<uint16_t>(sign);                                   // <= 2^-25: rounds to zero (2^-25 itself: tie to even 0)
+        const uint32_t e = a >> 23, m = (a & 0x7fffffu) | 0x800000u;
+        const uint32_t shift = 126u - e;                                                           // value = m * 2^(e-150); unit 2^-24 -> shift by 126 - e
+        uint32_t r = m >> shift;
+        const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+        if (rem > half || (rem == half && (r & 1u))) ++r;
+        return static_cast<uint16_t>(sign | r);
+    }
+    uint32_t r = a - 0x38000000u;                                                                  // rebias exponent 127 -> 15 (in place, << 13)
+    r += 0xfffu + ((r >> 13) & 1u);
+    return static_cast<uint16_t>(sign | (r >> 13));
+}
+
+// Host converter of a 16-bit storage dtype (RC_BF16 / RC_F16).
+__host__ inline uint16_t host_f32_to_h16(float f, int dtype) { return dtype == RC_F16 ? host_f32_to_f16(f) : host_f32_to_bf16(f); }
 
 __device__ __forceinline__ float apply_act(float v, int act, float slope) {
     if (act == RC_ACT_RELU) return v > 0.f ? v : 0.f;

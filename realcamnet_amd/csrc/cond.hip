@@ -419,7 +419,7 @@ int rc_channel_sums_slots(int n_pix) {
 
 int rc_channel_sums(const void* d_x, int dtype, int batch, int n_pix, int c, float* d_sums, void* stream) {
     RC_REQUIRE(d_x && d_sums, "rc_channel_sums: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_channel_sums: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_channel_sums: bad dtype");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(batch >= 1 && batch <= 65535 && n_pix >= 1 && c >= U && c % U == 0 && c / U <= 256,
                "rc_channel_sums: C must be a multiple of 16 bytes, at most 256 vectors");
@@ -430,9 +430,12 @@ int rc_channel_sums(const void* d_x, int dtype, int batch, int n_pix, int c, flo
     if (dtype == RC_F32)
         hipLaunchKernelGGL(channel_sums_kernel<float>, dim3(slots, batch), dim3(256), lds, as_stream(stream),
                            static_cast<const float*>(d_x), d_sums, n_pix, c, L);
-    else
+    else if (dtype == RC_BF16)
         hipLaunchKernelGGL(channel_sums_kernel<bf16_t>, dim3(slots, batch), dim3(256), lds, as_stream(stream),
                            static_cast<const bf16_t*>(d_x), d_sums, n_pix, c, L);
+    else
+        hipLaunchKernelGGL(channel_sums_kernel<f16_t>, dim3(slots, batch), dim3(256), lds, as_stream(stream),
+                           static_cast<const f16_t*>(d_x), d_sums, n_pix, c, L);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }
@@ -464,7 +467,7 @@ int rc_ca_gate_ahead(float* d_sums, int batch, int n_tiles, int c, int cr, const
                      const float* d_w2t, const float* d_b2, const float* d_w0, const float* d_b0, const float* d_w1, const float* d_b1,
                      float* d_scratch, float* d_gate, void* stream) {
     RC_REQUIRE(d_sums && d_t && d_w2t && d_w0 && d_b0 && d_w1 && d_b1 && d_scratch && d_gate, "rc_ca_gate_ahead: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_ca_gate_ahead: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_ca_gate_ahead: bad dtype");
     RC_REQUIRE(batch >= 1 && batch <= 65535 && n_tiles >= 1 && c >= 1 && cr >= 1 && H >= 1 && W >= 1, "rc_ca_gate_ahead: bad shape");
     const size_t lds = (kGateThreads + 10 * (size_t)c + cr) * sizeof(float);
     RC_REQUIRE(lds <= 64 * 1024, "rc_ca_gate_ahead: too many channels");
@@ -480,9 +483,12 @@ int rc_ca_gate_ahead(float* d_sums, int batch, int n_tiles, int c, int cr, const
     if (dtype == RC_F32)
         hipLaunchKernelGGL(ca_reduce_border_kernel<float>, dim3(n_red + 4 * kEdgeSegs, batch), dim3(256), 0, as_stream(stream), d_sums, n_tiles, c, L, n_red,
                            static_cast<const float*>(d_t), edge, corner, H, W);
-    else
+    else if (dtype == RC_BF16)
         hipLaunchKernelGGL(ca_reduce_border_kernel<bf16_t>, dim3(n_red + 4 * kEdgeSegs, batch), dim3(256), 0, as_stream(stream), d_sums, n_tiles, c, L, n_red,
                            static_cast<const bf16_t*>(d_t), edge, corner, H, W);
+    else
+        hipLaunchKernelGGL(ca_reduce_border_kernel<f16_t>, dim3(n_red + 4 * kEdgeSegs, batch), dim3(256), 0, as_stream(stream), d_sums, n_tiles, c, L, n_red,
+                           static_cast<const f16_t*>(d_t), edge, corner, H, W);
     hipLaunchKernelGGL(ca_gate_ahead_kernel, dim3(batch), dim3(kGateThreads), lds, as_stream(stream), d_sums, slots, stride, (size_t)n_tiles * c,
                        edge, corner, d_w2t, d_b2, c, cr, 1.0f / ((float)H * (float)W), d_w0, d_b0, d_w1, d_b1, d_gate);
     RC_HIP_CHECK(hipGetLastError());
@@ -494,7 +500,7 @@ int rc_color_block(const void* d_x, int x_dtype, float* d_y, int batch, int cin,
                    const float* d_in_gamma, const float* d_in_beta, void* stream) {
     RC_REQUIRE(d_x && d_y && d_w && d_b, "rc_color_block: null pointer");
     RC_REQUIRE(batch >= 1 && cin >= 1 && cout >= 1 && h >= 1 && w >= 1, "rc_color_block: bad shape");
-    RC_REQUIRE(x_dtype == RC_F32 || x_dtype == RC_BF16, "rc_color_block: bad dtype");
+    RC_REQUIRE(x_dtype == RC_F32 || x_dtype == RC_BF16 || x_dtype == RC_F16, "rc_color_block: bad dtype");
     if (d_in_mean) RC_REQUIRE(d_in_rstd && d_in_gamma && d_in_beta, "rc_color_block: incomplete InstanceNorm arguments");
     const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
     const size_t lds = ((size_t)cin + 1) * CB_PX * sizeof(float);
@@ -503,6 +509,7 @@ int rc_color_block(const void* d_x, int x_dtype, float* d_y, int batch, int cin,
     if (!attr.test_and_set()) {
         RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&color_block_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
         RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&color_block_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
+        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&color_block_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
     }
     const size_t g = (size_t)batch * (((size_t)ho * wo + CB_PX - 1) / CB_PX);
     RC_REQUIRE(g < (1ull << 31), "rc_color_block: too many tiles");
@@ -513,9 +520,13 @@ int rc_color_block(const void* d_x, int x_dtype, float* d_y, int batch, int cin,
         hipLaunchKernelGGL(color_block_kernel<float>, dim3((unsigned)g, (unsigned)slices), dim3(256), lds, as_stream(stream),
                            static_cast<const float*>(d_x), d_y, batch, cin, cout, h, w, ho, wo, d_w, d_b,
                            d_in_mean, d_in_rstd, d_in_gamma, d_in_beta);
-    else
+    else if (x_dtype == RC_BF16)
         hipLaunchKernelGGL(color_block_kernel<bf16_t>, dim3((unsigned)g, (unsigned)slices), dim3(256), lds, as_stream(stream),
                            static_cast<const bf16_t*>(d_x), d_y, batch, cin, cout, h, w, ho, wo, d_w, d_b,
+                           d_in_mean, d_in_rstd, d_in_gamma, d_in_beta);
+    else
+        hipLaunchKernelGGL(color_block_kernel<f16_t>, dim3((unsigned)g, (unsigned)slices), dim3(256), lds, as_stream(stream),
+                           static_cast<const f16_t*>(d_x), d_y, batch, cin, cout, h, w, ho, wo, d_w, d_b,
                            d_in_mean, d_in_rstd, d_in_gamma, d_in_beta);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;

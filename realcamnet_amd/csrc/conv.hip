@@ -30,16 +30,17 @@ static int g_conv32 = 0;           // rc_debug_set("conv32", v): which layers ta
 // Must mirror ConvCfg<> (static_asserts in check_plan_consistency below keep them in lock-step).
 static bool make_plan(int cin, int cout, int ksize, int dtype, int out_mode, ConvPlan* p, int cout_tile = 0) {
     if (cin < 1 || cout < 1 || (ksize != 1 && ksize != 3 && ksize != 2 && ksize != 5)) return false;
-    if (dtype != RC_F32 && dtype != RC_BF16) return false;
-    // ksize 5: the folded tail (rc_tail_fold_weights): one 16-wide cout tile; bf16 with 48 k or 32 k input channels, fp32 with 16 k
-    if (ksize == 5 && (cout > 16 || out_mode == RC_OUT_PIXEL_SHUFFLE2 || (dtype == RC_BF16 ? (cin % 48 != 0 && cin % 32 != 0) : cin % 16 != 0))) return false;
+    if (dtype != RC_F32 && dtype != RC_BF16 && dtype != RC_F16) return false;
+    const bool h16 = dtype != RC_F32;        // RC_F16 is planned exactly as RC_BF16 (same bytes per element, same MFMA shapes)
+    // ksize 5: the folded tail (rc_tail_fold_weights): one 16-wide cout tile; bf16 / fp16 with 48 k or 32 k input channels, fp32 with 16 k
+    if (ksize == 5 && (cout > 16 || out_mode == RC_OUT_PIXEL_SHUFFLE2 || (h16 ? (cin % 48 != 0 && cin % 32 != 0) : cin % 16 != 0))) return false;
     if (out_mode == RC_OUT_PIXEL_SHUFFLE2_NCHW && cout % 4 != 0) return false;
     // ksize 2: the 2x2 window at pixel offsets {-1, 0}^2 = the non-zero taps of a stride-2 3x3 convolution over its space-to-depth map
-    // (bf16, Cin a multiple of 16 that is not routed to the 8- / 48- / 80-wide chunk forms; plain NHWC store)
+    // (bf16 only: a codec form; Cin a multiple of 16 that is not routed to the 8- / 48- / 80-wide chunk forms; plain NHWC store)
     if (ksize == 2 && (dtype != RC_BF16 || cin % 16 != 0 || out_mode != RC_OUT_NHWC || (cin % 48 == 0 && cin % 64 != 0))) return false;
     p->unit = dtype == RC_F32 ? 4 : 8;
-    if (ksize == 5) p->ck = dtype == RC_BF16 ? (cin % 48 == 0 ? 48 : 32) : 16;      // 25 taps: chunks that keep halo tile + weights inside 80 KB of LDS
-    else if (dtype == RC_BF16) {
+    if (ksize == 5) p->ck = h16 ? (cin % 48 == 0 ? 48 : 32) : 16;      // 25 taps: chunks that keep halo tile + weights inside 80 KB of LDS
+    else if (h16) {
         if (cin <= 8) p->ck = 8;
         else if (ksize == 1 && cin % 80 == 0 && cin % 64 != 0) p->ck = 80;   // GroupMix dims (80, 240, 320 -> 64)
         else if (ksize >= 2 && cin % 64 == 0 && cin > 64) p->ck = 32;         // multi-chunk layers: 32-channel chunks so two
@@ -58,17 +59,17 @@ static bool make_plan(int cin, int cout, int ksize, int dtype, int out_mode, Con
         // a cout tile = one sub-pixel x 16*NT consecutive OUT channels, so stores write whole pixel records
         if (cout % 4 != 0) return false;
         const int cps = cout / 4;
-        if (cps % 64 == 0 && !(cps % 48 == 0 && dtype == RC_BF16 && cin == 48)) p->nt = 4;
+        if (cps % 64 == 0 && !(cps % 48 == 0 && h16 && cin == 48)) p->nt = 4;
         else if (cps % 48 == 0) p->nt = 3;
         else if (cps % 64 == 0) p->nt = 4;
         else if (cps % 16 == 0) p->nt = 1;
         else return false;
-    } else if (cout % 48 == 0 && dtype == RC_BF16 && cin == 48) p->nt = 3;
-    else if (dtype == RC_BF16 && ksize == 3 && cin == 32 && cout == 32) p->nt = 2;   // 32 -> 32: one 32-wide cout tile, three persistent blocks per CU
+    } else if (cout % 48 == 0 && h16 && cin == 48) p->nt = 3;
+    else if (h16 && ksize == 3 && cin == 32 && cout == 32) p->nt = 2;   // 32 -> 32: one 32-wide cout tile, three persistent blocks per CU
     else if (ksize == 1 && cout % 80 == 0) p->nt = 5;          // 80-wide cout tiles for the GroupMix Linears
     else if (cout % 64 == 0) p->nt = 4;
     else if (cout % 48 == 0) p->nt = 3;
-    else if (dtype == RC_BF16 && ksize == 3 && p->ck == 32 && cout % 32 == 0) p->nt = 2;   // e.g. the codec's 320..640 -> 224 slice transforms: 7 exact 32-wide tiles instead of 14
+    else if (h16 && ksize == 3 && p->ck == 32 && cout % 32 == 0) p->nt = 2;   // e.g. the codec's 320..640 -> 224 slice transforms: 7 exact 32-wide tiles instead of 14
                                                                                              // 16-wide ones (each re-staging the input): 286 -> 192 us at 576 -> 224, 8 x 72 x 120 (tools/cout_tile_probe.py)
     else p->nt = 1;
     // Caller-chosen cout tile width (rc_conv_desc.cout_tile, the *_ct packers): narrower tiles = more blocks for the general kernel on maps too small to fill the chip
@@ -81,7 +82,7 @@ static bool make_plan(int cin, int cout, int ksize, int dtype, int out_mode, Con
     // 32x32x16 form: 3x3 bf16 layers whose weights are streamed (several 32-channel chunks, or the one-chunk 48 -> 192 layers) and whose
     // couts fill whole 32-row tiles.  The packed order differs, so the choice depends on the shape and on the `conv32` knob ONLY (not on `persist`:
     // a 32x32x16 layer runs its own kernel in every persist mode) -- weights packed under one conv32 setting must not be used under another
-    // (rc_debug_get("conv32") is part of the host mirror's pack-cache key).
+    // (rc_debug_get("conv32") is part of the host mirror's pack-cache key).  bf16 only: fp16 layers stay on the 16x16x32 kernels in every conv32 mode.
     p->m32 = 0;
     if (cout_tile == 0 && dtype == RC_BF16 && ksize == 3 && g_conv32 != 0 && cout <= kPersistMaxCout && out_mode != RC_OUT_NCHW && out_mode != RC_OUT_PIXEL_SHUFFLE2_NCHW) {
         const int cw = out_mode == RC_OUT_PIXEL_SHUFFLE2 ? cout / 4 : cout;          // channels a lane's 16-value run must tile
@@ -233,7 +234,7 @@ int rc_conv_pack_weights_ct(const float* w, int cin, int cout, int ksize, int dt
                             if (dtype == RC_F32) {
                                 *reinterpret_cast<float*>(out) = val; out += 4;
                             } else {
-                                *reinterpret_cast<uint16_t*>(out) = host_f32_to_bf16(val); out += 2;
+                                *reinterpret_cast<uint16_t*>(out) = host_f32_to_h16(val, dtype); out += 2;
                             }
                         }
                     }
@@ -380,8 +381,8 @@ static int conv_build_args(const rc_conv_desc* d, ConvPlan& p, ConvArgs& a, size
         RC_REQUIRE(d->out_dtype == d->dtype && reinterpret_cast<uintptr_t>(d->out) % 16 == 0, "rc_conv2d: RC_OUT_NHWC_DWT: out_dtype must equal dtype, out 16-byte aligned");
         RC_REQUIRE(!d->mul_plus1 && !d->film_scale && !d->out_scale && !d->chan_sums && !d->in_gate && !d->in1 && !d->in_store && !d->src_h && !d->src_w && !d->cout_tile,
                    "rc_conv2d: RC_OUT_NHWC_DWT excludes mul_plus1 / film / out_scale / chan_sums / gated input / src_h / cout_tile");
-        if (d->dtype != RC_BF16 || d->ksize != 3 || p.m32 || !(d->act == RC_ACT_NONE || ((d->act == RC_ACT_RELU || d->act == RC_ACT_LEAKY) && !d->residual)))
-            return fail(RC_ERR_UNSUPPORTED, "rc_conv2d: RC_OUT_NHWC_DWT is a bf16 3x3 form with act NONE / RELU / LEAKY, or act NONE + residual");
+        if (d->dtype == RC_F32 || d->ksize != 3 || p.m32 || !(d->act == RC_ACT_NONE || ((d->act == RC_ACT_RELU || d->act == RC_ACT_LEAKY) && !d->residual)))
+            return fail(RC_ERR_UNSUPPORTED, "rc_conv2d: RC_OUT_NHWC_DWT is a bf16 / fp16 3x3 form with act NONE / RELU / LEAKY, or act NONE + residual");
     }
     RC_REQUIRE(d->act >= RC_ACT_NONE && d->act <= RC_ACT_RELU_POST, "rc_conv2d: bad act");
     RC_REQUIRE(d->act != RC_ACT_RELU_POST || (d->residual != nullptr && d->mul_plus1 == nullptr && d->film_scale == nullptr && d->chan_sums == nullptr),
@@ -397,13 +398,14 @@ static int conv_build_args(const rc_conv_desc* d, ConvPlan& p, ConvArgs& a, size
         RC_REQUIRE(reinterpret_cast<uintptr_t>(d->out_scale) % 4 == 0, "rc_conv2d: out_scale must be 4-byte aligned");
     }
     const size_t es = dtype_size(d->dtype);
+    const int planar16 = d->dtype == RC_F16 ? RC_F16 : RC_BF16;        // the 16-bit planar store: the activation type (bf16 from an fp32 net)
     if (dwt) {
         // validated above; the store is whole 16-byte pieces of (H / 2, W / 2, 4 cout) pixel records
     } else if (d->out_mode == RC_OUT_NHWC) {
         RC_REQUIRE(d->out_dtype == d->dtype, "rc_conv2d: out_dtype must equal dtype for RC_OUT_NHWC");
         RC_REQUIRE(!full_tiles || (d->cout * es) % 8 == 0, "rc_conv2d: cout*elem_size must be a multiple of 8 bytes for RC_OUT_NHWC");
         RC_REQUIRE(reinterpret_cast<uintptr_t>(d->out) % 16 == 0, "rc_conv2d: out must be 16-byte aligned");
-        if (p.nt == 4 && d->dtype == RC_BF16) RC_REQUIRE(d->cout % 8 == 0, "rc_conv2d: cout % 8");
+        if (p.nt == 4 && d->dtype != RC_F32) RC_REQUIRE(d->cout % 8 == 0, "rc_conv2d: cout % 8");
     } else if (d->out_mode == RC_OUT_PIXEL_SHUFFLE2) {
         RC_REQUIRE(d->out_dtype == d->dtype, "rc_conv2d: out_dtype must equal dtype for RC_OUT_PIXEL_SHUFFLE2");
         RC_REQUIRE(full_tiles && ((d->cout / 4) * es) % 8 == 0, "rc_conv2d: pixel-shuffle store needs (cout/4)*elem_size % 8 == 0");
@@ -411,12 +413,12 @@ static int conv_build_args(const rc_conv_desc* d, ConvPlan& p, ConvArgs& a, size
         RC_REQUIRE(reinterpret_cast<uintptr_t>(d->out) % 16 == 0, "rc_conv2d: out must be 16-byte aligned");
     } else if (d->out_mode == RC_OUT_PIXEL_SHUFFLE2_NCHW) {
         RC_REQUIRE(d->out_h >= 1 && d->out_h <= 2 * d->height && d->out_w >= 1 && d->out_w <= 2 * d->width, "rc_conv2d: bad pixel-shuffle NCHW crop");
-        RC_REQUIRE(d->out_dtype == RC_F32 || d->out_dtype == RC_BF16, "rc_conv2d: bad out_dtype");
+        RC_REQUIRE(d->out_dtype == RC_F32 || d->out_dtype == planar16, "rc_conv2d: bad out_dtype");
         RC_REQUIRE(!d->chan_sums, "rc_conv2d: chan_sums needs RC_OUT_NHWC");
         RC_REQUIRE((double)d->out_h * d->out_w * (d->cout / 4) * 4.0 < 2147483647.0, "rc_conv2d: one output image must be < 2 GiB");
     } else {
         RC_REQUIRE(d->out_h >= 1 && d->out_h <= d->height && d->out_w >= 1 && d->out_w <= d->width, "rc_conv2d: bad NCHW crop");
-        RC_REQUIRE(d->out_dtype == RC_F32 || d->out_dtype == RC_BF16, "rc_conv2d: bad out_dtype");
+        RC_REQUIRE(d->out_dtype == RC_F32 || d->out_dtype == planar16, "rc_conv2d: bad out_dtype");
     }
     {   // buffer descriptors use signed 32-bit byte offsets inside one image
         const double lim = 2147483647.0;
@@ -508,7 +510,7 @@ int rc_conv2d(const rc_conv_desc* d, void* stream_) {
                          px * d->cout * es * ((d->residual ? 1.0 : 0.0) + (d->mul_plus1 ? 1.0 : 0.0));
     conv_prof_begin(2.0 * px * (double)d->cin * d->cout * taps, stream, &tok, bytes, d->cin, d->cout, d->ksize);
     const int rcode = p.m32 ? (p.ck == 16 ? conv32_ck16(0, a, stream) : p.ck == 32 ? conv32_ck32(g_conv32 == 3 ? 1 : 0, a, stream) : conv32_ck48(0, a, stream))
-                            : dispatch_conv(d->dtype == RC_BF16, d->ksize, p.ck, p.nt, a, stream);
+                            : dispatch_conv(d->dtype, d->ksize, p.ck, p.nt, a, stream);
     conv_prof_end(tok, stream);
     return rcode;
 }
@@ -523,7 +525,7 @@ int rc_conv_sum_slots(const rc_conv_desc* d) {
     if (p.m32) return legacy;                                  // the 32x32x16 forms write the per-tile layout
     int q[2] = {0, legacy};
     a.query = q;                                               // the launcher reports the branch it would take and launches nothing
-    if (dispatch_conv(d->dtype == RC_BF16, d->ksize, p.ck, p.nt, a, nullptr) != RC_OK) return -1;
+    if (dispatch_conv(d->dtype, d->ksize, p.ck, p.nt, a, nullptr) != RC_OK) return -1;
     return q[1];
 }
 

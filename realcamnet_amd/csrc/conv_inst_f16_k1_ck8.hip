@@ -1,0 +1,10 @@
+// Instantiations of the MFMA conv kernels: f16_t, 1x1, 8-channel Cin chunks (no 80-wide cout tiles: those serve the GroupMix Linears, which have no fp16 form).
+#include "conv_kernel.hpp"
+namespace rc {
+int conv_f16_k1_ck8(int nt, const ConvArgs& a, hipStream_t s) {
+    if (nt == 1) return launch_conv<ConvCfg<f16_t, 8, 1, 1>>(a, s);
+    if (nt == 3) return launch_conv<ConvCfg<f16_t, 8, 3, 1>>(a, s);
+    if (nt == 4) return launch_conv<ConvCfg<f16_t, 8, 4, 1>>(a, s);
+    return fail(RC_ERR_UNSUPPORTED, "conv: no kernel instantiation for this cout tile width");
+}
+}  // namespace rc

@@ -153,6 +153,11 @@ template <> struct Mma<bf16_t> {
         acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0, 0, 0);
     }
 };
+template <> struct Mma<f16_t> {     // the same A/B and C/D lane maps as the bf16 form: only the element type differs
+    __device__ static __forceinline__ void run(const uint4& w, const uint4& x, f32x4& acc) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), acc, 0, 0, 0);
+    }
+};
 template <> struct Mma<float> {
     __device__ static __forceinline__ void run(const uint4& w, const uint4& x, f32x4& acc) {
         acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(w.x), __uint_as_float(x.x), acc, 0, 0, 0);
@@ -165,11 +170,15 @@ template <> struct Mma<float> {
 __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
     return Vec16<bf16_t>::rne2(lo, hi);
 }
+// two values of a 16-bit storage type T (bf16_t / f16_t) in one word, round-nearest-even (Vec16<T>::rne2: the same hazard rule)
+template <typename T> __device__ __forceinline__ unsigned pack16x2(float lo, float hi) {
+    return Vec16<T>::rne2(lo, hi);
+}
 
 // Store / load NV consecutive elements of type TT at byte offset voff of a buffer (OOB -> dropped / 0).
-// bf16: values are converted in pairs (v_cvt_pk_bf16_f32) and written with the widest pieces that fit
+// bf16 / fp16: values are converted in pairs (v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32) and written with the widest pieces that fit
 // (24 bytes = 16 + 8).  PK_RELU applies max(x, 0) to the packed pairs: signed 16-bit max with 0 equals
-// max(x, +0) on bf16 bit patterns, one VALU op per two values.
+// max(x, +0) on bf16 and fp16 bit patterns alike (sign in bit 15), one VALU op per two values.
 template <typename TT, int NV, bool PK_RELU>
 __device__ __forceinline__ void buf_store_row(__amdgpu_buffer_rsrc_t r, int voff, const float* v) {
     if constexpr (sizeof(TT) == 4) {
@@ -182,7 +191,7 @@ __device__ __forceinline__ void buf_store_row(__amdgpu_buffer_rsrc_t r, int voff
         unsigned w[NV / 2];
 #pragma unroll
         for (int i = 0; i < NV / 2; ++i) {
-            w[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
+            w[i] = pack16x2<TT>(v[2 * i], v[2 * i + 1]);
             if constexpr (PK_RELU) {
                 typedef short s16x2 __attribute__((ext_vector_type(2)));
                 const s16x2 z = {0, 0};
@@ -210,8 +219,8 @@ __device__ __forceinline__ void buf_load_row(__amdgpu_buffer_rsrc_t r, int voff,
 #pragma unroll
         for (int i = 0; i < NV; i += 4) {
             const u32x2_t p = __builtin_amdgcn_raw_buffer_load_b64(r, voff + 2 * i, 0, 0);
-            v[i] = __uint_as_float(p.x << 16); v[i + 1] = __uint_as_float(p.x & 0xffff0000u);
-            v[i + 2] = __uint_as_float(p.y << 16); v[i + 3] = __uint_as_float(p.y & 0xffff0000u);
+            v[i] = lo16<TT>(p.x); v[i + 1] = hi16<TT>(p.x);
+            v[i + 2] = lo16<TT>(p.y); v[i + 3] = hi16<TT>(p.y);
         }
     }
 }
@@ -237,6 +246,7 @@ __device__ __forceinline__ void band_decode(int idx, int tiles_x, int tiles_y, c
 template <class Cfg>
 struct ConvDev {
     using T = typename Cfg::elem;
+    using TS = typename std::conditional<sizeof(T) == 4, bf16_t, T>::type;   // a 16-bit planar store (out_dtype != RC_F32): the activation type; bf16 from fp32
     static constexpr int CK = Cfg::CK, NT = Cfg::NT, KS = Cfg::KS, UNIT = Cfg::UNIT, UPT = Cfg::UPT, TAPS = Cfg::TAPS;
     static constexpr int STEPS = Cfg::STEPS, HALO = Cfg::HALO, THH = Cfg::THH, TWH = Cfg::TWH;
     static constexpr int SPIX = Cfg::SPIX, NV = 4 * NT, ES = (int)sizeof(T);
@@ -890,8 +900,8 @@ struct ConvDev {
             for (int e = 0; e < NV; ++e) v[e] *= gs[e];
 #pragma unroll
             for (int i = 0; i < NRH; ++i) {
-                v[2 * i] += __uint_as_float(rp[pt][i] << 16);
-                v[2 * i + 1] += __uint_as_float(rp[pt][i] & 0xffff0000u);
+                v[2 * i] += lo16<T>(rp[pt][i]);
+                v[2 * i + 1] += hi16<T>(rp[pt][i]);
             }
             const int oo = (valid && !(a.dbg_flags & 1)) ? off0 + dy * row_b + dx * col_b : kOOB;
             buf_store_row<T, NV, false>(r_out, oo, v);
@@ -961,8 +971,8 @@ struct ConvDev {
             if constexpr ((F & EP_RES) != 0) {
 #pragma unroll
                 for (int i = 0; i < NRH; ++i) {
-                    v[2 * i] += __uint_as_float(rp[p][i] << 16);
-                    v[2 * i + 1] += __uint_as_float(rp[p][i] & 0xffff0000u);
+                    v[2 * i] += lo16<T>(rp[p][i]);
+                    v[2 * i + 1] += hi16<T>(rp[p][i]);
                 }
             }
             if constexpr ((F & EP_SUMS) != 0) {
@@ -1016,14 +1026,14 @@ struct ConvDev {
             if constexpr ((F & EP_RES) != 0) {
 #pragma unroll
                 for (int i = 0; i < NV / 2; ++i) {
-                    v[2 * i] += __uint_as_float(rp[pt][i] << 16);
-                    v[2 * i + 1] += __uint_as_float(rp[pt][i] & 0xffff0000u);
+                    v[2 * i] += lo16<T>(rp[pt][i]);
+                    v[2 * i + 1] += hi16<T>(rp[pt][i]);
                 }
             }
             char* dst = st + (pt >> 1) * ROW + (16 * (pt & 1) + n) * REC + q * (NV * 2);
 #pragma unroll
             for (int i = 0; i < NV / 4; ++i)
-                *reinterpret_cast<uint2*>(dst + 8 * i) = make_uint2(pack_bf16x2(v[4 * i], v[4 * i + 1]), pack_bf16x2(v[4 * i + 2], v[4 * i + 3]));
+                *reinterpret_cast<uint2*>(dst + 8 * i) = make_uint2(pack16x2<T>(v[4 * i], v[4 * i + 1]), pack16x2<T>(v[4 * i + 2], v[4 * i + 3]));
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");             // other lanes' writes are read back below: keep the compiler from moving the
         __builtin_amdgcn_wave_barrier();                                   // reads above them (the LDS queue itself is in order)
@@ -1034,8 +1044,8 @@ struct ConvDev {
 #pragma unroll
             for (int i = 0; i < NV / 4; ++i) {
                 const uint2 w = *reinterpret_cast<const uint2*>(src + (t >> 1) * ROW + (t & 1) * REC + 8 * i);
-                in[t][2 * i] = f32x2{__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u)} * 0.5f;
-                in[t][2 * i + 1] = f32x2{__uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u)} * 0.5f;
+                in[t][2 * i] = f32x2{lo16<T>(w.x), hi16<T>(w.x)} * 0.5f;
+                in[t][2 * i + 1] = f32x2{lo16<T>(w.y), hi16<T>(w.y)} * 0.5f;
             }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");             // ... and the next strip's commit (same buffer) below these reads
         __builtin_amdgcn_wave_barrier();
@@ -1045,8 +1055,8 @@ struct ConvDev {
             const f32x2 sab = in[0][p] + in[1][p], dab = in[0][p] - in[1][p];
             const f32x2 k0 = (sab + in[2][p]) + in[3][p], k1 = (sab - in[2][p]) - in[3][p];
             const f32x2 k2 = (dab + in[2][p]) - in[3][p], k3 = (dab - in[2][p]) + in[3][p];
-            o[4 * p] = pack_bf16x2(k0.x, k1.x); o[4 * p + 1] = pack_bf16x2(k2.x, k3.x);
-            o[4 * p + 2] = pack_bf16x2(k0.y, k1.y); o[4 * p + 3] = pack_bf16x2(k2.y, k3.y);
+            o[4 * p] = pack16x2<T>(k0.x, k1.x); o[4 * p + 1] = pack16x2<T>(k2.x, k3.x);
+            o[4 * p + 2] = pack16x2<T>(k0.y, k1.y); o[4 * p + 3] = pack16x2<T>(k2.y, k3.y);
         }
         const int Hh = a.H >> 1, Wh = a.W >> 1, oy = (y0 >> 1) + wave, ox = (x0 >> 1) + n;
         const size_t img_out = (size_t)a.H * a.W * a.cout;                  // (H / 2) (W / 2) (4 cout): the same bytes per image
@@ -1149,7 +1159,7 @@ struct ConvDev {
                     for (int e = 0; e < NV; ++e) {
                         const int o = (valid && jbase + e < a.cout) ? pix_off + e * ES : kOOB;
                         if constexpr (ES == 4) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[e]), r_out, o, 0, 0);
-                        else __builtin_amdgcn_raw_buffer_store_b16((unsigned short)Vec16<bf16_t>::rne(v[e]), r_out, o, 0, 0);
+                        else __builtin_amdgcn_raw_buffer_store_b16((unsigned short)Vec16<T>::rne(v[e]), r_out, o, 0, 0);
                     }
                 }
             } else if (a.out_mode == RC_OUT_PIXEL_SHUFFLE2) {
@@ -1176,10 +1186,10 @@ struct ConvDev {
                                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v1), r_out, in1 ? idx * 4 + 4 : kOOB, 0, 0);
                             }
                         } else {
-                            if (pair_ok) __builtin_amdgcn_raw_buffer_store_b32(pack_bf16x2(v0, v1), r_out, in1 ? idx * 2 : kOOB, 0, 0);
+                            if (pair_ok) __builtin_amdgcn_raw_buffer_store_b32(pack16x2<TS>(v0, v1), r_out, in1 ? idx * 2 : kOOB, 0, 0);
                             else {
-                                __builtin_amdgcn_raw_buffer_store_b16((unsigned short)Vec16<bf16_t>::rne(v0), r_out, in0 ? idx * 2 : kOOB, 0, 0);
-                                __builtin_amdgcn_raw_buffer_store_b16((unsigned short)Vec16<bf16_t>::rne(v1), r_out, in1 ? idx * 2 + 2 : kOOB, 0, 0);
+                                __builtin_amdgcn_raw_buffer_store_b16((unsigned short)Vec16<TS>::rne(v0), r_out, in0 ? idx * 2 : kOOB, 0, 0);
+                                __builtin_amdgcn_raw_buffer_store_b16((unsigned short)Vec16<TS>::rne(v1), r_out, in1 ? idx * 2 + 2 : kOOB, 0, 0);
                             }
                         }
                     }
@@ -1193,7 +1203,7 @@ struct ConvDev {
                     if (a.out_dtype == RC_F32)
                         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[e]), r_out, (inside && co < a.cout) ? idx * 4 : kOOB, 0, 0);
                     else
-                        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)Vec16<bf16_t>::rne(v[e]), r_out, (inside && co < a.cout) ? idx * 2 : kOOB, 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)Vec16<TS>::rne(v[e]), r_out, (inside && co < a.cout) ? idx * 2 : kOOB, 0, 0);
                 }
             }
         }
@@ -2234,7 +2244,7 @@ __global__ __launch_bounds__(kWsmThreads) void conv_mfma_pss_kernel(const ConvAr
                     float v0 = acc[pt][(2 * i) >> 2][(2 * i) & 3], v1 = acc[pt][(2 * i + 1) >> 2][(2 * i + 1) & 3];
                     if (key == D::EP_RELU) { v0 = __builtin_amdgcn_fmed3f(v0, 0.f, inf); v1 = __builtin_amdgcn_fmed3f(v1, 0.f, inf); }
                     else if (key == D::EP_LEAKY) { v0 = __builtin_amdgcn_fmed3f(v0, v0 * a.act_slope, inf); v1 = __builtin_amdgcn_fmed3f(v1, v1 * a.act_slope, inf); }
-                    pend[pt][i] = pack_bf16x2(v0, v1);
+                    pend[pt][i] = pack16x2<T>(v0, v1);
                 }
             __syncthreads();
         }
@@ -2467,7 +2477,7 @@ template <class Cfg>
 constexpr int auto64_lds_bytes() { return (int)Cfg::CHUNK_W_BYTES + (kAutoBias + kAutoGate) * 4 + kAutoWaves * kA64STRIP; }
 
 // one MFMA step with the next step's fragment reads interleaved (kernel 7): 4 weight + 2 pixel fragments, 8 MFMAs
-template <int I, bool NEXT, int NT>
+template <typename T, int I, bool NEXT, int NT>
 __device__ __forceinline__ void a64_step(int s, const char* s_my, const char* s_w, int lane_w, const int (&xo)[3][2], const uint4 (&wf)[NT], const uint4 (&xf)[2],
                                          uint4 (&wfn)[NT], uint4 (&xfn)[2], f32x4 (&acc)[2][NT]) {
     constexpr int FR = NT + 2, FM = 2 * NT;
@@ -2479,9 +2489,9 @@ __device__ __forceinline__ void a64_step(int s, const char* s_my, const char* s_
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int m = (I * FM) / FR; m < ((I + 1) * FM) / FR; ++m) Mma<bf16_t>::run(wf[m % NT], xf[m / NT], acc[m / NT][m % NT]);
+        for (int m = (I * FM) / FR; m < ((I + 1) * FM) / FR; ++m) Mma<T>::run(wf[m % NT], xf[m / NT], acc[m / NT][m % NT]);
         __builtin_amdgcn_sched_barrier(0);
-        a64_step<I + 1, NEXT, NT>(s, s_my, s_w, lane_w, xo, wf, xf, wfn, xfn, acc);
+        a64_step<T, I + 1, NEXT, NT>(s, s_my, s_w, lane_w, xo, wf, xf, wfn, xfn, acc);
     }
 }
 
@@ -2610,9 +2620,9 @@ __global__ __launch_bounds__(kAutoThreads) void conv_mfma_auto64_kernel(const Co
             xfa[1] = *reinterpret_cast<const uint4*>(s_my + xo[0][0] + kA64ROWB);
 #pragma unroll
             for (int s = 0; s < STEPS; s += 2) {
-                a64_step<0, true, NT>(s, s_my, s_w, lane_w, xo, wfa, xfa, wfb, xfb, acc);
-                if (s + 2 < STEPS) a64_step<0, true, NT>(s + 1, s_my, s_w, lane_w, xo, wfb, xfb, wfa, xfa, acc);
-                else a64_step<0, false, NT>(s + 1, s_my, s_w, lane_w, xo, wfb, xfb, wfa, xfa, acc);
+                a64_step<T, 0, true, NT>(s, s_my, s_w, lane_w, xo, wfa, xfa, wfb, xfb, acc);
+                if (s + 2 < STEPS) a64_step<T, 0, true, NT>(s + 1, s_my, s_w, lane_w, xo, wfb, xfb, wfa, xfa, acc);
+                else a64_step<T, 0, false, NT>(s + 1, s_my, s_w, lane_w, xo, wfb, xfb, wfa, xfa, acc);
             }
         }
 
@@ -2712,7 +2722,7 @@ int launch_conv_g(const ConvArgs& a, hipStream_t stream) {
                 return RC_OK;
             }
         }
-        return fail(RC_ERR_UNSUPPORTED, "rc_conv2d: RC_OUT_NHWC_DWT needs a bf16 3x3 layer of one Cin chunk and one 32- or 48-wide cout tile (cin == cout == 32 or 48), 16-byte aligned operands");
+        return fail(RC_ERR_UNSUPPORTED, "rc_conv2d: RC_OUT_NHWC_DWT needs a bf16 / fp16 3x3 layer of one Cin chunk and one 32- or 48-wide cout tile (cin == cout == 32 or 48), 16-byte aligned operands");
     }
     constexpr int WS_LDS = ws_lds_bytes<Cfg>();
     if constexpr (WS_LDS <= 150 * 1024) {              // one 8-wave producer/consumer block per CU
@@ -2735,7 +2745,8 @@ int launch_conv_g(const ConvArgs& a, hipStream_t stream) {
             return RC_OK;
         }
     }
-    if constexpr (!GATED && FAST && sizeof(typename Cfg::elem) == 2 && Cfg::KS == 3 && Cfg::STEPS >= 2 && pss_lds_bytes<Cfg>() <= 160 * 1024 &&
+    // (kernel 5 is a bf16 A/B form, off by default: no fp16 instantiation)
+    if constexpr (!GATED && FAST && dtype_of<typename Cfg::elem>::value == RC_BF16 && Cfg::KS == 3 && Cfg::STEPS >= 2 && pss_lds_bytes<Cfg>() <= 160 * 1024 &&
                   (kWsmTH * kTW * Cfg::COUT_TILE * 2) % (16 * kThreads * 2) == 0) {
         // single-chunk pixel-shuffle layers: output staged through LDS, stored by the loader waves (kernel 5)
         if (a.pss && a.n_chunks == 1 && a.n_ct == 4 && a.cin_vec_ok && a.cin_chunk_ok && a.persist_ok && n_tiles < (1 << 24)) {
@@ -2899,6 +2910,6 @@ int launch_conv(const ConvArgs& a, hipStream_t stream) {
 }
 
 // defined in conv_dispatch.hip; the instantiations live in conv_inst_*.hip
-int dispatch_conv(bool bf16, int ksize, int ck, int nt, const ConvArgs& a, hipStream_t s);
+int dispatch_conv(int dtype, int ksize, int ck, int nt, const ConvArgs& a, hipStream_t s);
 
 }  // namespace rc

@@ -38,8 +38,8 @@ __global__ void bayer_unshuffle_kernel(const TI* __restrict__ mosaic, TO* __rest
             *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
         } else {
             uint2 p;
-            p.x = Vec16<bf16_t>::rne2(v[0], v[1]);
-            p.y = Vec16<bf16_t>::rne2(v[2], v[3]);
+            p.x = Vec16<TO>::rne2(v[0], v[1]);
+            p.y = Vec16<TO>::rne2(v[2], v[3]);
             *reinterpret_cast<uint2*>(o) = p;
         }
     }
@@ -73,8 +73,8 @@ __global__ void raw_ingest_kernel(const TI* __restrict__ mosaic, TO* __restrict_
                 *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
             } else {
                 uint2 p;
-                p.x = Vec16<bf16_t>::rne2(v[0], v[1]);
-                p.y = Vec16<bf16_t>::rne2(v[2], v[3]);
+                p.x = Vec16<TO>::rne2(v[0], v[1]);
+                p.y = Vec16<TO>::rne2(v[2], v[3]);
                 *reinterpret_cast<uint2*>(o) = p;
             }
         } else {
@@ -567,6 +567,10 @@ using namespace rc;
         else if (in_dt == RC_F32 && out_dt == RC_BF16) { CALL(float, bf16_t); }         \
         else if (in_dt == RC_BF16 && out_dt == RC_F32) { CALL(bf16_t, float); }         \
         else if (in_dt == RC_BF16 && out_dt == RC_BF16) { CALL(bf16_t, bf16_t); }       \
+        else if (in_dt == RC_F32 && out_dt == RC_F16) { CALL(float, f16_t); }           \
+        else if (in_dt == RC_F16 && out_dt == RC_F32) { CALL(f16_t, float); }           \
+        else if (in_dt == RC_F16 && out_dt == RC_F16) { CALL(f16_t, f16_t); }           \
+        else if (in_dt == RC_BF16 && out_dt == RC_F16) { CALL(bf16_t, f16_t); }         \
         else return fail(RC_ERR_INVALID, "bad dtype");                                  \
     } while (0)
 
@@ -601,7 +605,8 @@ int rc_raw_ingest(const void* d_mosaic, int in_dtype, void* d_packed, void* d_co
                        static_cast<const TI*>(d_mosaic), static_cast<TO*>(d_packed), static_cast<TO*>(d_cond), batch, h, w, \
                        hp, wp, cond_h, cond_w, black_level, inv, sy, sx)
     if (in_dtype == RC_U16) {
-        if (out_dtype == RC_F32) { CALL(uint16_t, float); } else if (out_dtype == RC_BF16) { CALL(uint16_t, bf16_t); } else return fail(RC_ERR_INVALID, "bad dtype");
+        if (out_dtype == RC_F32) { CALL(uint16_t, float); } else if (out_dtype == RC_BF16) { CALL(uint16_t, bf16_t); }
+        else if (out_dtype == RC_F16) { CALL(uint16_t, f16_t); } else return fail(RC_ERR_INVALID, "bad dtype");
     } else {
         RC_DISPATCH_2(in_dtype, out_dtype, CALL);
     }
@@ -654,31 +659,37 @@ int rc_gate_residual(const void* d_r, const float* d_gate, const void* d_x, void
                      int batch, int n_pix, int c, void* stream) {
     RC_REQUIRE(d_r && d_gate && d_y, "rc_gate_residual: null pointer");
     const int U = dtype == RC_F32 ? 4 : 8;
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_gate_residual: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_gate_residual: bad dtype");
     RC_REQUIRE(batch >= 1 && n_pix >= 1 && c >= U && c % U == 0, "rc_gate_residual: c must be a multiple of 16 bytes");
     const size_t total = (size_t)batch * n_pix * (c / U);
     if (dtype == RC_F32)
         hipLaunchKernelGGL(gate_residual_kernel<float>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const float*>(d_r), d_gate, static_cast<const float*>(d_x), static_cast<float*>(d_y), batch, (size_t)n_pix, c);
-    else
+    else if (dtype == RC_BF16)
         hipLaunchKernelGGL(gate_residual_kernel<bf16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const bf16_t*>(d_r), d_gate, static_cast<const bf16_t*>(d_x), static_cast<bf16_t*>(d_y), batch, (size_t)n_pix, c);
+    else
+        hipLaunchKernelGGL(gate_residual_kernel<f16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
+                           static_cast<const f16_t*>(d_r), d_gate, static_cast<const f16_t*>(d_x), static_cast<f16_t*>(d_y), batch, (size_t)n_pix, c);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }
 
 int rc_film_apply(const void* d_x, const float* d_scale, const float* d_shift, void* d_y, int dtype, int batch, int n_pix, int c, void* stream) {
     RC_REQUIRE(d_x && d_scale && d_shift && d_y, "rc_film_apply: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_film_apply: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_film_apply: bad dtype");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(batch >= 1 && n_pix >= 1 && c >= U && c % U == 0, "rc_film_apply: c must be a multiple of 16 bytes");
     const size_t total = (size_t)batch * n_pix * (c / U);
     if (dtype == RC_F32)
         hipLaunchKernelGGL(film_apply_kernel<float>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream), static_cast<const float*>(d_x),
                            d_scale, d_shift, static_cast<float*>(d_y), batch, (size_t)n_pix, c);
-    else
+    else if (dtype == RC_BF16)
         hipLaunchKernelGGL(film_apply_kernel<bf16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream), static_cast<const bf16_t*>(d_x),
                            d_scale, d_shift, static_cast<bf16_t*>(d_y), batch, (size_t)n_pix, c);
+    else
+        hipLaunchKernelGGL(film_apply_kernel<f16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream), static_cast<const f16_t*>(d_x),
+                           d_scale, d_shift, static_cast<f16_t*>(d_y), batch, (size_t)n_pix, c);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }
@@ -686,7 +697,7 @@ int rc_film_apply(const void* d_x, const float* d_scale, const float* d_shift, v
 int rc_sigmoid_gate_add(const void* d_a, const void* d_b, const void* d_identity, void* d_y, int dtype, long long n_elems,
                         void* stream) {
     RC_REQUIRE(d_a && d_b && d_identity && d_y, "rc_sigmoid_gate_add: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_sigmoid_gate_add: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_sigmoid_gate_add: bad dtype");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(n_elems >= U && n_elems % U == 0, "rc_sigmoid_gate_add: element count must be a whole number of 16-byte vectors");
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_a) % 16 == 0 && reinterpret_cast<uintptr_t>(d_b) % 16 == 0 &&
@@ -695,16 +706,19 @@ int rc_sigmoid_gate_add(const void* d_a, const void* d_b, const void* d_identity
     if (dtype == RC_F32)
         hipLaunchKernelGGL(sigmoid_gate_add_kernel<float>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const float*>(d_a), static_cast<const float*>(d_b), static_cast<const float*>(d_identity), static_cast<float*>(d_y), total);
-    else
+    else if (dtype == RC_BF16)
         hipLaunchKernelGGL(sigmoid_gate_add_kernel<bf16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const bf16_t*>(d_a), static_cast<const bf16_t*>(d_b), static_cast<const bf16_t*>(d_identity), static_cast<bf16_t*>(d_y), total);
+    else
+        hipLaunchKernelGGL(sigmoid_gate_add_kernel<f16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
+                           static_cast<const f16_t*>(d_a), static_cast<const f16_t*>(d_b), static_cast<const f16_t*>(d_identity), static_cast<f16_t*>(d_y), total);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }
 
 int rc_subsample2(const void* d_src, void* d_dst, int dtype, int batch, int H, int W, int c, void* stream) {
     RC_REQUIRE(d_src && d_dst, "rc_subsample2: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_subsample2: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_subsample2: bad dtype");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(batch >= 1 && H >= 1 && W >= 1 && c >= U && c % U == 0, "rc_subsample2: channels must be a whole number of 16-byte vectors");
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % 16 == 0 && reinterpret_cast<uintptr_t>(d_dst) % 16 == 0, "rc_subsample2: 16-byte alignment");
@@ -712,16 +726,19 @@ int rc_subsample2(const void* d_src, void* d_dst, int dtype, int batch, int H, i
     if (dtype == RC_F32)
         hipLaunchKernelGGL(subsample2_kernel<float>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const float*>(d_src), static_cast<float*>(d_dst), batch, H, W, c);
-    else
+    else if (dtype == RC_BF16)
         hipLaunchKernelGGL(subsample2_kernel<bf16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const bf16_t*>(d_src), static_cast<bf16_t*>(d_dst), batch, H, W, c);
+    else
+        hipLaunchKernelGGL(subsample2_kernel<f16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
+                           static_cast<const f16_t*>(d_src), static_cast<f16_t*>(d_dst), batch, H, W, c);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }
 
 int rc_upsample_bilinear2(const void* d_src, void* d_dst, int dtype, int batch, int H, int W, int c, void* stream) {
     RC_REQUIRE(d_src && d_dst, "rc_upsample_bilinear2: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_upsample_bilinear2: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_upsample_bilinear2: bad dtype");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(batch >= 1 && H >= 1 && W >= 1 && c >= U && c % U == 0, "rc_upsample_bilinear2: channels must be a whole number of 16-byte vectors");
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % 16 == 0 && reinterpret_cast<uintptr_t>(d_dst) % 16 == 0, "rc_upsample_bilinear2: 16-byte alignment");
@@ -729,9 +746,12 @@ int rc_upsample_bilinear2(const void* d_src, void* d_dst, int dtype, int batch, 
     if (dtype == RC_F32)
         hipLaunchKernelGGL(upsample_bilinear2_kernel<float>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const float*>(d_src), static_cast<float*>(d_dst), batch, H, W, c);
-    else
+    else if (dtype == RC_BF16)
         hipLaunchKernelGGL(upsample_bilinear2_kernel<bf16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const bf16_t*>(d_src), static_cast<bf16_t*>(d_dst), batch, H, W, c);
+    else
+        hipLaunchKernelGGL(upsample_bilinear2_kernel<f16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
+                           static_cast<const f16_t*>(d_src), static_cast<f16_t*>(d_dst), batch, H, W, c);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }
@@ -739,7 +759,7 @@ int rc_upsample_bilinear2(const void* d_src, void* d_dst, int dtype, int batch, 
 int rc_sft_apply(const void* d_x, const void* d_scale, const void* d_shift, const void* d_identity, void* d_y, int dtype,
                  long long n_elems, void* stream) {
     RC_REQUIRE(d_x && d_scale && d_shift && d_y, "rc_sft_apply: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_sft_apply: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_sft_apply: bad dtype");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(n_elems >= U && n_elems % U == 0, "rc_sft_apply: element count must be a whole number of 16-byte vectors");
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && reinterpret_cast<uintptr_t>(d_scale) % 16 == 0 && reinterpret_cast<uintptr_t>(d_shift) % 16 == 0 &&
@@ -749,17 +769,21 @@ int rc_sft_apply(const void* d_x, const void* d_scale, const void* d_shift, cons
         hipLaunchKernelGGL(sft_apply_kernel<float>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const float*>(d_x), static_cast<const float*>(d_scale), static_cast<const float*>(d_shift),
                            static_cast<const float*>(d_identity), static_cast<float*>(d_y), total);
-    else
+    else if (dtype == RC_BF16)
         hipLaunchKernelGGL(sft_apply_kernel<bf16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const bf16_t*>(d_x), static_cast<const bf16_t*>(d_scale), static_cast<const bf16_t*>(d_shift),
                            static_cast<const bf16_t*>(d_identity), static_cast<bf16_t*>(d_y), total);
+    else
+        hipLaunchKernelGGL(sft_apply_kernel<f16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
+                           static_cast<const f16_t*>(d_x), static_cast<const f16_t*>(d_scale), static_cast<const f16_t*>(d_shift),
+                           static_cast<const f16_t*>(d_identity), static_cast<f16_t*>(d_y), total);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }
 
 int rc_space_to_depth2(const void* d_src, void* d_dst, int dtype, int batch, int H, int W, int c, void* stream) {
     RC_REQUIRE(d_src && d_dst, "rc_space_to_depth2: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_space_to_depth2: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_space_to_depth2: bad dtype");
     RC_REQUIRE(batch >= 1 && H >= 1 && W >= 1 && c >= 1, "rc_space_to_depth2: bad shape");
     const int U = dtype == RC_F32 ? 4 : 8;
     if (c % U == 0 && reinterpret_cast<uintptr_t>(d_src) % 16 == 0 && reinterpret_cast<uintptr_t>(d_dst) % 16 == 0) {
@@ -767,9 +791,12 @@ int rc_space_to_depth2(const void* d_src, void* d_dst, int dtype, int batch, int
         if (dtype == RC_F32)
             hipLaunchKernelGGL(space_to_depth2_vec_kernel<float>, dim3(grid_for(tv)), dim3(kPwThreads), 0, as_stream(stream),
                                static_cast<const float*>(d_src), static_cast<float*>(d_dst), batch, H, W, c);
-        else
+        else if (dtype == RC_BF16)
             hipLaunchKernelGGL(space_to_depth2_vec_kernel<bf16_t>, dim3(grid_for(tv)), dim3(kPwThreads), 0, as_stream(stream),
                                static_cast<const bf16_t*>(d_src), static_cast<bf16_t*>(d_dst), batch, H, W, c);
+        else
+            hipLaunchKernelGGL(space_to_depth2_vec_kernel<f16_t>, dim3(grid_for(tv)), dim3(kPwThreads), 0, as_stream(stream),
+                               static_cast<const f16_t*>(d_src), static_cast<f16_t*>(d_dst), batch, H, W, c);
         RC_HIP_CHECK(hipGetLastError());
         return RC_OK;
     }
@@ -777,39 +804,48 @@ int rc_space_to_depth2(const void* d_src, void* d_dst, int dtype, int batch, int
     if (dtype == RC_F32)
         hipLaunchKernelGGL(space_to_depth2_kernel<float>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const float*>(d_src), static_cast<float*>(d_dst), batch, H, W, c);
-    else
+    else if (dtype == RC_BF16)
         hipLaunchKernelGGL(space_to_depth2_kernel<bf16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const bf16_t*>(d_src), static_cast<bf16_t*>(d_dst), batch, H, W, c);
+    else
+        hipLaunchKernelGGL(space_to_depth2_kernel<f16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
+                           static_cast<const f16_t*>(d_src), static_cast<f16_t*>(d_dst), batch, H, W, c);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }
 
 int rc_pixel_shuffle2(const void* d_src, void* d_dst, int dtype, int batch, int H, int W, int c_out, void* stream) {
     RC_REQUIRE(d_src && d_dst, "rc_pixel_shuffle2: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_pixel_shuffle2: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_pixel_shuffle2: bad dtype");
     RC_REQUIRE(batch >= 1 && H >= 1 && W >= 1 && c_out >= 1, "rc_pixel_shuffle2: bad shape");
     const size_t total = (size_t)batch * 4 * H * W * c_out;
     if (dtype == RC_F32)
         hipLaunchKernelGGL(pixel_shuffle2_kernel<float>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const float*>(d_src), static_cast<float*>(d_dst), batch, H, W, c_out);
-    else
+    else if (dtype == RC_BF16)
         hipLaunchKernelGGL(pixel_shuffle2_kernel<bf16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const bf16_t*>(d_src), static_cast<bf16_t*>(d_dst), batch, H, W, c_out);
+    else
+        hipLaunchKernelGGL(pixel_shuffle2_kernel<f16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
+                           static_cast<const f16_t*>(d_src), static_cast<f16_t*>(d_dst), batch, H, W, c_out);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }
 
 int rc_pixel_shuffle2_nchw(const void* d_src, void* d_dst, int dtype, int batch, int H, int W, int c_out, void* stream) {
     RC_REQUIRE(d_src && d_dst, "rc_pixel_shuffle2_nchw: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_pixel_shuffle2_nchw: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_pixel_shuffle2_nchw: bad dtype");
     RC_REQUIRE(batch >= 1 && H >= 1 && W >= 1 && c_out >= 1, "rc_pixel_shuffle2_nchw: bad shape");
     const size_t total = (size_t)batch * 4 * H * W * c_out;
     if (dtype == RC_F32)
         hipLaunchKernelGGL(pixel_shuffle2_nchw_kernel<float>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const float*>(d_src), static_cast<float*>(d_dst), batch, H, W, c_out);
-    else
+    else if (dtype == RC_BF16)
         hipLaunchKernelGGL(pixel_shuffle2_nchw_kernel<bf16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const bf16_t*>(d_src), static_cast<bf16_t*>(d_dst), batch, H, W, c_out);
+    else
+        hipLaunchKernelGGL(pixel_shuffle2_nchw_kernel<f16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
+                           static_cast<const f16_t*>(d_src), static_cast<f16_t*>(d_dst), batch, H, W, c_out);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }
@@ -890,7 +926,7 @@ int rc_channel_concat(const void* const* d_parts, const int* widths, int n_parts
 int rc_dwt_forward(const void* d_x, void* d_y, const float* d_taps, int taps_uniform, int dtype,
                    int batch, int H, int W, int c, void* stream) {
     RC_REQUIRE(d_x && d_y && d_taps, "rc_dwt_forward: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_dwt_forward: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_dwt_forward: bad dtype");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(batch >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "rc_dwt_forward: H and W must be even");
     RC_REQUIRE(c % U == 0, "rc_dwt_forward: channels must be a multiple of 16 bytes");
@@ -900,11 +936,16 @@ int rc_dwt_forward(const void* d_x, void* d_y, const float* d_taps, int taps_uni
                            static_cast<const float*>(d_x), static_cast<float*>(d_y), d_taps, batch, H, W, c);
         else hipLaunchKernelGGL((dwt_forward_kernel<float, false>), dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const float*>(d_x), static_cast<float*>(d_y), d_taps, batch, H, W, c);
-    } else {
+    } else if (dtype == RC_BF16) {
         if (taps_uniform) hipLaunchKernelGGL((dwt_forward_kernel<bf16_t, true>), dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const bf16_t*>(d_x), static_cast<bf16_t*>(d_y), d_taps, batch, H, W, c);
         else hipLaunchKernelGGL((dwt_forward_kernel<bf16_t, false>), dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const bf16_t*>(d_x), static_cast<bf16_t*>(d_y), d_taps, batch, H, W, c);
+    } else {
+        if (taps_uniform) hipLaunchKernelGGL((dwt_forward_kernel<f16_t, true>), dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
+                           static_cast<const f16_t*>(d_x), static_cast<f16_t*>(d_y), d_taps, batch, H, W, c);
+        else hipLaunchKernelGGL((dwt_forward_kernel<f16_t, false>), dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
+                           static_cast<const f16_t*>(d_x), static_cast<f16_t*>(d_y), d_taps, batch, H, W, c);
     }
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
@@ -913,7 +954,7 @@ int rc_dwt_forward(const void* d_x, void* d_y, const float* d_taps, int taps_uni
 int rc_dwt_inverse(const void* d_x, void* d_y, const float* d_taps, int taps_uniform, int dtype,
                    int batch, int h, int w, int c4, void* stream) {
     RC_REQUIRE(d_x && d_y && d_taps, "rc_dwt_inverse: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_dwt_inverse: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_dwt_inverse: bad dtype");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(batch >= 1 && h >= 1 && w >= 1 && c4 % 4 == 0 && (c4 / 4) % U == 0,
                "rc_dwt_inverse: out channels (c4/4) must be a multiple of 16 bytes");
@@ -923,11 +964,16 @@ int rc_dwt_inverse(const void* d_x, void* d_y, const float* d_taps, int taps_uni
                            static_cast<const float*>(d_x), static_cast<float*>(d_y), d_taps, batch, h, w, c4);
         else hipLaunchKernelGGL((dwt_inverse_kernel<float, false>), dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const float*>(d_x), static_cast<float*>(d_y), d_taps, batch, h, w, c4);
-    } else {
+    } else if (dtype == RC_BF16) {
         if (taps_uniform) hipLaunchKernelGGL((dwt_inverse_kernel<bf16_t, true>), dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const bf16_t*>(d_x), static_cast<bf16_t*>(d_y), d_taps, batch, h, w, c4);
         else hipLaunchKernelGGL((dwt_inverse_kernel<bf16_t, false>), dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
                            static_cast<const bf16_t*>(d_x), static_cast<bf16_t*>(d_y), d_taps, batch, h, w, c4);
+    } else {
+        if (taps_uniform) hipLaunchKernelGGL((dwt_inverse_kernel<f16_t, true>), dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
+                           static_cast<const f16_t*>(d_x), static_cast<f16_t*>(d_y), d_taps, batch, h, w, c4);
+        else hipLaunchKernelGGL((dwt_inverse_kernel<f16_t, false>), dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
+                           static_cast<const f16_t*>(d_x), static_cast<f16_t*>(d_y), d_taps, batch, h, w, c4);
     }
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
@@ -935,7 +981,7 @@ int rc_dwt_inverse(const void* d_x, void* d_y, const float* d_taps, int taps_uni
 
 int rc_tail_ring_gather(const void* d_x, void* d_rows, void* d_cols, int dtype, int batch, int H, int W, int c, void* stream) {
     RC_REQUIRE(d_x && d_rows && d_cols, "rc_tail_ring_gather: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_tail_ring_gather: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_tail_ring_gather: bad dtype");
     RC_REQUIRE(batch >= 1 && H >= 2 && W >= 2 && c >= 1 && (c * dtype_size(dtype)) % 16 == 0, "rc_tail_ring_gather: H, W >= 2 and a pixel record of whole 16-byte vectors");
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && reinterpret_cast<uintptr_t>(d_rows) % 16 == 0 && reinterpret_cast<uintptr_t>(d_cols) % 16 == 0,
                "rc_tail_ring_gather: 16-byte alignment");
@@ -950,15 +996,18 @@ int rc_tail_ring_gather(const void* d_x, void* d_rows, void* d_cols, int dtype, 
 int rc_tail_ring_scatter(const void* d_rows_out, const void* d_cols_out, void* d_out, int dtype, int batch, int c_out, int H, int W,
                          int out_h, int out_w, void* stream) {
     RC_REQUIRE(d_rows_out && d_cols_out && d_out, "rc_tail_ring_scatter: null pointer");
-    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_tail_ring_scatter: bad dtype");
+    RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_tail_ring_scatter: bad dtype");
     RC_REQUIRE(batch >= 1 && c_out >= 1 && H >= 2 && W >= 2 && out_h >= 1 && out_h <= 2 * H && out_w >= 1 && out_w <= 2 * W, "rc_tail_ring_scatter: bad shape");
     const size_t total = (size_t)batch * c_out * (2 * (size_t)out_w + 2 * (size_t)out_h);
     if (dtype == RC_F32)
         hipLaunchKernelGGL(tail_ring_scatter_kernel<float>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream), static_cast<const float*>(d_rows_out),
                            static_cast<const float*>(d_cols_out), static_cast<float*>(d_out), batch, c_out, H, W, out_h, out_w);
-    else
+    else if (dtype == RC_BF16)
         hipLaunchKernelGGL(tail_ring_scatter_kernel<bf16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream), static_cast<const bf16_t*>(d_rows_out),
                            static_cast<const bf16_t*>(d_cols_out), static_cast<bf16_t*>(d_out), batch, c_out, H, W, out_h, out_w);
+    else
+        hipLaunchKernelGGL(tail_ring_scatter_kernel<f16_t>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream), static_cast<const f16_t*>(d_rows_out),
+                           static_cast<const f16_t*>(d_cols_out), static_cast<f16_t*>(d_out), batch, c_out, H, W, out_h, out_w);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

@@ -281,6 +281,9 @@ class ConvPosEnc(nn.Module):
         return self._nhwc(_as_nhwc(x, size)).reshape(x.shape)
 
 
+SUPPORTED_DTYPES = (torch.float32, torch.bfloat16)     # no fp16 kernels for the GroupMix stages (fp16 is built for the ISP path)
+
+
 class GMA_Block(nn.Module):
     """cpe -> LN -> EfficientAtt -> + ; LN -> Mlp -> +   (upstream groupmix.py:274-299)."""
 
@@ -323,6 +326,7 @@ class GMA_Block(nn.Module):
         pre = the conv1x1 module in front of the block (gma_in): `a` is ITS input, and conv + ConvPosEnc run as one launch where possible."""
         if self.training:
             raise RuntimeError("realcamnet_amd is an inference path: call .eval() first")
+        ops.require_dtype(a, SUPPORTED_DTYPES, "GMA_Block")
         if pre is not None:
             x = self._entry(a, pre)
             a = x                                   # (only its dtype / width matter below)

@@ -1,7 +1,7 @@
 """Host-side operator layer: thin, typed wrappers from torch tensors to the C ABI (include/realcam_hip.h).
 
 PyTorch is used for device memory (caching allocator), the current HIP stream and nothing else.
-Internal activations are NHWC tensors of shape (B, H, W, C), contiguous, fp32 or bf16.
+Internal activations are NHWC tensors of shape (B, H, W, C), contiguous, fp32, bf16 or fp16 (fp16: the ISP networks' ops only).
 There is NO fallback: CPU tensors or a missing library raise.
 """
 from __future__ import annotations
@@ -15,10 +15,11 @@ import torch
 
 from . import _lib
 from . import torch_ops as _T  # noqa: F401  (registers torch.ops.realcam.*)
-from ._lib import (RC_ACT_GELU, RC_ACT_LEAKY, RC_ACT_NONE, RC_ACT_RELU, RC_ACT_RELU_POST, RC_BF16, RC_F32, RC_OUT_NCHW, RC_OUT_NHWC, RC_OUT_NHWC_DWT,
+from ._lib import (RC_ACT_GELU, RC_ACT_LEAKY, RC_ACT_NONE, RC_ACT_RELU, RC_ACT_RELU_POST, RC_BF16, RC_F16, RC_F32, RC_OUT_NCHW, RC_OUT_NHWC, RC_OUT_NHWC_DWT,
                    RC_OUT_PIXEL_SHUFFLE2, RC_OUT_PIXEL_SHUFFLE2_NCHW, ConvDesc, ConvPairDesc, check)
 
-_DT = {torch.float32: RC_F32, torch.bfloat16: RC_BF16}
+_DT = {torch.float32: RC_F32, torch.bfloat16: RC_BF16, torch.float16: RC_F16}
+_HALF = (torch.bfloat16, torch.float16)        # the 16-bit storage types: same bytes per element, same kernel forms (RC_F16 is planned as RC_BF16)
 _R = torch.ops.realcam          # every launch below goes through the dispatcher op registered in torch_ops.py
 
 
@@ -39,7 +40,14 @@ def _dt(t: torch.Tensor) -> int:
     try:
         return _DT[t.dtype]
     except KeyError:
-        raise TypeError(f"realcamnet_amd: unsupported dtype {t.dtype} (fp32 / bf16 only)") from None
+        raise TypeError(f"realcamnet_amd: unsupported dtype {t.dtype} (fp32 / bf16 / fp16)") from None
+
+
+def require_dtype(t: torch.Tensor, allowed, what: str) -> None:
+    """Refuse, before anything is launched, an activation dtype a module has no kernels for (fp16 is built for the ISP networks only)."""
+    if t.dtype not in allowed:
+        names = " / ".join({torch.float32: "fp32", torch.bfloat16: "bf16", torch.float16: "fp16"}.get(d, str(d)) for d in allowed)
+        raise TypeError(f"realcamnet_amd: {what} supports {names} only, got {t.dtype}")
 
 
 def _req(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -617,11 +625,11 @@ _HAAR_TAPS = (0.5, 0.5, 0.5, 0.5, 0.5, 0.5, -0.5, -0.5, 0.5, -0.5, 0.5, -0.5, 0.
 
 def conv_dwt_ok(x: torch.Tensor, conv, dwt, act: Optional[str] = None, slope: float = 0.0, residual: bool = False) -> bool:
     """Can `conv [+ act | + residual] -> dwt` (networks.Conv2d, networks.DWTForward; upstream models/LiteISP.py:1950-1958: `down1`'s closing conv, `down2`'s RCAGroup
-    = conv + group skip) run as ONE rc_conv2d launch with RC_OUT_NHWC_DWT?  The kernel form exists for the bf16 3x3 layers of the wave-autonomous kernel
+    = conv + group skip) run as ONE rc_conv2d launch with RC_OUT_NHWC_DWT?  The kernel form exists for the bf16 / fp16 3x3 layers of the wave-autonomous kernel
     (cin == cout == 32 or 48) and computes with the reference's frozen Haar taps, so the module's taps must BE those (checked once per write of the tap tensor)."""
     if residual and act is not None:
         return False
-    if not FUSE_DWT or x.dtype != torch.bfloat16 or x.dim() != 4 or conv.weight.dim() != 4:
+    if not FUSE_DWT or x.dtype not in _HALF or x.dim() != 4 or conv.weight.dim() != 4:
         return False
     cout, cin, kh, kw = conv.weight.shape
     if not (kh == kw == 3 and cin == cout and cin in (32, 48) and x.shape[3] == cin and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0):
@@ -656,7 +664,7 @@ FOLD_TAIL = True
 
 
 def tail_fold_ok(x: torch.Tensor, conv1, conv2) -> bool:
-    """conv(C -> 4C, 3x3) -> PixelShuffle(2) -> conv(C -> O, 3x3) with a 5x5 kernel instantiation for (C, 4 O, dtype): bf16 C = 48 k / 32 k, fp32 C = 16 k."""
+    """conv(C -> 4C, 3x3) -> PixelShuffle(2) -> conv(C -> O, 3x3) with a 5x5 kernel instantiation for (C, 4 O, dtype): bf16 / fp16 C = 48 k / 32 k, fp32 C = 16 k."""
     w1, w2 = conv1.weight, conv2.weight
     if not (FOLD_TAIL and x.dim() == 4 and x.dtype in _DT and x.shape[1] >= 2 and x.shape[2] >= 2 and w1.dim() == 4 and w2.dim() == 4):
         return False
@@ -718,6 +726,7 @@ def conv_pair(x: torch.Tensor, m1, m2, *, act: str = "relu", slope: float = 0.0,
               residual: Optional[torch.Tensor] = None, want_sums: bool = False):
     """out = conv(m2)(act(conv(m1)(x)))  (+ residual, + channel partial sums) in one launch; operands as conv2d.
     Returns out, or (out, [stored_input], [chan_sums])."""
+    require_dtype(x, (torch.bfloat16,), "conv_pair (rc_conv_pair)")
     for m in (m1, m2):
         check_conv_module(m)
     x = _req(x, "conv_pair input")

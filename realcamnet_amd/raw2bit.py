@@ -360,6 +360,7 @@ class raw_compression_tcm_final(nn.Module):
         self.gaussian_conditional = GaussianConditional(None)
 
     def _act_dtype(self):
+        ops.require_dtype(self.conv_first.weight, T.SUPPORTED_DTYPES, type(self).__name__)   # every entry point asks this first: refused before any launch
         return self.conv_first.weight.dtype
 
     update = T._codec_update

@@ -20,6 +20,8 @@ from . import networks as N
 from . import networks as N_mod      # TCM.__init__ keeps upstream's parameter name `N`
 from . import ops
 
+SUPPORTED_DTYPES = (torch.float32, torch.bfloat16)     # the codecs (and their entropy models / rANS coder) have no fp16 kernels
+
 
 class WMSA(nn.Module):
     """Window / shifted-window multi-head self-attention (upstream models/tcm.py:139-212)."""
@@ -714,7 +716,9 @@ class TCM(nn.Module):
         return _slice_loop(self, self.g_a._nhwc(ops.to_nhwc(x, dtype=self._act_dtype())))
 
     def _act_dtype(self):
-        return next(self.g_a.parameters()).dtype
+        p = next(self.g_a.parameters())
+        ops.require_dtype(p, SUPPORTED_DTYPES, "TCM")                  # every entry point asks this first: refused before any launch
+        return p.dtype
 
     update = _codec_update
     load_state_dict = _codec_load_state_dict

@@ -21,9 +21,9 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import RC_BF16, RC_F32, RC_OUT_NCHW, RC_OUT_NHWC, RC_OUT_NHWC_DWT, RC_OUT_PIXEL_SHUFFLE2, RC_OUT_PIXEL_SHUFFLE2_NCHW, ConvDesc, ConvPairDesc, check
+from ._lib import RC_BF16, RC_F16, RC_F32, RC_OUT_NCHW, RC_OUT_NHWC, RC_OUT_NHWC_DWT, RC_OUT_PIXEL_SHUFFLE2, RC_OUT_PIXEL_SHUFFLE2_NCHW, ConvDesc, ConvPairDesc, check
 
-_DT = {torch.float32: RC_F32, torch.bfloat16: RC_BF16}
+_DT = {torch.float32: RC_F32, torch.bfloat16: RC_BF16, torch.float16: RC_F16}
 _LIB = torch.library.Library("realcam", "DEF")
 SCHEMAS = {}
 
