@@ -92,6 +92,45 @@ int rc_bayer_unshuffle(const void* d_mosaic, int in_dtype, void* d_packed, int o
 int rc_raw_ingest(const void* d_mosaic, int in_dtype, void* d_packed, void* d_cond, int out_dtype, int batch, int h, int w,
                   int hp, int wp, int cond_h, int cond_w, float black_level, float white_level, void* stream);
 
+/* ---- sensor RAW formats (ABI 15, additive) -----------------------------------------------------
+ * rc_raw_ingest for the frames a camera stack delivers.  Still the "Unpixel shuffle" and "Resize" boxes of
+ * assets/networkarch.png in front of pad_to_multiple_of_16 (models/LiteISP.py:84-105), one launch. */
+typedef enum rc_raw_storage {
+    RC_RAW_F32 = 0, RC_RAW_BF16 = 1, RC_RAW_U16 = 2, RC_RAW_F16 = 3,   /* one sample per element (the rc_dtype values; U16: LSB-aligned counts) */
+    RC_RAW_U8 = 4,                                                      /* one count per byte */
+    RC_RAW_MIPI10 = 5,  /* MIPI CSI-2 RAW10: 4 samples in 5 bytes; bytes 0-3 = bits [9:2] of samples 0-3, byte 4 bits 2k+1..2k = bits [1:0] of
+                           sample k.  The mosaic width 2w must be a multiple of 4 */
+    RC_RAW_MIPI12 = 6   /* MIPI CSI-2 RAW12: 2 samples in 3 bytes; byte 0 = s0[11:4], byte 1 = s1[11:4], byte 2 = s1[3:0] << 4 | s0[3:0] */
+} rc_raw_storage;
+
+/* Colour of the mosaic cell positions (0,0), (0,1), (1,0), (1,1).  The packed map keeps the RGGB slot meaning (slot 0 R, 1 G of the
+ * R row, 2 G of the B row, 3 B); each slot reads the position of its colour in the same 2x2 cell (pack_raw convention). */
+typedef enum rc_cfa { RC_CFA_RGGB = 0, RC_CFA_BGGR = 1, RC_CFA_GRBG = 2, RC_CFA_GBRG = 3 } rc_cfa;
+
+typedef struct rc_raw_format {
+    int storage;      /* rc_raw_storage */
+    int cfa;          /* rc_cfa */
+    int line_bytes;   /* bytes from one mosaic row to the next, >= the packed / element size of 2w samples; 0: exactly that.  The bytes past
+                         the row's samples are ignored (a V4L2 bytesperline) */
+    int width;        /* mosaic width 2w in samples, or 0 */
+    float black[4];   /* black level per CFA position (0,0), (0,1), (1,0), (1,1) (DNG BlackLevel order) */
+    float white;      /* white level, > every black level */
+    int reserved[4];  /* zero */
+} rc_raw_format;
+size_t rc_raw_format_size(void);
+
+/* d_src: B frames of 2h rows of fmt->line_bytes bytes (4-byte aligned for MIPI storage).  packed NHWC (B,hp,wp,4) zero padded and cond
+ * (B,4,cond_h,cond_w) NCHW exactly as rc_raw_ingest, with v' = (v - black[pos]) * (1 / (white - black[pos])) (fp32, the divisor
+ * computed on the host) for the CFA position pos each packed slot reads.  RGGB with four equal black levels gives rc_raw_ingest's
+ * bits.  out_dtype RC_F32 / RC_BF16 / RC_F16. */
+int rc_raw_ingest_fmt(const void* d_src, const rc_raw_format* fmt, void* d_packed, void* d_cond, int out_dtype, int batch, int h, int w,
+                      int hp, int wp, int cond_h, int cond_w, void* stream);
+
+/* ---- RGB out: the network's planar result (models/LiteISP.py:2032-2035, the sRGB tensor `out`) as interleaved 8- or 16-bit RGB ----------
+ * src (B,3,H,W) RC_F32 / RC_BF16 / RC_F16, cropped to (h,w); dst (B,h,w,3) uint8 (out_bits 8) or uint16 (out_bits 16), 16-byte
+ * aligned: q = clamp(rint(float(y) * S), 0, S), S = 255 or 65535, round half to even, NaN -> 0. */
+int rc_rgb_encode(const void* d_src, int src_dtype, void* d_dst, int out_bits, int batch, int H, int W, int h, int w, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

@@ -254,13 +254,39 @@ class Color_Condition_GFM_LFM(nn.Module):
         return vec.to(global_raw.dtype).view(vec.shape[0], vec.shape[1], 1, 1), ops.to_nchw(lfm)
 
 
-def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw):
-    """Front end shared by every forward_mosaic: packed NHWC RAW (+ the cond image when the caller did not bring one)."""
+def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, raw_format=None):
+    """Front end shared by every forward_mosaic: packed NHWC RAW (+ the cond image when the caller did not bring one).
+    raw_format (a RawFormat): the sensor's CFA phase / storage / levels, decoded by the one-launch rc_raw_ingest_fmt."""
     need_cond = hasattr(net, "classifier") and cond is None and not getattr(net, "cond_from_raw", False)
+    if raw_format is not None:
+        a, c = ops.raw_ingest(mosaic, dtype=dt, pad_to=pad_to, black_level=black_level, white_level=white_level, cond_hw=cond_hw,
+                              raw_format=raw_format)
+        return a, (c if need_cond else cond)
     if need_cond or black_level != 0.0 or white_level != 1.0 or mosaic.dtype == torch.uint16:
         a, c = ops.raw_ingest(mosaic, dtype=dt, pad_to=pad_to, black_level=black_level, white_level=white_level, cond_hw=cond_hw)
         return a, (c if need_cond else cond)
     return ops.bayer_unshuffle(mosaic, dtype=dt, pad_to=pad_to), cond
+
+
+def _mosaic_hw(mosaic, raw_format):
+    """(2h, 2w) of the frame: the tensor's last two dimensions, or for MIPI-packed lines the height and raw_format.width."""
+    if raw_format is None:
+        return mosaic.shape[-2], mosaic.shape[-1]
+    return raw_format.validate(mosaic.shape)
+
+
+_OUT_BITS = {None: None, "rgb8": 8, "rgb16": 16}
+
+
+def _out_bits(out_format):
+    if out_format not in _OUT_BITS:
+        raise ValueError(f"out_format must be None, 'rgb8' or 'rgb16', got {out_format!r}")
+    return _OUT_BITS[out_format]
+
+
+def _encode(y, bits):
+    """out_format: the planar float sRGB (B,3,2h,2w) as it is, or interleaved (B,2h,2w,3) uint8 / uint16 (rc_rgb_encode)."""
+    return y if bits is None else ops.rgb_encode(y, bits)
 
 
 class _DwtUNet(nn.Module):
@@ -365,25 +391,29 @@ class _DwtUNet(nn.Module):
         return self._trunk(h, vec)
 
     def forward_mosaic(self, mosaic, cond=None, coord=None, pad_to: int = 16, black_level: float = 0.0, white_level: float = 1.0,
-                       cond_hw=(256, 256)):
+                       cond_hw=(256, 256), raw_format=None, out_format=None):
         """Bayer mosaic (B,1,2h,2w), cond (B,4,hc,wc), coord (B,2,h,w) -> sRGB (B,3,2h,2w).
         RAW and coord are zero-padded bottom/right to a multiple of `pad_to` (reference convention,
         upstream LiteISP.py:84-105) and the output is cropped back.  cond=None on a net with a colour prior: the fused ingest
-        kernel (ops.raw_ingest) also produces cond = bilinear resize of the normalised packed RAW to `cond_hw`."""
+        kernel (ops.raw_ingest) also produces cond = bilinear resize of the normalised packed RAW to `cond_hw`.
+        raw_format (a RawFormat): the sensor frame's CFA phase, storage (MIPI RAW10 / RAW12 lines: (B,[1,]2h,line_bytes) uint8) and
+        per-position levels.  out_format "rgb8" / "rgb16": the result as interleaved (B,2h,2w,3) uint8 / uint16."""
         if self.training:
             raise RuntimeError("realcamnet_amd is an inference path: call .eval() first")
+        bits = _out_bits(out_format)
         dt = self._act_dtype()
-        a, cond = _ingest(self, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw)
+        mh, mw = _mosaic_hw(mosaic, raw_format)
+        a, cond = _ingest(self, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, raw_format)
         b, hp, wp, _ = a.shape
         co = None
         if hasattr(self, "lsc"):
-            if coord is None or coord.shape[-2:] != (mosaic.shape[-2] // 2, mosaic.shape[-1] // 2):
+            if coord is None or coord.shape[-2:] != (mh // 2, mw // 2):
                 raise ValueError("coord must be at packed resolution (h, w)")
             co = ops.to_nhwc(coord, dtype=dt, pad_hw=(hp, wp))
         if hasattr(self, "classifier") and self.cond_from_raw:
             cond = ops.to_nchw(a)                             # the padded packed RAW, as upstream's x[0]
         h, vec = self._front(a, cond, co)
-        return self._trunk(h, vec, crop_hw=(mosaic.shape[-2], mosaic.shape[-1]))
+        return _encode(self._trunk(h, vec, crop_hw=(mh, mw)), bits)
 
 
 class LiteISPNet(_DwtUNet):
@@ -534,22 +564,24 @@ class _StridedUNet(nn.Module):
         return self._run(ops.to_nhwc(raw, dtype=dt), cond, co)
 
     def forward_mosaic(self, mosaic, cond=None, coord=None, pad_to: int = 16, black_level: float = 0.0, white_level: float = 1.0,
-                       cond_hw=(256, 256)):
+                       cond_hw=(256, 256), raw_format=None, out_format=None):
         """Bayer mosaic (B,1,2h,2w), cond, coord (B,2,h,w) -> sRGB (B,3,2h,2w) with the unshuffle / pad16 / crop front end
-        (cond=None: see _DwtUNet.forward_mosaic)."""
+        (cond=None, raw_format, out_format: see _DwtUNet.forward_mosaic)."""
         if self.training:
             raise RuntimeError("realcamnet_amd is an inference path: call .eval() first")
+        bits = _out_bits(out_format)
         dt = self._act_dtype()
-        a, cond = _ingest(self, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw)
+        mh, mw = _mosaic_hw(mosaic, raw_format)
+        a, cond = _ingest(self, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, raw_format)
         b, hp, wp, _ = a.shape
         co = None
         if hasattr(self, "lsc") or self.coord_in_intro:
-            if coord is None or coord.shape[-2:] != (mosaic.shape[-2] // 2, mosaic.shape[-1] // 2):
+            if coord is None or coord.shape[-2:] != (mh // 2, mw // 2):
                 raise ValueError("coord must be at packed resolution (h, w)")
             co = ops.to_nhwc(coord, dtype=dt, pad_hw=(hp, wp))
         if hasattr(self, "classifier") and self.cond_from_raw:
             cond = ops.to_nchw(a)                             # the padded packed RAW, as upstream's x[0]
-        return self._run(a, cond, co, crop_hw=(mosaic.shape[-2], mosaic.shape[-1]))
+        return _encode(self._run(a, cond, co, crop_hw=(mh, mw)), bits)
 
 
 class ISPUNet_GFM_LSC(_StridedUNet):
@@ -695,11 +727,13 @@ class ISPUNet_GFM_LFM(nn.Module):
         return self._run(ops.to_nhwc(raw, dtype=self._act_dtype()), cond)
 
     def forward_mosaic(self, mosaic, cond=None, coord=None, pad_to: int = 16, black_level: float = 0.0, white_level: float = 1.0,
-                       cond_hw=(256, 256)):
+                       cond_hw=(256, 256), raw_format=None, out_format=None):
         if self.training:
             raise RuntimeError("realcamnet_amd is an inference path: call .eval() first")
-        a, cond = _ingest(self, mosaic, cond, self._act_dtype(), pad_to, black_level, white_level, cond_hw)
-        return self._run(a, cond, crop_hw=(mosaic.shape[-2], mosaic.shape[-1]))
+        bits = _out_bits(out_format)
+        mh, mw = _mosaic_hw(mosaic, raw_format)
+        a, cond = _ingest(self, mosaic, cond, self._act_dtype(), pad_to, black_level, white_level, cond_hw, raw_format)
+        return _encode(self._run(a, cond, crop_hw=(mh, mw)), bits)
 
 
 class LiteISPNet_GFM_LSC_GMA(LiteISPNet_GFM_LSC):

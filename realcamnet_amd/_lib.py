@@ -18,6 +18,8 @@ RC_F32, RC_BF16, RC_U16, RC_F16 = 0, 1, 2, 3
 RC_ACT_NONE, RC_ACT_RELU, RC_ACT_LEAKY, RC_ACT_GELU, RC_ACT_RELU_POST = 0, 1, 2, 3, 4
 RC_OUT_NHWC, RC_OUT_PIXEL_SHUFFLE2, RC_OUT_NCHW, RC_OUT_PIXEL_SHUFFLE2_NCHW, RC_OUT_NHWC_DWT = 0, 1, 2, 3, 4
 ABI_VERSION = 15
+RC_RAW_F32, RC_RAW_BF16, RC_RAW_U16, RC_RAW_F16, RC_RAW_U8, RC_RAW_MIPI10, RC_RAW_MIPI12 = 0, 1, 2, 3, 4, 5, 6
+RC_CFA_RGGB, RC_CFA_BGGR, RC_CFA_GRBG, RC_CFA_GBRG = 0, 1, 2, 3
 
 
 class ConvDesc(C.Structure):
@@ -55,6 +57,14 @@ class ConvPairDesc(C.Structure):
     ]
 
 
+class RawFormatDesc(C.Structure):
+    """Mirror of `struct rc_raw_format`."""
+    _fields_ = [
+        ("storage", C.c_int32), ("cfa", C.c_int32), ("line_bytes", C.c_int32), ("width", C.c_int32),
+        ("black", C.c_float * 4), ("white", C.c_float), ("reserved", C.c_int32 * 4),
+    ]
+
+
 def declared_symbols() -> list[str]:
     """Every function the public header declares (used by the CPU-side ABI test)."""
     text = HEADER.read_text()
@@ -70,6 +80,9 @@ _SIGS = {
     "rc_device_arch": (C.c_int, [C.c_char_p, _SZ]),
     "rc_bayer_unshuffle": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "rc_raw_ingest": (C.c_int, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P]),
+    "rc_raw_format_size": (_SZ, []),
+    "rc_raw_ingest_fmt": (C.c_int, [_P, C.POINTER(RawFormatDesc), _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "rc_rgb_encode": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

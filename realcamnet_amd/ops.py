@@ -462,11 +462,15 @@ def bayer_unshuffle(mosaic: torch.Tensor, dtype: Optional[torch.dtype] = None, p
 
 
 def raw_ingest(mosaic: torch.Tensor, dtype: Optional[torch.dtype] = None, pad_to: int = 16, black_level: float = 0.0, white_level: float = 1.0,
-               cond_hw: Tuple[int, int] = (256, 256)):
+               cond_hw: Tuple[int, int] = (256, 256), raw_format=None):
     """The RAW ingest step in front of the path (the 'Unpixel shuffle' and 'Resize' boxes of
     assets/networkarch.png), one launch: sensor mosaic (B,[1,]2h,2w) -> normalise (v - black) / (white - black) ->
     Bayer unshuffle -> zero-pad to `pad_to` -> packed NHWC (B,hp,wp,4); and cond (B,4,ch,cw) NCHW = bilinear resize
-    (align_corners=False, as F.interpolate) of the un-padded normalised packed RAW.  Returns (packed, cond)."""
+    (align_corners=False, as F.interpolate) of the un-padded normalised packed RAW.  Returns (packed, cond).
+    raw_format (a RawFormat): the frame's CFA phase, storage (incl. MIPI RAW10 / RAW12 lines) and per-position levels, which then
+    replace black_level / white_level (rc_raw_ingest_fmt)."""
+    if raw_format is not None:
+        return _raw_ingest_fmt(mosaic, dtype, pad_to, black_level, white_level, cond_hw, raw_format)
     mosaic = _mosaic3(mosaic)
     if not white_level > black_level:
         raise ValueError("white_level must exceed black_level")
@@ -478,6 +482,51 @@ def raw_ingest(mosaic: torch.Tensor, dtype: Optional[torch.dtype] = None, pad_to
         dtype = dtype or mosaic.dtype
     _DT[dtype]
     return _R.raw_ingest(mosaic, dtype, int(pad_to), float(black_level), float(white_level), int(cond_hw[0]), int(cond_hw[1]))
+
+
+_RAW_TENSOR_DTYPE = {"u16": torch.uint16, "u8": torch.uint8, "mipi10": torch.uint8, "mipi12": torch.uint8}
+_RAW_STORAGE = {"u16": _lib.RC_RAW_U16, "u8": _lib.RC_RAW_U8, "mipi10": _lib.RC_RAW_MIPI10, "mipi12": _lib.RC_RAW_MIPI12}
+
+
+def _raw_ingest_fmt(mosaic, dtype, pad_to, black_level, white_level, cond_hw, fmt):
+    from .raw_format import CFAS, RawFormat
+    if not isinstance(fmt, RawFormat):
+        raise TypeError(f"raw_format must be a RawFormat, got {type(fmt).__name__}")
+    if black_level != 0.0 or white_level != 1.0:
+        raise ValueError("raw_format carries the black / white levels: leave black_level / white_level at their defaults")
+    if not isinstance(mosaic, torch.Tensor):
+        raise TypeError("mosaic: expected a tensor")
+    _, w2 = fmt.validate(mosaic.shape)
+    want = _RAW_TENSOR_DTYPE.get(fmt.storage)
+    if want is None:
+        _dt(mosaic)
+        storage = _DT[mosaic.dtype]                         # RC_RAW_F32 / BF16 / F16 are the rc_dtype values
+        dtype = dtype or mosaic.dtype
+    else:
+        if mosaic.dtype != want:
+            raise TypeError(f"raw_format storage {fmt.storage!r} takes a {want} tensor, got {mosaic.dtype}")
+        if dtype is None:
+            raise ValueError(f"raw_ingest: give the activation dtype for a {fmt.storage} mosaic")
+        storage = _RAW_STORAGE[fmt.storage]
+    _DT[dtype]
+    mosaic = _req(mosaic, "mosaic")
+    if mosaic.dim() == 4:
+        mosaic = mosaic[:, 0]
+    return _R.raw_ingest_fmt(mosaic, dtype, int(pad_to), storage, CFAS[fmt.cfa], int(w2), list(fmt.blacks()), float(fmt.white_level),
+                             int(cond_hw[0]), int(cond_hw[1]))
+
+
+def rgb_encode(y: torch.Tensor, bits: int, crop_hw: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """Planar float result (B,3,H,W) -> interleaved (B,h,w,3) uint8 (bits 8) or uint16 (bits 16), cropped to crop_hw:
+    clamp(rint(float(y) * S), 0, S) with S = 2**bits - 1, round half to even, NaN -> 0 (rc_rgb_encode)."""
+    y = _req(y, "rgb_encode input")
+    if bits not in (8, 16):
+        raise ValueError(f"rgb_encode: bits must be 8 or 16, got {bits!r}")
+    if y.dim() != 4 or y.shape[1] != 3:
+        raise ValueError(f"rgb_encode: expected (B,3,H,W), got {tuple(y.shape)}")
+    _dt(y)
+    h, w = crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])
+    return _R.rgb_encode(y, int(bits), int(h), int(w))
 
 
 def make_coord(b: int, h: int, w: int, device=None, dtype: torch.dtype = torch.float32) -> torch.Tensor:

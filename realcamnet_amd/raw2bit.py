@@ -394,16 +394,21 @@ class raw_compression_tcm_final(nn.Module):
         dt = self._act_dtype()
         return self._forward_nhwc(ops.to_nhwc(raw, dtype=dt), cond, ops.to_nhwc(coord, dtype=dt))
 
-    def forward_mosaic(self, mosaic, cond, coord, pad_to: int = 128, black_level: float = 0.0, white_level: float = 1.0, cond_hw=(256, 256)):
+    def forward_mosaic(self, mosaic, cond, coord, pad_to: int = 128, black_level: float = 0.0, white_level: float = 1.0, cond_hw=(256, 256),
+                       raw_format=None, out_format=None):
         """Bayer mosaic (B,1,2h,2w), cond (B,4,hc,wc), coord (B,2,h,w) -> the same dict as forward().  The packed RAW and coord are
         zero-padded bottom/right to a multiple of `pad_to` (128: window 4 at 1/32 of the packed size), x_hat
-        is NOT cropped (it is the decoder's output for the padded frame)."""
+        is NOT cropped (it is the decoder's output for the padded frame).  raw_format: the sensor frame's layout (see
+        LiteISP._DwtUNet.forward_mosaic); out_format must stay None: x_hat is the padded decoder output, not an image to encode."""
         if self.training:
             raise RuntimeError("realcamnet_amd is an inference path: call .eval() first")
+        if out_format is not None:
+            raise ValueError("raw_compression_tcm_final.forward_mosaic returns the codec's dict: out_format is not supported")
         dt = self._act_dtype()
-        from .LiteISP import _ingest
-        a, cond = _ingest(self, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw)    # cond=None: resized packed RAW
-        if coord.shape[-2:] != (mosaic.shape[-2] // 2, mosaic.shape[-1] // 2):
+        from .LiteISP import _ingest, _mosaic_hw
+        mh, mw = _mosaic_hw(mosaic, raw_format)
+        a, cond = _ingest(self, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, raw_format)    # cond=None: resized packed RAW
+        if coord.shape[-2:] != (mh // 2, mw // 2):
             raise ValueError("coord must be at packed resolution (h, w)")
         return self._forward_nhwc(a, cond, ops.to_nhwc(coord, dtype=dt, pad_hw=(a.shape[1], a.shape[2])))
 

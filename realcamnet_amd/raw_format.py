@@ -1,0 +1,88 @@
+"""How a sensor frame is laid out: the `raw_format=` argument of forward_mosaic / ops.raw_ingest (include/realcam_hip.h, rc_raw_format).
+
+Pure Python: validation raises ValueError and never touches the GPU or the library.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple, Union
+
+from . import _lib
+
+CFAS = {"RGGB": _lib.RC_CFA_RGGB, "BGGR": _lib.RC_CFA_BGGR, "GRBG": _lib.RC_CFA_GRBG, "GBRG": _lib.RC_CFA_GBRG}
+STORAGES = ("float", "u16", "u8", "mipi10", "mipi12")
+PACKED_BITS = {"mipi10": 10, "mipi12": 12}
+# packed slot k (0 R, 1 G of the R row, 2 G of the B row, 3 B) <- cell position (row * 2 + col) of that colour in the 2x2 cell
+SLOT_POS = {"RGGB": (0, 1, 2, 3), "BGGR": (3, 2, 1, 0), "GRBG": (1, 0, 3, 2), "GBRG": (2, 3, 0, 1)}
+
+
+@dataclass(frozen=True)
+class RawFormat:
+    """A sensor frame's layout and levels.
+
+    cfa          colour of mosaic cell positions (0,0), (0,1), (1,0), (1,1): "RGGB" (default), "BGGR", "GRBG", "GBRG".  The packed map
+                 keeps the RGGB slot meaning; each slot reads its colour's position in the same 2x2 cell.
+    storage      "float" (the tensor's own fp32 / bf16 / fp16), "u16" (LSB-aligned counts), "u8", "mipi10", "mipi12" (MIPI CSI-2
+                 packed lines: a (B,[1,]2h,line_bytes) uint8 tensor, bytes past a line's samples ignored).
+    width        mosaic width 2w in samples; required for the MIPI storages (the tensor's last dimension is the line stride).
+    black_level  one float, or four in CFA-position order (DNG BlackLevel order).
+    white_level  must exceed every black level.
+    """
+
+    cfa: str = "RGGB"
+    storage: str = "float"
+    width: Optional[int] = None
+    black_level: Union[float, Tuple[float, float, float, float]] = 0.0
+    white_level: float = 1.0
+
+    @property
+    def packed(self) -> bool:
+        return self.storage in PACKED_BITS
+
+    def blacks(self) -> Tuple[float, float, float, float]:
+        b = self.black_level
+        if isinstance(b, (int, float)):
+            return (float(b),) * 4
+        return tuple(float(v) for v in b)
+
+    def min_line_bytes(self, width: int) -> int:
+        """Bytes of one MIPI-packed line of `width` samples."""
+        return math.ceil(width * PACKED_BITS[self.storage] / 8)
+
+    def validate(self, mosaic_shape: Sequence[int]) -> Tuple[int, int]:
+        """Check this format against a mosaic tensor's shape (B,[1,]2h,X); returns the mosaic size (2h, 2w).  X is 2w for the sample
+        storages and the line stride in bytes for the MIPI ones.  Raises ValueError."""
+        if self.cfa not in CFAS:
+            raise ValueError(f"RawFormat.cfa must be one of {sorted(CFAS)}, got {self.cfa!r}")
+        if self.storage not in STORAGES:
+            raise ValueError(f"RawFormat.storage must be one of {STORAGES}, got {self.storage!r}")
+        b = self.black_level
+        if not isinstance(b, (int, float)):
+            if isinstance(b, (str, bytes)) or not hasattr(b, "__len__") or len(b) != 4 or not all(isinstance(v, (int, float)) for v in b):
+                raise ValueError(f"RawFormat.black_level must be a float or four floats in CFA-position order, got {b!r}")
+        if not isinstance(self.white_level, (int, float)) or not all(float(self.white_level) > v for v in self.blacks()):
+            raise ValueError(f"RawFormat.white_level ({self.white_level!r}) must exceed every black level {self.blacks()}")
+        shape = tuple(int(s) for s in mosaic_shape)
+        if len(shape) == 4 and shape[1] == 1:
+            shape = (shape[0],) + shape[2:]
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError(f"mosaic must be (B,[1,]2h,X), got {tuple(mosaic_shape)}")
+        _, h2, x = shape
+        if h2 % 2:
+            raise ValueError(f"mosaic height must be even, got {h2}")
+        if self.packed:
+            if self.width is None:
+                raise ValueError(f"RawFormat.width is required for storage {self.storage!r}")
+            w2 = self.width
+        else:
+            w2 = x if self.width is None else self.width
+            if w2 != x:
+                raise ValueError(f"RawFormat.width {self.width} does not match the mosaic width {x}")
+        if not isinstance(w2, int) or w2 < 2 or w2 % 2:
+            raise ValueError(f"mosaic width must be a positive even number of samples, got {w2!r}")
+        if self.storage == "mipi10" and w2 % 4:
+            raise ValueError(f"RAW10 packs 4 samples in 5 bytes: the mosaic width must be a multiple of 4, got {w2}")
+        if self.packed and x < self.min_line_bytes(w2):
+            raise ValueError(f"{self.storage} line of {w2} samples needs {self.min_line_bytes(w2)} bytes, the tensor's lines have {x}")
+        return h2, w2

@@ -102,6 +102,35 @@ define("raw_ingest(Tensor mosaic, ScalarType dtype, int pad_to, float black, flo
        _ingest_alloc, _ingest_launch)
 
 
+def _fmt_alloc(src, dtype, pad_to, storage, cfa, width, black, white, cond_h, cond_w):
+    b, h2, _ = src.shape
+    h, w = h2 // 2, width // 2
+    return (src.new_empty((b, -(-h // pad_to) * pad_to, -(-w // pad_to) * pad_to, 4), dtype=dtype),
+            src.new_empty((b, 4, cond_h, cond_w), dtype=dtype))
+
+
+def _fmt_launch(outs, src, dtype, pad_to, storage, cfa, width, black, white, cond_h, cond_w):
+    packed, cond = outs
+    b, h2, x = src.shape
+    if src.data_ptr() % 4:
+        src = src.clone()                       # MIPI lines are read as whole dwords from a 4-byte aligned base (a view may start mid-dword)
+    d = _lib.RawFormatDesc(storage=storage, cfa=cfa, line_bytes=x * src.element_size(), width=width, white=float(white))
+    for k in range(4):
+        d.black[k] = float(black[k])
+    check(lib().rc_raw_ingest_fmt(src.data_ptr(), C.byref(d), packed.data_ptr(), cond.data_ptr(), _DT[dtype], b, h2 // 2, width // 2,
+                                  packed.shape[1], packed.shape[2], cond_h, cond_w, _stream()), "rc_raw_ingest_fmt")
+
+
+# src (B, 2h, X): X = 2w samples, or the line stride in bytes of a MIPI-packed frame; storage / cfa: rc_raw_storage / rc_cfa; black: 4 floats
+define("raw_ingest_fmt(Tensor src, ScalarType dtype, int pad_to, int storage, int cfa, int width, float[] black, float white, int cond_h, "
+       "int cond_w) -> (Tensor, Tensor)", _fmt_alloc, _fmt_launch)
+
+define("rgb_encode(Tensor y, int bits, int h, int w) -> Tensor",
+       lambda y, bits, h, w: y.new_empty((y.shape[0], h, w, 3), dtype=torch.uint8 if bits == 8 else torch.uint16),
+       lambda out, y, bits, h, w: check(lib().rc_rgb_encode(y.data_ptr(), _dt(y), out.data_ptr(), bits, y.shape[0], y.shape[2], y.shape[3], h, w,
+                                                            _stream()), "rc_rgb_encode"))
+
+
 define("nchw_to_nhwc(Tensor x, ScalarType dtype, int hp, int wp) -> Tensor",
        lambda x, dtype, hp, wp: x.new_empty((x.shape[0], hp, wp, x.shape[1]), dtype=dtype),
        lambda out, x, dtype, hp, wp: check(lib().rc_nchw_to_nhwc(x.data_ptr(), _dt(x), out.data_ptr(), _DT[dtype], x.shape[0], x.shape[1],

@@ -1,0 +1,275 @@
+"""GPU: sensor RAW formats for forward_mosaic (rc_raw_ingest_fmt, rc_rgb_encode).  Every check is bitwise: a phase-X frame against the
+RGGB frame with the same cell permutation through today's ingest, MIPI lines against their uint16 counts, per-position black levels
+against an fp32 restatement of the kernel's arithmetic, and the RGB encoding against torch quantisation of the float result."""
+import numpy as np
+import pytest
+import torch
+
+import liteisp_oracle as O
+import realcamnet_amd as M
+from realcamnet_amd import ops
+from realcamnet_amd.raw_format import SLOT_POS
+from test_raw_formats_host import mipi_pack
+
+DEV = "cuda"
+DTS = (torch.float32, torch.bfloat16, torch.float16)
+CFAS = ("RGGB", "BGGR", "GRBG", "GBRG")
+
+
+def to_phase(m_rggb: torch.Tensor, cfa: str) -> torch.Tensor:
+    """The phase-`cfa` mosaic whose packed slot k (read at its colour's cell position) is slot k of the RGGB mosaic m_rggb."""
+    m = torch.empty_like(m_rggb)
+    for k, pos in enumerate(SLOT_POS[cfa]):
+        m[..., pos >> 1::2, pos & 1::2] = m_rggb[..., k >> 1::2, k & 1::2]
+    return m
+
+
+def counts(shape, bits, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(0, 1 << bits, shape, generator=g, dtype=torch.int32).to(torch.uint16)
+
+
+def lines_of(c: torch.Tensor, bits: int, line_bytes: int = 0) -> torch.Tensor:
+    return torch.from_numpy(mipi_pack(c.to(torch.int32).numpy(), bits, line_bytes))
+
+
+def restated_ingest(mosaic, cfa, blacks, white, dt, pad_to, cond_hw):
+    """fp32 torch restatement of rc_raw_ingest_fmt: v' = (v - black[pos]) * (1 / (white - black[pos])) per slot, zero pad, and cond with
+    the kernel's own bilinear tap arithmetic (raw_ingest_kernel's F.interpolate(align_corners=False) rules, same operation order)."""
+    f32 = torch.float32
+    m = mosaic.to(f32)
+    planes = []
+    for k, pos in enumerate(SLOT_POS[cfa]):
+        bk = torch.tensor(blacks[pos], dtype=f32)
+        inv = torch.tensor(1.0, dtype=f32) / (torch.tensor(white, dtype=f32) - bk)
+        planes.append((m[..., pos >> 1::2, pos & 1::2] - bk) * inv)
+    norm = torch.stack(planes, 1)                                    # (B,4,h,w)
+    b, _, h, w = norm.shape
+    hp, wp = -(-h // pad_to) * pad_to, -(-w // pad_to) * pad_to
+    packed = torch.zeros(b, hp, wp, 4, dtype=f32)
+    packed[:, :h, :w] = norm.permute(0, 2, 3, 1)
+
+    def taps(n_in, n_out):
+        s = torch.tensor(n_in, dtype=f32) / torch.tensor(n_out, dtype=f32)
+        src = (s * (torch.arange(n_out, dtype=f32) + 0.5) - 0.5).clamp_min(0.0)
+        i0 = src.to(torch.int64).clamp_max(n_in - 1)
+        i1 = i0 + (i0 < n_in - 1).to(torch.int64)
+        l1 = src - i0.to(f32)
+        return i0, i1, 1.0 - l1, l1
+
+    y0, y1, ly0, ly1 = taps(h, cond_hw[0])
+    x0, x1, lx0, lx1 = taps(w, cond_hw[1])
+    ly0, ly1 = ly0[:, None], ly1[:, None]
+    v00, v01 = norm[:, :, y0][..., x0], norm[:, :, y0][..., x1]
+    v10, v11 = norm[:, :, y1][..., x0], norm[:, :, y1][..., x1]
+    cond = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11)
+    return packed.to(dt), cond.to(dt)
+
+
+def same(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.cpu(), b.cpu())
+
+
+# ---- 1. CFA phase -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfa", CFAS)
+@pytest.mark.parametrize("dt", DTS)
+def test_phase_equals_permuted_rggb(hip, cfa, dt):
+    g = torch.Generator().manual_seed(11)
+    m_rggb = torch.rand(2, 1, 2 * 13, 2 * 21, generator=g).to(dt)
+    m = to_phase(m_rggb, cfa)
+    fmt = M.RawFormat(cfa=cfa, black_level=0.0625, white_level=0.9375)
+    got = ops.raw_ingest(m.to(DEV), dtype=dt, pad_to=16, cond_hw=(24, 40), raw_format=fmt)
+    want = ops.raw_ingest(m_rggb.to(DEV), dtype=dt, pad_to=16, black_level=0.0625, white_level=0.9375, cond_hw=(24, 40))
+    assert same(got[0], want[0]) and same(got[1], want[1])
+    c_rggb = counts((2, 2 * 13, 2 * 21), 10, 12)                    # uint16 counts, activation dtype dt
+    c = to_phase(c_rggb.to(torch.int32), cfa).to(torch.uint16)
+    got = ops.raw_ingest(c.to(DEV), dtype=dt, pad_to=16, cond_hw=(9, 50), raw_format=M.RawFormat(cfa=cfa, storage="u16", black_level=64, white_level=1023))
+    want = ops.raw_ingest(c_rggb.to(DEV), dtype=dt, pad_to=16, black_level=64.0, white_level=1023.0, cond_hw=(9, 50))
+    assert same(got[0], want[0]) and same(got[1], want[1])
+
+
+# ---- 2. per-position black levels ---------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", DTS)
+def test_black_levels(hip, dt):
+    c = counts((2, 2 * 19, 2 * 27), 12, 21)
+    equal = M.RawFormat(storage="u16", black_level=(256.0,) * 4, white_level=4095)
+    got = ops.raw_ingest(c.to(DEV), dtype=dt, pad_to=16, cond_hw=(32, 48), raw_format=equal)
+    want = ops.raw_ingest(c.to(DEV), dtype=dt, pad_to=16, black_level=256.0, white_level=4095.0, cond_hw=(32, 48))
+    assert same(got[0], want[0]) and same(got[1], want[1])
+    for cfa in CFAS:
+        blacks = (240.0, 256.5, 251.0, 263.25)
+        got = ops.raw_ingest(c.to(DEV), dtype=dt, pad_to=16, cond_hw=(32, 48),
+                             raw_format=M.RawFormat(cfa=cfa, storage="u16", black_level=blacks, white_level=4095))
+        want = restated_ingest(c, cfa, blacks, 4095.0, dt, 16, (32, 48))
+        assert same(got[0], want[0]) and same(got[1], want[1]), cfa
+
+
+# ---- 3. MIPI RAW10 / RAW12 and u8 ---------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("bits,w2,line_bytes", [(10, 44, 0), (10, 44, 64), (10, 44, 61), (10, 600, 768), (10, 600, 753),
+                                                (12, 42, 0), (12, 42, 64), (12, 42, 67), (12, 602, 903), (12, 602, 1024)])
+@pytest.mark.parametrize("dt", (torch.float32, torch.bfloat16))
+def test_mipi_equals_u16_counts(hip, bits, w2, line_bytes, dt):
+    c = counts((2, 26, w2), bits, bits + w2)
+    blacks = (64.0, 66.0, 60.0, 63.5) if bits == 10 else (256.0, 250.0, 261.0, 256.0)
+    white = float((1 << bits) - 1)
+    for cfa in ("GRBG", "BGGR"):
+        kw = dict(cfa=cfa, black_level=blacks, white_level=white)
+        got = ops.raw_ingest(lines_of(c, bits, line_bytes).to(DEV), dtype=dt, pad_to=16, cond_hw=(20, 30),
+                             raw_format=M.RawFormat(storage=f"mipi{bits}", width=w2, **kw))
+        want = ops.raw_ingest(c.to(DEV), dtype=dt, pad_to=16, cond_hw=(20, 30), raw_format=M.RawFormat(storage="u16", **kw))
+        assert same(got[0], want[0]) and same(got[1], want[1]), cfa
+    # RGGB, equal blacks: today's scalar rc_raw_ingest on the counts
+    got = ops.raw_ingest(lines_of(c, bits, line_bytes).to(DEV), dtype=dt, pad_to=1, cond_hw=(20, 30),
+                         raw_format=M.RawFormat(storage=f"mipi{bits}", width=w2, black_level=64.0, white_level=white))
+    want = ops.raw_ingest(c.to(DEV), dtype=dt, pad_to=1, cond_hw=(20, 30), black_level=64.0, white_level=white)
+    assert same(got[0], want[0]) and same(got[1], want[1])
+
+
+@pytest.mark.gpu
+def test_mipi_line_stride_view_and_padding_bytes_are_ignored(hip):
+    """The bytes past a line's samples never reach the result, and a frame that starts at an odd byte (a view) is read right."""
+    c = counts((1, 24, 40), 10, 5)
+    fmt = M.RawFormat(storage="mipi10", width=40, cfa="GBRG")
+    a = lines_of(c, 10, 57)
+    b = a.clone()
+    b[..., 50:] = 0x5A
+    ra = ops.raw_ingest(a.to(DEV), dtype=torch.float32, raw_format=fmt, cond_hw=(8, 8))
+    rb = ops.raw_ingest(b.to(DEV), dtype=torch.float32, raw_format=fmt, cond_hw=(8, 8))
+    buf = torch.zeros(a.numel() + 3, dtype=torch.uint8)
+    buf[3:] = a.flatten()
+    rv = ops.raw_ingest(buf.to(DEV)[3:].view(a.shape), dtype=torch.float32, raw_format=fmt, cond_hw=(8, 8))
+    assert same(ra[0], rb[0]) and same(ra[1], rb[1]) and same(ra[0], rv[0]) and same(ra[1], rv[1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", DTS)
+def test_u8_equals_u16(hip, dt):
+    c = counts((2, 1, 30, 46), 8, 3)
+    for cfa in CFAS:
+        kw = dict(cfa=cfa, black_level=(16.0, 17.0, 15.0, 16.0), white_level=255.0)
+        got = ops.raw_ingest(c.to(torch.uint8).to(DEV), dtype=dt, raw_format=M.RawFormat(storage="u8", **kw), cond_hw=(16, 16))
+        want = ops.raw_ingest(c.to(DEV), dtype=dt, raw_format=M.RawFormat(storage="u16", **kw), cond_hw=(16, 16))
+        assert same(got[0], want[0]) and same(got[1], want[1]), cfa
+
+
+# ---- 4. end to end ------------------------------------------------------------------------------------------------------------------
+_NETS = {}
+
+
+def net_on_gpu(name, dt, **kw):
+    key = (name, dt)
+    if key not in _NETS:
+        torch.manual_seed(0)
+        _NETS[key] = getattr(M, name)(**kw).to(device=DEV, dtype=dt).eval()
+    return _NETS[key]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,dt", [("LiteISPNet_GFM_LSC", torch.float32), ("LiteISPNet_GFM_LSC", torch.bfloat16), ("LiteISPNet_GFM_LSC", torch.float16),
+                                     ("ISPUNet_GFM_LSC", torch.float32), ("ISPUNet_GFM_LSC", torch.bfloat16)])
+def test_forward_mosaic_raw10_gbrg_equals_rggb_u16(hip, name, dt):
+    c_rggb = counts((2, 1, 2 * 40, 2 * 56), 10, 31)
+    lines = lines_of(to_phase(c_rggb.to(torch.int32), "GBRG")[:, 0], 10, 160).unsqueeze(1)
+    coord = O.make_coord(2, 40, 56).to(DEV, dt)
+    net = net_on_gpu(name, dt)
+    fmt = M.RawFormat(cfa="GBRG", storage="mipi10", width=112, black_level=64.0, white_level=1023.0)
+    with torch.no_grad():
+        got = net.forward_mosaic(lines.to(DEV), None, coord, raw_format=fmt)
+        want = net.forward_mosaic(c_rggb.to(DEV), None, coord, black_level=64.0, white_level=1023.0)
+    assert got.shape == (2, 3, 80, 112) and same(got, want)
+
+
+@pytest.mark.gpu
+def test_codec_forward_mosaic_raw10_gbrg_equals_rggb_u16(hip):
+    import realcamnet_amd.raw2bit as RB
+    torch.manual_seed(0)
+    net = RB.raw_compression_tcm_final(N=32).to(device=DEV, dtype=torch.bfloat16).eval()
+    c_rggb = counts((1, 1, 512, 512), 10, 41)
+    lines = lines_of(to_phase(c_rggb.to(torch.int32), "GBRG")[:, 0], 10, 640).unsqueeze(1)
+    coord = O.make_coord(1, 256, 256).to(DEV, torch.bfloat16)
+    fmt = M.RawFormat(cfa="GBRG", storage="mipi10", width=512, black_level=64.0, white_level=1023.0)
+    with torch.no_grad():
+        got = net.forward_mosaic(lines.to(DEV), None, coord, raw_format=fmt)
+        want = net.forward_mosaic(c_rggb.to(DEV), None, coord, black_level=64.0, white_level=1023.0)
+    assert set(got) == set(want)
+    assert same(got["x_hat"], want["x_hat"]) and same(got["y"], want["y"])
+    for k in want["likelihoods"]:
+        assert same(got["likelihoods"][k], want["likelihoods"][k]), k
+
+
+# ---- 5. RGB out ---------------------------------------------------------------------------------------------------------------------
+def torch_quantise(y, bits):
+    s = float((1 << bits) - 1)
+    return (y.float().cpu() * s).round().clamp(0, s).to(torch.uint8 if bits == 8 else torch.uint16).permute(0, 2, 3, 1).contiguous()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dt", DTS)
+@pytest.mark.parametrize("bits", (8, 16))
+def test_rgb_encode_equals_torch_quantisation(hip, dt, bits):
+    g = torch.Generator().manual_seed(bits)
+    s = (1 << bits) - 1
+    for b, hh, ww in ((2, 37, 53), (1, 16, 64), (2, 8, 48)):
+        y = (torch.rand(b, 3, hh, ww, generator=g) * 1.6 - 0.3)             # values outside [0, 1] clamp
+        ties = (torch.arange(hh * ww, dtype=torch.float32).view(1, hh, ww) % (s + 1) + 0.5) / s
+        y[:, 1] = ties                                                      # exact halves of the scaled value, before rounding to dt
+        y[0, 2, 0, :4] = torch.tensor([float("inf"), float("-inf"), 1.0, 0.0])
+        y = y.to(dt)
+        got = ops.rgb_encode(y.to(DEV), bits)
+        assert same(got, torch_quantise(y, bits))
+        big = torch.zeros(b, 3, hh + 3, ww + 5, dtype=dt)
+        big[:, :, :hh, :ww] = y
+        assert same(ops.rgb_encode(big.to(DEV), bits, crop_hw=(hh, ww)), torch_quantise(y, bits))
+    nan = torch.full((1, 3, 2, 8), float("nan"), dtype=dt)
+    assert ops.rgb_encode(nan.to(DEV), bits).cpu().to(torch.int32).abs().sum() == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,dt", [("LiteISPNet_GFM_LSC", torch.float32), ("LiteISPNet_GFM_LSC", torch.bfloat16), ("LiteISPNet_GFM_LSC", torch.float16),
+                                     ("ISPUNet_GFM_LSC", torch.bfloat16)])
+def test_forward_mosaic_out_format(hip, name, dt):
+    g = torch.Generator().manual_seed(7)
+    mosaic = (torch.rand(2, 1, 2 * 24, 2 * 40, generator=g) * 1.4 - 0.2).to(DEV, dt)
+    coord = O.make_coord(2, 24, 40).to(DEV, dt)
+    net = net_on_gpu(name, dt)
+    with torch.no_grad():
+        y = net.forward_mosaic(mosaic, None, coord)
+        q8 = net.forward_mosaic(mosaic, None, coord, out_format="rgb8")
+        q16 = net.forward_mosaic(mosaic, None, coord, out_format="rgb16")
+    assert same(q8, torch_quantise(y, 8)) and same(q16, torch_quantise(y, 16))
+
+
+# ---- 6. graph capture ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_graphed_formatted_forward_equals_eager(hip):
+    net = net_on_gpu("LiteISPNet_GFM_LSC", torch.bfloat16)
+    fmt = M.RawFormat(cfa="BGGR", storage="mipi12", width=112, black_level=(256.0, 250.0, 258.0, 256.0), white_level=4095.0)
+    lines = lines_of(counts((2, 80, 112), 12, 77), 12, 176).to(DEV)
+    coord = O.make_coord(2, 40, 56).to(DEV, torch.bfloat16)
+    call = M.GraphedCall(lambda x, co: net.forward_mosaic(x, None, co, raw_format=fmt, out_format="rgb8"))
+    with torch.no_grad():
+        eager = net.forward_mosaic(lines, None, coord, raw_format=fmt, out_format="rgb8")
+    g1 = call(lines, coord).clone()
+    lines2 = lines_of(counts((2, 80, 112), 12, 78), 12, 176).to(DEV)
+    g2 = call(lines2, coord).clone()
+    with torch.no_grad():
+        eager2 = net.forward_mosaic(lines2, None, coord, raw_format=fmt, out_format="rgb8")
+    assert g1.dtype == torch.uint8 and g1.shape == (2, 80, 112, 3)
+    assert same(g1, eager) and same(g2, eager2) and not torch.equal(g1, g2)
+
+
+# ---- 7. full size -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_4k_raw10_bggr_gma_equals_rggb_u16(hip):
+    c_rggb = counts((1, 1, 2160, 3840), 10, 2160)
+    lines = lines_of(to_phase(c_rggb.to(torch.int32), "BGGR")[:, 0], 10, 4864).unsqueeze(1)       # 4800 bytes of samples, 64-byte stride
+    coord = O.make_coord(1, 1080, 1920).to(DEV, torch.bfloat16)
+    net = net_on_gpu("LiteISPNet_GFM_LSC_GMA", torch.bfloat16)
+    fmt = M.RawFormat(cfa="BGGR", storage="mipi10", width=3840, black_level=64.0, white_level=1023.0)
+    with torch.no_grad():
+        got = net.forward_mosaic(lines.to(DEV), None, coord, raw_format=fmt)
+        want = net.forward_mosaic(c_rggb.to(DEV), None, coord, black_level=64.0, white_level=1023.0)
+    assert got.shape == (1, 3, 2160, 3840) and same(got, want)
