@@ -131,6 +131,53 @@ int rc_raw_ingest_fmt(const void* d_src, const rc_raw_format* fmt, void* d_packe
  * aligned: q = clamp(rint(float(y) * S), 0, S), S = 255 or 65535, round half to even, NaN -> 0. */
 int rc_rgb_encode(const void* d_src, int src_dtype, void* d_dst, int out_bits, int batch, int H, int W, int h, int w, void* stream);
 
+/* ---- video-encoder out (ABI 15, additive): the same planar result as one Y'CbCr 4:2:0 surface per frame -------------------------------
+ * What hardware and software video encoders take: NV12 / I420 (8 bit) and P010 (10 bit), with the caller's row pitch and plane
+ * offsets.  One launch that reads the result once; pitch and height padding is written as zero by the same launch. */
+typedef enum rc_yuv_layout {
+    RC_YUV_NV12 = 0,   /* uint8: Y plane, then one plane of interleaved Cb,Cr pairs at half size, same pitch */
+    RC_YUV_P010 = 1,   /* NV12's planes as uint16, the 10-bit code in the HIGH bits (code << 6); pitch and offsets still in bytes */
+    RC_YUV_I420 = 2    /* uint8: Y, Cb, Cr planes; the chroma pitch is pitch / 2 */
+} rc_yuv_layout;
+typedef enum rc_yuv_matrix { RC_MATRIX_BT601 = 0, RC_MATRIX_BT709 = 1, RC_MATRIX_BT2020 = 2 /* its luma coefficients only: no gamut conversion */ } rc_yuv_matrix;
+typedef enum rc_yuv_range { RC_RANGE_LIMITED = 0, RC_RANGE_FULL = 1 } rc_yuv_range;
+typedef enum rc_chroma_siting { RC_SITING_LEFT = 0 /* co-sited with the even column, between the rows: MPEG-2 / H.264 / HEVC */,
+                                RC_SITING_CENTER = 1 /* the middle of the 2x2 block: JPEG / MPEG-1 */ } rc_chroma_siting;
+
+/* The one table of luma coefficients {Kr, Kb} per rc_yuv_matrix.  Kg = 1 - Kr - Kb, sb = 0.5 / (1 - Kb), sr = 0.5 / (1 - Kr) are
+ * computed from it in double and rounded to fp32 once. */
+#define RC_YUV_KR_KB {{0.299, 0.114}, {0.2126, 0.0722}, {0.2627, 0.0593}}
+
+typedef struct rc_out_format {
+    int layout;            /* rc_yuv_layout */
+    int matrix;            /* rc_yuv_matrix */
+    int range;             /* rc_yuv_range */
+    int siting;            /* rc_chroma_siting */
+    int pitch;             /* bytes from one Y row to the next, >= the row's bytes, a multiple of the sample size (I420: even); 0: exactly the
+                              row's bytes.  A multiple of 16 (with 16-byte aligned offsets) takes the 16-byte store path */
+    int rows;              /* allocated rows of the Y plane, >= h; 0: h.  A chroma plane has ceil(rows / 2) allocated rows */
+    int chroma_offset[2];  /* bytes from the frame's start to the CbCr plane (NV12 / P010) or the Cb and Cr planes (I420); 0: packed behind
+                              the plane before.  Planes must not overlap */
+    int reserved[4];       /* zero */
+} rc_out_format;
+size_t rc_out_format_size(void);
+
+/* Bytes of one frame of (h, w) pixels: the end of its last plane, allocated rows included (frame b of a batch starts at b times this).
+ * 0 and rc_last_error() for a format rc_yuv_encode would refuse. */
+size_t rc_yuv_frame_bytes(const rc_out_format* fmt, int h, int w);
+
+/* src (B,3,H,W) RC_F32 / RC_BF16 / RC_F16 planar R,G,B, cropped to (h,w), both even; d_dst 16-byte aligned, batch * rc_yuv_frame_bytes.
+ * fp32, every product and every sum rounded on its own in the order written (no fused multiply-add):
+ *   r,g,b = float(src), NaN -> 0, clamped to [0,1];  Y = ((Kr r) + (Kg g)) + (Kb b);  Cb = (b - Y) sb;  Cr = (r - Y) sr
+ *   4:2:0 of the unquantised Cb, Cr, for block rows 2j, 2j+1 and columns 2i, 2i+1:
+ *     CENTER  ((c[2j][2i] + c[2j][2i+1]) + (c[2j+1][2i] + c[2j+1][2i+1])) 0.25
+ *     LEFT    per row t = ((c[x-1] + c[x+1]) + (c[x] + c[x])) 0.25 with x = 2i, x-1 clamped to column 0; then (t[2j] + t[2j+1]) 0.5
+ *   code = clamp(rint(v S + O), lo, hi), round half to even; n = 8 or 10 bits, k = 2^(n-8):
+ *     LIMITED  Y: S 219k, O 16k, [16k, 235k]; chroma: S 224k, O 128k, [16k, 240k].  FULL  S 2^n - 1, O 0 (Y) / 2^(n-1) (chroma), [0, 2^n - 1]
+ * Every byte of the Y plane's rows x pitch and of the chroma planes' ceil(rows / 2) x pitch that is not a sample is written as zero.
+ * Odd h / w, a pitch below the row's bytes, overlapping planes, a misaligned d_dst: RC_ERR_INVALID before any launch. */
+int rc_yuv_encode(const void* d_src, int src_dtype, const rc_out_format* fmt, void* d_dst, int batch, int H, int W, int h, int w, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

@@ -17,6 +17,7 @@ from . import networks as N
 from . import ops
 from .groupmix import GMA_Block, SUPPORTED_DTYPES
 from ._lib import RC_OUT_NCHW, RC_OUT_PIXEL_SHUFFLE2
+from .out_format import OutFormat
 
 
 def color_block(in_filters, out_filters, normalization=False):
@@ -279,14 +280,22 @@ _OUT_BITS = {None: None, "rgb8": 8, "rgb16": 16}
 
 
 def _out_bits(out_format):
+    """What _encode does with the result: None (as it is), 8 / 16 (interleaved RGB) or the OutFormat itself (an encoder surface)."""
+    if isinstance(out_format, OutFormat):
+        return out_format
+    if out_format is not None and not isinstance(out_format, str):
+        raise TypeError(f"out_format must be None, 'rgb8', 'rgb16' or an OutFormat, got {type(out_format).__name__}")
     if out_format not in _OUT_BITS:
-        raise ValueError(f"out_format must be None, 'rgb8' or 'rgb16', got {out_format!r}")
+        raise ValueError(f"out_format must be None, 'rgb8', 'rgb16' or an OutFormat, got {out_format!r}")
     return _OUT_BITS[out_format]
 
 
 def _encode(y, bits):
-    """out_format: the planar float sRGB (B,3,2h,2w) as it is, or interleaved (B,2h,2w,3) uint8 / uint16 (rc_rgb_encode)."""
-    return y if bits is None else ops.rgb_encode(y, bits)
+    """out_format: the planar float sRGB (B,3,2h,2w) as it is, interleaved (B,2h,2w,3) uint8 / uint16 (rc_rgb_encode), or a YuvFrames
+    holding one Y'CbCr 4:2:0 surface per frame (rc_yuv_encode)."""
+    if bits is None:
+        return y
+    return ops.yuv_encode(y, bits) if isinstance(bits, OutFormat) else ops.rgb_encode(y, bits)
 
 
 class _DwtUNet(nn.Module):
@@ -397,7 +406,8 @@ class _DwtUNet(nn.Module):
         upstream LiteISP.py:84-105) and the output is cropped back.  cond=None on a net with a colour prior: the fused ingest
         kernel (ops.raw_ingest) also produces cond = bilinear resize of the normalised packed RAW to `cond_hw`.
         raw_format (a RawFormat): the sensor frame's CFA phase, storage (MIPI RAW10 / RAW12 lines: (B,[1,]2h,line_bytes) uint8) and
-        per-position levels.  out_format "rgb8" / "rgb16": the result as interleaved (B,2h,2w,3) uint8 / uint16."""
+        per-position levels.  out_format "rgb8" / "rgb16": the result as interleaved (B,2h,2w,3) uint8 / uint16; an OutFormat: a YuvFrames
+        (one NV12 / P010 / I420 encoder surface per frame, and views of its planes)."""
         if self.training:
             raise RuntimeError("realcamnet_amd is an inference path: call .eval() first")
         bits = _out_bits(out_format)

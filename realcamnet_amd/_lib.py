@@ -20,6 +20,10 @@ RC_OUT_NHWC, RC_OUT_PIXEL_SHUFFLE2, RC_OUT_NCHW, RC_OUT_PIXEL_SHUFFLE2_NCHW, RC_
 ABI_VERSION = 15
 RC_RAW_F32, RC_RAW_BF16, RC_RAW_U16, RC_RAW_F16, RC_RAW_U8, RC_RAW_MIPI10, RC_RAW_MIPI12 = 0, 1, 2, 3, 4, 5, 6
 RC_CFA_RGGB, RC_CFA_BGGR, RC_CFA_GRBG, RC_CFA_GBRG = 0, 1, 2, 3
+RC_YUV_NV12, RC_YUV_P010, RC_YUV_I420 = 0, 1, 2
+RC_MATRIX_BT601, RC_MATRIX_BT709, RC_MATRIX_BT2020 = 0, 1, 2
+RC_RANGE_LIMITED, RC_RANGE_FULL = 0, 1
+RC_SITING_LEFT, RC_SITING_CENTER = 0, 1
 
 
 class ConvDesc(C.Structure):
@@ -65,6 +69,14 @@ class RawFormatDesc(C.Structure):
     ]
 
 
+class OutFormatDesc(C.Structure):
+    """Mirror of `struct rc_out_format`."""
+    _fields_ = [
+        ("layout", C.c_int32), ("matrix", C.c_int32), ("range", C.c_int32), ("siting", C.c_int32),
+        ("pitch", C.c_int32), ("rows", C.c_int32), ("chroma_offset", C.c_int32 * 2), ("reserved", C.c_int32 * 4),
+    ]
+
+
 def declared_symbols() -> list[str]:
     """Every function the public header declares (used by the CPU-side ABI test)."""
     text = HEADER.read_text()
@@ -83,6 +95,9 @@ _SIGS = {
     "rc_raw_format_size": (_SZ, []),
     "rc_raw_ingest_fmt": (C.c_int, [_P, C.POINTER(RawFormatDesc), _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_rgb_encode": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "rc_out_format_size": (_SZ, []),
+    "rc_yuv_frame_bytes": (_SZ, [C.POINTER(OutFormatDesc), _I, _I]),
+    "rc_yuv_encode": (C.c_int, [_P, _I, C.POINTER(OutFormatDesc), _P, _I, _I, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

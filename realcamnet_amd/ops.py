@@ -529,6 +529,31 @@ def rgb_encode(y: torch.Tensor, bits: int, crop_hw: Optional[Tuple[int, int]] = 
     return _R.rgb_encode(y, int(bits), int(h), int(w))
 
 
+def yuv_encode(y: torch.Tensor, fmt, crop_hw: Optional[Tuple[int, int]] = None):
+    """Planar float result (B,3,H,W), cropped to crop_hw (even), -> a YuvFrames: one Y'CbCr 4:2:0 encoder surface per frame (NV12 / P010 /
+    I420 with the format's matrix, range, chroma siting, pitch and height alignment) in one allocation, and views of its planes.
+    One launch; padding bytes are zero (rc_yuv_encode; the arithmetic is fixed in include/realcam_hip.h)."""
+    from .out_format import LAYOUTS, MATRICES, RANGES, SITINGS, OutFormat, YuvFrames
+    if not isinstance(fmt, OutFormat):
+        raise TypeError(f"yuv_encode: fmt must be an OutFormat, got {type(fmt).__name__}")
+    y = _req(y, "yuv_encode input")
+    if y.dim() != 4 or y.shape[1] != 3:
+        raise ValueError(f"yuv_encode: expected (B,3,H,W), got {tuple(y.shape)}")
+    _dt(y)
+    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
+    if h > y.shape[2] or w > y.shape[3]:
+        raise ValueError(f"yuv_encode: crop {(h, w)} exceeds the source {tuple(y.shape[2:])}")
+    pl = fmt.plane_layout(h, w)
+    buf = _R.yuv_encode(y, LAYOUTS[fmt.layout], MATRICES[fmt.matrix], RANGES[fmt.range], SITINGS[fmt.chroma_siting], pl.pitch,
+                        pl.planes[0].alloc_rows, h, w)
+    es, views = pl.elem_bytes, []
+    for p in pl.planes:
+        v = buf[:, p.offset // es:(p.offset + p.pitch * p.alloc_rows) // es].unflatten(1, (p.alloc_rows, p.pitch // es))
+        v = v[:, :p.rows, :p.valid_bytes // es]
+        views.append(v.unflatten(2, (w // 2, 2)) if p.name == "cbcr" else v)
+    return YuvFrames(buf, tuple(views))
+
+
 def make_coord(b: int, h: int, w: int, device=None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """Normalised pixel-coordinate map (B,2,h,w) in [-1,1], channel 0 = y, channel 1 = x: the lens-shading branch's input x[2]
     (upstream never published its generator; build convention).  Plain tensor construction, no kernel."""

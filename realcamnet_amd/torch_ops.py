@@ -131,6 +131,27 @@ define("rgb_encode(Tensor y, int bits, int h, int w) -> Tensor",
                                                             _stream()), "rc_rgb_encode"))
 
 
+def _yuv_alloc(y, layout, matrix, range_, siting, pitch, rows, h, w):
+    from .out_format import frame_layout
+    pl = frame_layout(layout, pitch, rows, h, w)
+    return y.new_empty((y.shape[0], pl.frame_bytes // pl.elem_bytes), dtype=torch.uint8 if pl.elem_bytes == 1 else torch.uint16)
+
+
+def _yuv_launch(out, y, layout, matrix, range_, siting, pitch, rows, h, w):
+    d = _lib.OutFormatDesc(layout=layout, matrix=matrix, range=range_, siting=siting, pitch=pitch, rows=rows)
+    nbytes = lib().rc_yuv_frame_bytes(C.byref(d), h, w)
+    if nbytes == 0:
+        check(-1, "rc_yuv_frame_bytes")
+    if nbytes != out.shape[1] * out.element_size():
+        raise RuntimeError(f"yuv_encode: the library plans {nbytes} bytes per frame, the binding {out.shape[1] * out.element_size()}")
+    check(lib().rc_yuv_encode(y.data_ptr(), _dt(y), C.byref(d), out.data_ptr(), y.shape[0], y.shape[2], y.shape[3], h, w, _stream()),
+          "rc_yuv_encode")
+
+
+# y (B,3,H,W) planar sRGB cropped to (h,w) -> (B, frame_elems) uint8 / uint16: one packed Y'CbCr 4:2:0 frame per batch entry; layout /
+# matrix / range / siting: the rc_yuv_* enums; pitch in bytes, rows = allocated Y rows
+define("yuv_encode(Tensor y, int layout, int matrix, int vrange, int siting, int pitch, int rows, int h, int w) -> Tensor", _yuv_alloc, _yuv_launch)
+
 define("nchw_to_nhwc(Tensor x, ScalarType dtype, int hp, int wp) -> Tensor",
        lambda x, dtype, hp, wp: x.new_empty((x.shape[0], hp, wp, x.shape[1]), dtype=dtype),
        lambda out, x, dtype, hp, wp: check(lib().rc_nchw_to_nhwc(x.data_ptr(), _dt(x), out.data_ptr(), _DT[dtype], x.shape[0], x.shape[1],
