@@ -423,6 +423,7 @@ int rc_channel_sums(const void* d_x, int dtype, int batch, int n_pix, int c, flo
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(batch >= 1 && batch <= 65535 && n_pix >= 1 && c >= U && c % U == 0 && c / U <= 256,
                "rc_channel_sums: C must be a multiple of 16 bytes, at most 256 vectors");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_x) % 16 == 0, "rc_channel_sums: 16-byte alignment");
     const int slots = rc_channel_sums_slots(n_pix);
     const int L = ceil_div(n_pix, slots);
     const size_t lds = (size_t)(256 / (c / U)) * c * sizeof(float);

@@ -15,6 +15,7 @@ struct ConvPlan {
 static int g_persist_on = 1;       // rc_debug_set("persist", v): 0 general kernel only, 1 automatic (default), 2 producer/consumer wherever eligible, 3 persistent only
 extern int g_dw3_seg16;            // gma.hip
 extern int g_dec_lds;              // rans.hip
+extern int g_pw_grid_cap;          // pointwise.hip
 static int g_pss = 0;              // rc_debug_set("pss", v): 1: single-chunk pixel-shuffle layers (the tail 48 -> 192) take kernel 5 (output staged through LDS, stored by the
                                    // loader waves); 0 (default): kernel 4.  Measured on MI355X at 8 x 1088 x 1920: 3.16-3.29 vs 3.24-3.27 ms (conv_kernel.hpp, kernel 5)
 static int g_poison = 0;           // rc_debug_set("lds_poison", 1): every rc_conv2d launch is preceded by rc_debug_poison_lds (bf16 NaNs in all LDS) -- test aid
@@ -300,6 +301,7 @@ int rc_debug_set(const char* key, int value) {
     if (std::string(key) == "lds_poison") { g_poison = value != 0; return RC_OK; }
     if (std::string(key) == "conv32") { g_conv32 = value < 0 ? 0 : (value > 4 ? 4 : value); return RC_OK; }
     if (std::string(key) == "wino_nnt") { wino_set_nnt(value); return RC_OK; }
+    if (std::string(key) == "pw_grid_cap") { g_pw_grid_cap = value <= 0 || value > (1 << 22) ? (1 << 22) : value; return RC_OK; }
     return fail(RC_ERR_INVALID, std::string("rc_debug_set: unknown key ") + key);
 }
 
@@ -314,6 +316,7 @@ int rc_debug_get(const char* key) {
     if (std::string(key) == "thin") return g_thin;
     if (std::string(key) == "lds_poison") return g_poison;
     if (std::string(key) == "wino_nnt") return wino_get_nnt();
+    if (std::string(key) == "pw_grid_cap") return g_pw_grid_cap;
     return -1;
 }
 

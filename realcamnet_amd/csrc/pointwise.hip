@@ -9,10 +9,13 @@ constexpr int kPwThreads = 256;
 
 // One-shot grids: this part streams fastest when every thread handles one 16-byte item and the hardware scheduler orders the blocks
 // (tools/hbm_probe.py: copy 5.9 TB/s one-shot vs 4.8-5.0 TB/s from a 4096-block grid-stride loop); the loops remain for sizes past the cap.
-static inline int grid_for(size_t n_items, int cap = 1 << 22) {
+constexpr int kPwGridCap = 1 << 22;
+int g_pw_grid_cap = kPwGridCap;     // rc_debug_set("pw_grid_cap", v): blocks per launch of every kernel in this file (0 restores the default); tests set it to a handful
+                                    // of blocks so that the grid-stride loops run at sizes a test can afford
+static inline int grid_for(size_t n_items) {
     size_t g = (n_items + kPwThreads - 1) / kPwThreads;
     if (g < 1) g = 1;
-    if (g > (size_t)cap) g = cap;
+    if (g > (size_t)g_pw_grid_cap) g = g_pw_grid_cap;
     return (int)g;
 }
 
@@ -661,6 +664,7 @@ int rc_gate_residual(const void* d_r, const float* d_gate, const void* d_x, void
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_gate_residual: bad dtype");
     RC_REQUIRE(batch >= 1 && n_pix >= 1 && c >= U && c % U == 0, "rc_gate_residual: c must be a multiple of 16 bytes");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_r) % 16 == 0 && reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && reinterpret_cast<uintptr_t>(d_y) % 16 == 0, "rc_gate_residual: 16-byte alignment");
     const size_t total = (size_t)batch * n_pix * (c / U);
     if (dtype == RC_F32)
         hipLaunchKernelGGL(gate_residual_kernel<float>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
@@ -680,6 +684,7 @@ int rc_film_apply(const void* d_x, const float* d_scale, const float* d_shift, v
     RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_film_apply: bad dtype");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(batch >= 1 && n_pix >= 1 && c >= U && c % U == 0, "rc_film_apply: c must be a multiple of 16 bytes");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && reinterpret_cast<uintptr_t>(d_y) % 16 == 0, "rc_film_apply: 16-byte alignment");
     const size_t total = (size_t)batch * n_pix * (c / U);
     if (dtype == RC_F32)
         hipLaunchKernelGGL(film_apply_kernel<float>, dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream), static_cast<const float*>(d_x),
@@ -929,7 +934,8 @@ int rc_dwt_forward(const void* d_x, void* d_y, const float* d_taps, int taps_uni
     RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_dwt_forward: bad dtype");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(batch >= 1 && H >= 2 && W >= 2 && H % 2 == 0 && W % 2 == 0, "rc_dwt_forward: H and W must be even");
-    RC_REQUIRE(c % U == 0, "rc_dwt_forward: channels must be a multiple of 16 bytes");
+    RC_REQUIRE(c >= U && c % U == 0, "rc_dwt_forward: channels must be a multiple of 16 bytes");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && reinterpret_cast<uintptr_t>(d_y) % 16 == 0, "rc_dwt_forward: 16-byte alignment");
     const size_t total = (size_t)batch * (H / 2) * (W / 2) * (c / U);
     if (dtype == RC_F32) {
         if (taps_uniform) hipLaunchKernelGGL((dwt_forward_kernel<float, true>), dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),
@@ -956,8 +962,9 @@ int rc_dwt_inverse(const void* d_x, void* d_y, const float* d_taps, int taps_uni
     RC_REQUIRE(d_x && d_y && d_taps, "rc_dwt_inverse: null pointer");
     RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16 || dtype == RC_F16, "rc_dwt_inverse: bad dtype");
     const int U = dtype == RC_F32 ? 4 : 8;
-    RC_REQUIRE(batch >= 1 && h >= 1 && w >= 1 && c4 % 4 == 0 && (c4 / 4) % U == 0,
+    RC_REQUIRE(batch >= 1 && h >= 1 && w >= 1 && c4 >= 4 * U && c4 % 4 == 0 && (c4 / 4) % U == 0,
                "rc_dwt_inverse: out channels (c4/4) must be a multiple of 16 bytes");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && reinterpret_cast<uintptr_t>(d_y) % 16 == 0, "rc_dwt_inverse: 16-byte alignment");
     const size_t total = (size_t)batch * h * w * (c4 / 4 / U);
     if (dtype == RC_F32) {
         if (taps_uniform) hipLaunchKernelGGL((dwt_inverse_kernel<float, true>), dim3(grid_for(total)), dim3(kPwThreads), 0, as_stream(stream),

@@ -238,14 +238,22 @@ def is_stride2(mod) -> bool:
             tuple(mod.dilation) == (1, 1) and mod.groups == 1 and getattr(mod, "padding_mode", "zeros") == "zeros")
 
 
+def _req_map(t: torch.Tensor, name: str, layout: str = "NHWC (B,H,W,C)") -> torch.Tensor:
+    """_req for an op that reads its sizes off the tensor's shape: anything but a 4-D map is refused here, before a launch is sized from it."""
+    t = _req(t, name)
+    if t.dim() != 4:
+        raise ValueError(f"{name}: a 4-D {layout} map expected, got shape {tuple(t.shape)}")
+    return t
+
+
 def subsample2(x: torch.Tensor) -> torch.Tensor:
     """x[:, ::2, ::2, :] of an NHWC map as a new dense tensor (rc_subsample2)."""
-    return _R.subsample2(_req(x, "subsample2 input"))
+    return _R.subsample2(_req_map(x, "subsample2 input"))
 
 
 def upsample_bilinear2(x: torch.Tensor) -> torch.Tensor:
     """nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True) on an NHWC map (upstream models/raw2bit.py:790-793)."""
-    return _R.upsample_bilinear2(_req(x, "upsample_bilinear2 input"))
+    return _R.upsample_bilinear2(_req_map(x, "upsample_bilinear2 input"))
 
 
 def sft_apply(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, identity: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -277,7 +285,7 @@ def pixel_shuffle2_nchw(x: torch.Tensor) -> torch.Tensor:
 
 def space_to_depth2(x: torch.Tensor) -> torch.Tensor:
     """(B,H,W,c) -> (B,ceil(H/2),ceil(W/2),4c), channel (2i+j)*c + k <- pixel (2y+i, 2x+j), zero beyond the edge."""
-    return _R.space_to_depth2(_req(x, "space_to_depth2 input"))
+    return _R.space_to_depth2(_req_map(x, "space_to_depth2 input"))
 
 
 def _stride2_view(mod) -> "_ConvView":
@@ -1073,7 +1081,7 @@ def film_apply(x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor) -> tor
 def channel_sums(x: torch.Tensor) -> torch.Tensor:
     """Per-channel partial sums (B, slots, C) fp32 of an NHWC map, in the layout rc_ca_gate folds (AdaptiveAvgPool2d(1) of a
     CALayer that is not fed by a conv emitting them, models/networks.py:268)."""
-    return _R.channel_sums(_req(x, "channel_sums input"))
+    return _R.channel_sums(_req_map(x, "channel_sums input"))
 
 
 def sigmoid_gate_add(a: torch.Tensor, b: torch.Tensor, identity: torch.Tensor) -> torch.Tensor:
@@ -1158,6 +1166,10 @@ def color_block(x: torch.Tensor, conv, prev_norm=None, prev_stats=None) -> torch
 
 
 def instance_stats(x: torch.Tensor, eps: float = 1e-5):
+    """Per (b, c) mean and 1/sqrt(biased variance + eps) of an fp32 NCHW map (rc_instance_stats)."""
+    x = _req_map(x, "instance_stats input", "fp32 NCHW (B,C,H,W)")
+    if x.dtype != torch.float32:
+        raise ValueError("instance_stats: fp32 NCHW expected")
     return _R.instance_stats(x, float(eps))
 
 
@@ -1171,7 +1183,11 @@ def instance_norm(x: torch.Tensor, norm) -> torch.Tensor:
 
 
 def color_head(x: torch.Tensor, conv) -> torch.Tensor:
+    """Conv1x1 + AdaptiveAvgPool2d(1) of an fp32 NCHW map -> (B, cout) (rc_color_head)."""
+    x = _req_map(x, "color_head input", "fp32 NCHW (B,C,H,W)")
     cout, cin = conv.weight.shape[0], conv.weight.shape[1]
+    if x.dtype != torch.float32 or x.shape[1] != cin:
+        raise ValueError("color_head: fp32 NCHW with the conv's input channels expected")
     return _R.color_head(x, f32_param(conv, "weight").reshape(cout, cin), f32_param(conv, "bias"))
 
 

@@ -549,11 +549,11 @@ def _taps_uniform(taps: Tensor) -> int:
     hit = _UNIFORM.get(key)
     if hit is None:
         w = taps.detach().float().reshape(-1, 4, 4)
-        hit = int(bool((w == w[:1]).all().item()))
-        if len(_UNIFORM) > 256:
+        hit = (int(bool((w == w[:1]).all().item())), taps)     # the entry keeps the tensor (a few hundred bytes) alive: while it is cached its address cannot be
+        if len(_UNIFORM) > 256:                                # handed to ANOTHER taps tensor, which would inherit this verdict (a freed temporary's did)
             _UNIFORM.clear()
         _UNIFORM[key] = hit
-    return hit
+    return hit[0]
 
 
 define("haar_dwt(Tensor x, Tensor taps, bool check_uniform) -> Tensor",
