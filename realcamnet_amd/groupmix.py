@@ -151,22 +151,20 @@ class Aggregator(nn.Module):
         (upstream groupmix.py:178 after :293, then :56-105)."""
         seg = 16
         dws = [self.agg1.conv1.weight, self.agg2.conv1.weight, self.agg3.conv1.weight, self.agg0.conv.conv1.weight]
-        c = ops._cache(self)
-        key = ops._key(*dws)
-        hit = c.get("toeplitz")
-        if hit is None or hit[0] != key:
+
+        def pack():
             with torch.no_grad():
                 w1, w2, w3, w0 = [p.detach().float().cpu() for p in dws]
-                hit = (key, torch.ops.realcam.gma_toeplitz_pack(ops.dw_taps(w1).to(x.device), ops.dw_taps(w2).to(x.device), ops.dw_taps(w3).to(x.device),
-                                                                ops.dw_taps(w0).reshape(9, 3, seg).permute(1, 0, 2).contiguous().to(x.device)))
-            c["toeplitz"] = hit
+                return torch.ops.realcam.gma_toeplitz_pack(ops.dw_taps(w1).to(x.device), ops.dw_taps(w2).to(x.device), ops.dw_taps(w3).to(x.device),
+                                                           ops.dw_taps(w0).reshape(9, 3, seg).permute(1, 0, 2).contiguous().to(x.device))
+        toeplitz = ops.derived(self, "toeplitz", dws, pack)
         scale, shift, pw, pwl = self._folded()
         ln = self.agg0.norm
         if abs(ln.eps - 1e-5) > 0:
             raise NotImplementedError("Aggregator: LayerNorm eps must be the default 1e-5")
         f32 = ops.f32_param
         return torch.ops.realcam.gma_qkv_aggregate(x, ops.packed_chain_natural(qkv_linear), f32(qkv_linear, "bias") if qkv_linear.bias is not None else None,
-                                                   f32(norm1, "weight"), f32(norm1, "bias"), float(norm1.eps), hit[1], pw, pwl,
+                                                   f32(norm1, "weight"), f32(norm1, "bias"), float(norm1.eps), toeplitz, pw, pwl,
                                                    scale, shift, f32(ln, "weight"), f32(ln, "bias"))
 
 
@@ -311,14 +309,10 @@ class GMA_Block(nn.Module):
         w = pre.weight
         if (ops.FUSE_GMA_ENTRY and a.dtype == torch.bfloat16 and tuple(w.shape) == (80, 192, 1, 1) and tuple(self.cpe.proj.weight.shape) == (80, 1, 3, 3) and
                 a.shape[0] * a.shape[1] * a.shape[2] > 0 and a.shape[1] * a.shape[2] * 192 * 2 < 2 ** 31):
-            c = ops._cache(self.cpe)
-            key = ops._key(self.cpe.proj.weight)
-            hit = c.get("toeplitz3")
-            if hit is None or hit[0] != key:
-                hit = (key, torch.ops.realcam.dw_toeplitz_pack(ops.dw_taps(self.cpe.proj.weight.detach().float()).to(a.device), 3))
-                c["toeplitz3"] = hit
+            dw = self.cpe.proj.weight
+            toeplitz = ops.derived(self.cpe, "toeplitz3", (dw,), lambda: torch.ops.realcam.dw_toeplitz_pack(ops.dw_taps(dw.detach().float()).to(a.device), 3))
             return torch.ops.realcam.gma_in_cpe(ops._req(a, "gma_in input"), ops.packed_chain_natural(pre), ops.f32_param(pre, "bias") if pre.bias is not None else None,
-                                                hit[1], ops.f32_param(self.cpe.proj, "bias") if self.cpe.proj.bias is not None else None)
+                                                toeplitz, ops.f32_param(self.cpe.proj, "bias") if self.cpe.proj.bias is not None else None)
         return self.cpe._nhwc(pre._nhwc(a))
 
     def _nhwc(self, a, post=None, pre=None):

@@ -12,6 +12,7 @@ from typing import Optional, Tuple
 import numpy as np
 import os
 import torch
+from torch._subclasses.fake_tensor import FakeTensor
 
 from . import _lib
 from . import torch_ops as _T  # noqa: F401  (registers torch.ops.realcam.*)
@@ -70,28 +71,39 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 # --------------------------------------------------------------------------------------------------
 # parameter caches (never part of the state_dict)
 # --------------------------------------------------------------------------------------------------
-def _key(*params) -> tuple:
-    """Cache key of derived parameters: storage address + version counter + dtype + device.  NOTE: an in-place edit through
-    `.data` (`w.data.copy_()`, EMA swaps) does not bump `_version`; call invalidate_caches(module) after such edits."""
-    from torch._subclasses.fake_tensor import FakeTensor
-    return tuple(((id(p) if isinstance(p, FakeTensor) else p.data_ptr()), p._version, p.dtype, str(p.device)) if p is not None else None
-                 for p in params)
+def derived(mod, slot, params, build, extra=None):
+    """The value `build()` derives from the tensors `params` (None entries allowed), kept on `mod` under the hashable name `slot`.  The kept value
+    is returned while every tensor is the same object (`id`: an entry holds its tensors, so neither their ids nor their addresses can pass to other
+    tensors while it lives) at the same address (a fake tensor has none) with the same `_version`, dtype and device, and `extra` -- whatever else the
+    value depends on -- compares equal.  `build` runs on a miss only and its result is stored as it is; one that raises leaves no entry.
+    NOTE: an in-place edit through `.data` (`w.data.copy_()`, EMA swaps) does not bump `_version`; call invalidate_caches(module) after such edits."""
+    cache = mod.__dict__.get("_rc_cache")
+    if cache is None:
+        cache = mod.__dict__["_rc_cache"] = {}             # never a registered buffer, never in the state_dict
+    key = (tuple(None if p is None else (id(p), 0 if isinstance(p, FakeTensor) else p.data_ptr(), p._version, p.dtype, str(p.device)) for p in params), extra)
+    hit = cache.get(slot)
+    if hit is not None and hit[0] == key:
+        return hit[2]
+    cache.pop(slot, None)
+    value = build()
+    cache[slot] = (key, tuple(params), value)
+    return value
+
+
+def drop_derived(mod, *slots) -> None:
+    """Forget the named derived values of `mod`; without names, all of them."""
+    if not slots:
+        mod.__dict__.pop("_rc_cache", None)
+    for slot in slots:
+        mod.__dict__.get("_rc_cache", {}).pop(slot, None)
 
 
 def invalidate_caches(module) -> None:
     """Drop every derived-parameter cache (packed MFMA weights, fp32 views, folded BatchNorm, CDF tables ...) below `module`.
     load_state_dict / optimizer steps / .to() are detected automatically; edits through `.data` are not."""
     for m in module.modules():
-        for k in ("_rc_cache", "_pk", "_eff", "_coder_tables", "_f32_masters", "_graphs", "_f32_verdict"):
+        for k in ("_rc_cache", "_f32_masters", "_f32_verdict", "_graphs"):
             m.__dict__.pop(k, None)
-
-
-def _cache(mod) -> dict:
-    c = mod.__dict__.get("_rc_cache")
-    if c is None:
-        c = {}
-        mod.__dict__["_rc_cache"] = c
-    return c
 
 
 def f32_param(mod, name: str) -> torch.Tensor:
@@ -99,14 +111,7 @@ def f32_param(mod, name: str) -> torch.Tensor:
     p = getattr(mod, name)
     if p.dtype == torch.float32 and p.is_contiguous():
         return _req(p.detach(), name)
-    c = _cache(mod)
-    k = ("f32", name)
-    hit = c.get(k)
-    key = _key(p)
-    if hit is None or hit[0] != key:
-        hit = (key, _req(p.detach(), name).float().contiguous())
-        c[k] = hit
-    return hit[1]
+    return derived(mod, ("f32", name), (p,), lambda: _req(p.detach(), name).float().contiguous())
 
 
 class PackedConv:
@@ -116,62 +121,51 @@ class PackedConv:
 def packed_conv(mod, act_dtype: torch.dtype, out_mode: int, cout_tile: int = 0) -> PackedConv:
     """MFMA-fragment-ordered copy of a conv's weights (realcam::conv_pack_weights), cached on the module (one copy per cout tile width in use)."""
     w, b = mod.weight, mod.bias
-    c = _cache(mod)
-    k = ("conv", act_dtype, out_mode, cout_tile)
-    key = (_key(w, b), _lib.knob(b"conv32"))      # the 32x32x16 layers' packed order depends on that knob (and on nothing else); mirrored host-side, no C call per conv
-    hit = c.get(k)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    if not w.is_cuda:
-        raise RuntimeError("conv weights are not on a HIP device; move the module with .cuda() first")
-    if w.dim() == 2:                       # nn.Linear over tokens == 1x1 convolution over NHWC pixels
-        cout, cin = w.shape
-        kh = kw = 1
-    else:
-        cout, cin, kh, kw = w.shape
-    if kh != kw or kh not in (1, 2, 3, 5):                 # 2: the {-1, 0}^2 window of a stride-2 3x3 conv over its space-to-depth map; 5: the folded tail
-        raise NotImplementedError(f"HIP conv supports 1x1 and 3x3 kernels, got {kh}x{kw}")
-    wp, bp = _R.conv_pack_weights(w.detach(), b.detach() if b is not None else None, act_dtype, out_mode, cout_tile)
-    pc = PackedConv()
-    pc.wpacked = wp
-    pc.bias = bp if b is not None else None
-    pc.cin, pc.cout, pc.ksize, pc.dtype, pc.out_mode = cin, cout, kh, _DT[act_dtype], out_mode
-    c[k] = (key, pc)
-    return pc
+
+    def pack():
+        if not w.is_cuda:
+            raise RuntimeError("conv weights are not on a HIP device; move the module with .cuda() first")
+        if w.dim() == 2:                       # nn.Linear over tokens == 1x1 convolution over NHWC pixels
+            cout, cin = w.shape
+            kh = kw = 1
+        else:
+            cout, cin, kh, kw = w.shape
+        if kh != kw or kh not in (1, 2, 3, 5):                 # 2: the {-1, 0}^2 window of a stride-2 3x3 conv over its space-to-depth map; 5: the folded tail
+            raise NotImplementedError(f"HIP conv supports 1x1 and 3x3 kernels, got {kh}x{kw}")
+        wp, bp = _R.conv_pack_weights(w.detach(), b.detach() if b is not None else None, act_dtype, out_mode, cout_tile)
+        pc = PackedConv()
+        pc.wpacked = wp
+        pc.bias = bp if b is not None else None
+        pc.cin, pc.cout, pc.ksize, pc.dtype, pc.out_mode = cin, cout, kh, _DT[act_dtype], out_mode
+        return pc
+    # the 32x32x16 layers' packed order depends on the conv32 knob (and on nothing else); mirrored host-side, no C call per conv
+    return derived(mod, ("conv", act_dtype, out_mode, cout_tile), (w, b), pack, _lib.knob(b"conv32"))
 
 
 def packed_chain(mod):
     """(packed bf16 MFMA fragments, packed fp32 bias) of an nn.Linear / 1x1 conv for the register-resident layer chains of
     csrc/gma_fused.hip (realcam::chain_pack_weights), cached on the module."""
     w, b = mod.weight, mod.bias
-    c = _cache(mod)
-    key = _key(w, b)
-    hit = c.get("chain")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    if not w.is_cuda:
-        raise RuntimeError("weights are not on a HIP device; move the module with .cuda() first")
-    if w.dim() == 4 and tuple(w.shape[2:]) != (1, 1):
-        raise NotImplementedError("layer chains take Linear / 1x1 weights")
-    pair = _R.chain_pack_weights(w.detach().reshape(w.shape[0], w.shape[1]), b.detach() if b is not None else None)
-    c["chain"] = (key, pair)
-    return pair
+
+    def pack():
+        if not w.is_cuda:
+            raise RuntimeError("weights are not on a HIP device; move the module with .cuda() first")
+        if w.dim() == 4 and tuple(w.shape[2:]) != (1, 1):
+            raise NotImplementedError("layer chains take Linear / 1x1 weights")
+        return _R.chain_pack_weights(w.detach().reshape(w.shape[0], w.shape[1]), b.detach() if b is not None else None)
+    return derived(mod, "chain", (w, b), pack)
 
 
 def packed_chain_natural(mod):
     """bf16 MFMA A fragments of an nn.Linear / 1x1 conv with the output rows in NATURAL channel order (16-row tile m = channels 16 m ..), for
     kernels that consume the accumulators by 16-channel segment (realcam::gma_qkv_aggregate); cached on the module."""
     w = mod.weight
-    c = _cache(mod)
-    key = _key(w)
-    hit = c.get("chain_natural")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    if not w.is_cuda:
-        raise RuntimeError("weights are not on a HIP device; move the module with .cuda() first")
-    packed = _R.chain_pack_weights_natural(w.detach().reshape(w.shape[0], w.shape[1]))
-    c["chain_natural"] = (key, packed)
-    return packed
+
+    def pack():
+        if not w.is_cuda:
+            raise RuntimeError("weights are not on a HIP device; move the module with .cuda() first")
+        return _R.chain_pack_weights_natural(w.detach().reshape(w.shape[0], w.shape[1]))
+    return derived(mod, "chain_natural", (w,), pack)
 
 
 # The per-token stages of GMA_Block (LayerNorm1 + qkv; attention read-out + proj + LayerNorm2 + MLP [+ the net's output conv]) as
@@ -191,38 +185,30 @@ class _ConvView:
 def split_conv_views(mod, sizes):
     """Views of a convolution's output channels [0, s0), [s0, s0 + s1), ...: `torch.split(conv(x), sizes, dim=1)` (upstream models/tcm.py:261)
     as separate convolutions of the same input -- the input is read once more, the full-width result and its slice copies never exist."""
-    cache = _cache(mod)
-    key = _key(mod.weight, mod.bias)
-    hit = cache.get("split_views")
-    if hit is None or hit[0] != (key, tuple(sizes)):
+    def split():
         views, c0 = [], 0
         for n in sizes:
             views.append(_ConvView(mod.weight.detach()[c0:c0 + n], mod.bias.detach()[c0:c0 + n] if mod.bias is not None else None))
             c0 += n
         if c0 != mod.weight.shape[0]:
             raise ValueError("split_conv_views: sizes do not add up to the convolution's output channels")
-        hit = ((key, tuple(sizes)), views)
-        cache["split_views"] = hit
-    return hit[1]
+        return views
+    return derived(mod, "split_views", (mod.weight, mod.bias), split, tuple(sizes))
 
 
 def split_conv_input_views(mod, sizes):
     """Views of a convolution's INPUT channels [0, s0), [s0, s0 + s1), ...: conv(torch.cat(parts, dim=1)) = sum_i conv_i(parts[i]) (only the
     first view carries the bias).  Lets `intro(torch.cat([raw, coord], 1))` (upstream models/LiteISP.py:1497) run without the 6-channel
     concatenated map -- whose 8-byte coord pixels are no whole 16-byte vectors for rc_channel_copy anyway."""
-    cache = _cache(mod)
-    key = _key(mod.weight, mod.bias)
-    hit = cache.get("split_in_views")
-    if hit is None or hit[0] != (key, tuple(sizes)):
+    def split():
         views, c0 = [], 0
         for i, n in enumerate(sizes):
             views.append(_ConvView(mod.weight.detach()[:, c0:c0 + n].contiguous(), mod.bias.detach() if (mod.bias is not None and i == 0) else None))
             c0 += n
         if c0 != mod.weight.shape[1]:
             raise ValueError("split_conv_input_views: sizes do not add up to the convolution's input channels")
-        hit = ((key, tuple(sizes)), views)
-        cache["split_in_views"] = hit
-    return hit[1]
+        return views
+    return derived(mod, "split_in_views", (mod.weight, mod.bias), split, tuple(sizes))
 
 
 def is_down2x2(mod) -> bool:
@@ -291,10 +277,7 @@ def space_to_depth2(x: torch.Tensor) -> torch.Tensor:
 def _stride2_view(mod) -> "_ConvView":
     """Weights of a kxk stride-2 conv re-indexed for the space-to-depth map: input pixel offset d in {-1, 0, +1} of the strided
     conv is (phase 1, offset -1), (phase 0, offset 0), (phase 1, offset 0) of the half-resolution map."""
-    cache = _cache(mod)
-    key = _key(mod.weight, mod.bias)
-    hit = cache.get("stride2_s2d")
-    if hit is None or hit[0] != key:
+    def reindex():
         w = mod.weight.detach().float().cpu()
         cout, c, k, _ = w.shape
         # bf16: the 3x3 case only touches map offsets {-1, 0}^2 -- a 2x2 window (rc_conv2d ksize 2): 16 (tap, phase) blocks of which 9 are
@@ -310,10 +293,8 @@ def _stride2_view(mod) -> "_ConvView":
                     w3[:, ph * c:(ph + 1) * c, oy + 1, ox + 1] = w[:, :, dy + 1, dx + 1]
         else:
             w3[:, :c, 0, 0] = w[:, :, 0, 0]
-        view = _ConvView(w3.to(mod.weight.device, mod.weight.dtype), mod.bias.detach() if mod.bias is not None else None)
-        hit = (key, view)
-        cache["stride2_s2d"] = hit
-    return hit[1]
+        return _ConvView(w3.to(mod.weight.device, mod.weight.dtype), mod.bias.detach() if mod.bias is not None else None)
+    return derived(mod, "stride2_s2d", (mod.weight, mod.bias), reindex)
 
 
 # stride-2 3x3 convolutions with 64 | channels read their input directly (no rc_space_to_depth2 pass); False: always via the map
@@ -329,10 +310,7 @@ def conv_stride2(x: torch.Tensor, mod, s2d: Optional[torch.Tensor] = None, **fus
         raise NotImplementedError("conv_stride2: only an activation can be fused")
     unit = 16 // x.element_size()
     if mod.kernel_size[0] == 1 and x.shape[-1] % unit == 0:
-        cache = _cache(mod)
-        view = cache.get("stride2_view")
-        if view is None or view.weight is not mod.weight or view.bias is not mod.bias:
-            view = cache["stride2_view"] = _ConvView(mod.weight, mod.bias)
+        view = derived(mod, "stride2_view", (mod.weight, mod.bias), lambda: _ConvView(mod.weight, mod.bias))
         return conv2d(subsample2(x), view, **fuse)
     view = _stride2_view(mod)
     if FOLD_STRIDE2 and s2d is None and view.weight.shape[-1] == 2 and x.shape[-1] % 64 == 0:
@@ -403,17 +381,12 @@ def conv2x2s2(x: torch.Tensor, mod, **fuse):
     cout, cin = mod.weight.shape[:2]
     if cin != c:
         raise ValueError(f"conv expects {cin} input channels, got {c}")
-    cache = _cache(mod)
-    key = _key(mod.weight, mod.bias)
-    hit = cache.get("down2x2")
-    if hit is None or hit[0] != key:
+    def build():
         taps = torch.zeros((4 * c, 1, 2, 2), dtype=torch.float32)
         for k in range(4):
             taps[k::4, 0, k >> 1, k & 1] = 1.0
-        view = _ConvView(mod.weight.detach().reshape(cout, 4 * c, 1, 1), mod.bias.detach() if mod.bias is not None else None)
-        hit = (key, taps.to(x.device), view)
-        cache["down2x2"] = hit
-    _, taps, view = hit
+        return taps.to(x.device), _ConvView(mod.weight.detach().reshape(cout, 4 * c, 1, 1), mod.bias.detach() if mod.bias is not None else None)
+    taps, view = derived(mod, "down2x2", (mod.weight, mod.bias), build)
     return conv2d(_R.haar_dwt(x, taps, False), view, **fuse)     # one-hot 2x2 taps, the same for every channel
 
 
@@ -624,20 +597,16 @@ def winograd_ok(x: torch.Tensor, mod, *, act=None, gate=None, skip=None, mul_plu
 def packed_wino(mod, act_dtype: torch.dtype) -> PackedConv:
     """U = G g G^T of a 3x3 conv in the Winograd kernel's fragment order (realcam::wino_pack_weights) + its bias in natural order, cached on the module."""
     w, b = mod.weight, mod.bias
-    c = _cache(mod)
-    k = ("wino", act_dtype)
-    key = _key(w, b)
-    hit = c.get(k)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    if not w.is_cuda:
-        raise RuntimeError("conv weights are not on a HIP device; move the module with .cuda() first")
-    pc = PackedConv()
-    pc.wpacked = _R.wino_pack_weights(w.detach(), act_dtype)
-    pc.bias = b.detach().float().contiguous() if b is not None else None
-    pc.cout, pc.cin, pc.ksize, pc.dtype, pc.out_mode = w.shape[0], w.shape[1], 3, _DT[act_dtype], RC_OUT_NHWC
-    c[k] = (key, pc)
-    return pc
+
+    def pack():
+        if not w.is_cuda:
+            raise RuntimeError("conv weights are not on a HIP device; move the module with .cuda() first")
+        pc = PackedConv()
+        pc.wpacked = _R.wino_pack_weights(w.detach(), act_dtype)
+        pc.bias = b.detach().float().contiguous() if b is not None else None
+        pc.cout, pc.cin, pc.ksize, pc.dtype, pc.out_mode = w.shape[0], w.shape[1], 3, _DT[act_dtype], RC_OUT_NHWC
+        return pc
+    return derived(mod, ("wino", act_dtype), (w, b), pack)
 
 
 def conv2d(x: torch.Tensor, mod, *, act: Optional[str] = None, slope: float = 0.0,
@@ -723,16 +692,13 @@ def conv_dwt_ok(x: torch.Tensor, conv, dwt, act: Optional[str] = None, slope: fl
     w = getattr(dwt, "weight", None)
     if w is None or tuple(w.shape) != (4 * cout, 1, 2, 2):
         return False
-    from torch._subclasses.fake_tensor import FakeTensor
     if isinstance(w, FakeTensor):                 # shape tracing: values are not there to look at; a DWTForward is built with these taps and frozen
         return True
-    c = _cache(dwt)
-    hit = c.get("haar_ok")
-    if hit is None or hit[0] != _key(w):
+
+    def taps_are_haar():
         want = torch.tensor(_HAAR_TAPS, dtype=torch.float32).reshape(4, 1, 2, 2).repeat(cout, 1, 1, 1)
-        hit = (_key(w), bool(torch.equal(w.detach().float().cpu(), want)))
-        c["haar_ok"] = hit
-    return hit[1]
+        return bool(torch.equal(w.detach().float().cpu(), want))
+    return derived(dwt, "haar_ok", (w,), taps_are_haar)
 
 
 FUSE_SHUFFLE_STORE = True    # narrow subpel tails (conv -> PixelShuffle(2), 3 output channels: the codecs' x_hat): shuffle + NCHW in the conv's store
@@ -756,10 +722,7 @@ def tail_fold_ok(x: torch.Tensor, conv1, conv2) -> bool:
 
 
 def _folded_tail(conv1, conv2) -> "_ConvView":
-    cache = _cache(conv2)
-    key = (_key(conv1.weight, conv1.bias), _key(conv2.weight, conv2.bias))
-    hit = cache.get("tail_fold")
-    if hit is None or hit[0] != key:
+    def fold():
         det = lambda t: None if t is None else t.detach()
         wc, bc = _R.tail_fold_weights(conv1.weight.detach(), det(conv1.bias), conv2.weight.detach(), det(conv2.bias))
         # the two side strips (H x 2 pixels) run TRANSPOSED (2 x H: a 2-pixel-wide image wastes 15/16 of every 8 x 32 tile): the same two convolutions
@@ -768,8 +731,8 @@ def _folded_tail(conv1, conv2) -> "_ConvView":
         perm = (torch.arange(c, device=conv1.weight.device)[:, None] * 4 + torch.tensor([0, 2, 1, 3], device=conv1.weight.device)[None, :]).reshape(-1)
         v1t = _ConvView(conv1.weight.detach().transpose(2, 3)[perm].contiguous(), None if conv1.bias is None else conv1.bias.detach()[perm].contiguous())
         v2t = _ConvView(conv2.weight.detach().transpose(2, 3).contiguous(), det(conv2.bias))
-        hit = cache["tail_fold"] = (key, _ConvView(wc, bc), v1t, v2t)
-    return hit[1:]
+        return _ConvView(wc, bc), v1t, v2t
+    return derived(conv2, "tail_fold", (conv1.weight, conv1.bias, conv2.weight, conv2.bias), fold)
 
 
 def tail_fold(x: torch.Tensor, conv1, conv2, crop_hw: Optional[Tuple[int, int]] = None, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
@@ -874,7 +837,6 @@ def fork_join(side_fn, main_fn, inputs):
     Under HIP-graph capture the fork becomes two branches of the graph (the side stream joins the capture through wait_stream); the allocator's
     record_stream bookkeeping is skipped there: a capture's private pool is not reused across streams before the join, and every side tensor is
     consumed on the main stream only after it."""
-    from torch._subclasses.fake_tensor import FakeTensor
     probe = inputs[0]
     if not BRANCH_STREAMS or not probe.is_cuda or isinstance(probe, FakeTensor):
         return side_fn(), main_fn()
@@ -991,16 +953,12 @@ def lsc_chain(lsc, coord: torch.Tensor, head=None, raw: Optional[torch.Tensor] =
         raw = _req(raw, "raw")
     coord = _req(coord, "coord")
     params = [p for m in convs for p in (m.weight, m.bias)] + ([head.weight, head.bias] if head is not None else [])
-    cache = _cache(lsc)
-    k = ("lsc", id(head))
-    key = _key(*params)
-    hit = cache.get(k)
-    if hit is None or hit[0] != key:
+    def pack():
         det = lambda t: None if t is None else t.detach()
-        blob = _R.lsc_pack(det(convs[0].weight), det(convs[0].bias), [det(m.weight) for m in convs[1:]], [det(m.bias) for m in convs[1:]],
+        return _R.lsc_pack(det(convs[0].weight), det(convs[0].bias), [det(m.weight) for m in convs[1:]], [det(m.bias) for m in convs[1:]],
                            det(head.weight) if head is not None else None, det(head.bias) if head is not None else None)
-        hit = cache[k] = (key, blob)
-    return _R.lsc_chain(coord, hit[1], int(c), len(convs) - 1, slopes.pop(), raw if head is not None else None)
+    blob = derived(lsc, ("lsc", id(head)), params, pack)
+    return _R.lsc_chain(coord, blob, int(c), len(convs) - 1, slopes.pop(), raw if head is not None else None)
 
 
 def ca_gate(sums: torch.Tensor, hw: int, ca) -> torch.Tensor:
@@ -1111,7 +1069,6 @@ _ONES = {}
 
 def _const(value: float, shape, like: torch.Tensor) -> torch.Tensor:
     """A cached constant fp32 device tensor (never cached for fake tensors: they belong to their FakeTensorMode)."""
-    from torch._subclasses.fake_tensor import FakeTensor
     if isinstance(like, FakeTensor):
         return torch.full(shape, value, dtype=torch.float32, device=like.device)
     key = (value, tuple(shape), str(like.device))
@@ -1232,19 +1189,14 @@ def prof_collect():
 def host_cached(mod, key: str, params, build):
     """Small derived fp32 tensors (folded BatchNorm, tap-major depth-wise weights ...) built on the host from
     module parameters once per parameter version and kept on the parameters' device."""
-    c = _cache(mod)
-    k = ("derived", key)
-    ver = _key(*params)
-    hit = c.get(k)
-    if hit is None or hit[0] != ver:
+    def on_host():
         dev = params[0].device
         with torch.no_grad():
             vals = build(*[p.detach().float().cpu() for p in params])
         if isinstance(vals, torch.Tensor):
             vals = (vals,)
-        hit = (ver, tuple(v.contiguous().to(dev) for v in vals))
-        c[k] = hit
-    return hit[1]
+        return tuple(v.contiguous().to(dev) for v in vals)
+    return derived(mod, ("derived", key), params, on_host)
 
 
 def dw_taps(weight: torch.Tensor, pad_to: Optional[int] = None) -> torch.Tensor:

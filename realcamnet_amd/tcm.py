@@ -308,16 +308,12 @@ class GDN(nn.Module):
         self.gamma = nn.Parameter(self.gamma_reparam.init(float(gamma_init) * torch.eye(in_channels)))
 
     def _effective(self):
-        key = ops._key(self.beta, self.gamma)
-        hit = getattr(self, "_eff", None)
-        if hit is None or hit[0] != key:
+        def view():
             with torch.no_grad():
                 c = self.beta.numel()
-                view = ops._ConvView(self.gamma_reparam(self.gamma.float()).reshape(c, c, 1, 1).contiguous(),
+                return ops._ConvView(self.gamma_reparam(self.gamma.float()).reshape(c, c, 1, 1).contiguous(),
                                      self.beta_reparam(self.beta.float()).contiguous())
-            hit = (key, view)
-            object.__setattr__(self, "_eff", hit)
-        return hit[1]
+        return ops.derived(self, "gdn_effective", (self.beta, self.gamma), view)
 
     def _nhwc(self, a, identity=None):
         if ops.FUSE_MLP and a.dtype == torch.bfloat16 and a.shape[-1] in (64, 128):        # one per-token launch (rc_gdn_chain)
@@ -393,17 +389,12 @@ def _register_coder_buffers(mod, likelihood_bound: float) -> None:
 def _set_coder_buffers(mod, offset, cdf, length) -> None:
     dev = mod._offset.device
     mod._offset, mod._quantized_cdf, mod._cdf_length = offset.to(dev), cdf.to(dev), length.to(dev)
-    mod.__dict__.pop("_coder_tables", None)
+    ops.drop_derived(mod, "coder_tables")
 
 
 def _coder_tables(mod) -> "bitstream.Tables":
     dev = next(iter(mod.parameters()), mod._offset).device if any(True for _ in mod.parameters()) else mod._offset.device
-    key = (mod._quantized_cdf.data_ptr(), mod._quantized_cdf._version, str(dev))
-    hit = mod.__dict__.get("_coder_tables")
-    if hit is None or hit[0] != key:
-        hit = (key, bitstream.Tables(mod._quantized_cdf, mod._cdf_length, mod._offset, dev))
-        mod.__dict__["_coder_tables"] = hit
-    return hit[1]
+    return ops.derived(mod, "coder_tables", (mod._quantized_cdf,), lambda: bitstream.Tables(mod._quantized_cdf, mod._cdf_length, mod._offset, dev), str(dev))
 
 
 def _resize_coder_buffers(mod, prefix: str, names, state_dict) -> None:
@@ -416,7 +407,7 @@ def _resize_coder_buffers(mod, prefix: str, names, state_dict) -> None:
             new = state_dict[key]
             if cur.numel() == 0 or cur.shape != new.shape:
                 setattr(mod, name, torch.empty(new.shape, dtype=cur.dtype, device=cur.device))
-    mod.__dict__.pop("_coder_tables", None)
+    ops.drop_derived(mod, "coder_tables")
 
 
 import inspect as _inspect
@@ -482,7 +473,7 @@ class _Fp32Masters:
             live = getattr(self, n)
             if live.dtype != torch.float32 and m.shape == live.shape:
                 verdicts[n] = ((live.data_ptr(), live._version, live.dtype, str(live.device)), True)
-        self.__dict__.pop("_coder_tables", None)
+        ops.drop_derived(self, "coder_tables")
         return out
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
@@ -571,13 +562,11 @@ class EntropyBottleneck(_Fp32Masters, nn.Module):
     def _packed(self):
         ps = [getattr(self, f"_matrix{i}") for i in range(5)] + [getattr(self, f"_bias{i}") for i in range(5)] + \
              [getattr(self, f"_factor{i}") for i in range(4)] + [self.quantiles]
-        from torch._subclasses.fake_tensor import FakeTensor
-        if isinstance(self.quantiles, FakeTensor):                          # shape tracing: nothing to pack on the host
+        if isinstance(self.quantiles, ops.FakeTensor):                      # shape tracing: nothing to pack on the host
             q = self.quantiles
             return q.new_empty((self.channels, 58), dtype=torch.float32), q.new_empty((self.channels,), dtype=torch.float32)
-        key = tuple((p._version, p.data_ptr()) for p in ps)
-        hit = getattr(self, "_pk", None)
-        if hit is None or hit[0] != key:
+
+        def pack():
             import numpy as np
             g = lambda n: getattr(self, n).detach().float().cpu().numpy().astype(np.float64)
             softplus = lambda a: np.logaddexp(a, 0.0)
@@ -589,10 +578,8 @@ class EntropyBottleneck(_Fp32Masters, nn.Module):
                     cols.append(np.tanh(g(f"_factor{i}")).reshape(self.channels, -1))
             packed = np.concatenate(cols, axis=1).astype(np.float32)
             assert packed.shape == (self.channels, 58)
-            dev = self.quantiles.device
-            hit = (key, torch.from_numpy(packed).to(dev), self.quantiles.detach()[:, 0, 1].float().contiguous())
-            object.__setattr__(self, "_pk", hit)
-        return hit[1], hit[2]
+            return torch.from_numpy(packed).to(self.quantiles.device), self.quantiles.detach()[:, 0, 1].float().contiguous()
+        return ops.derived(self, "bottleneck_packed", ps, pack)
 
     def _nhwc(self, z):
         """(z_hat, likelihood fp32) of an NHWC latent."""
