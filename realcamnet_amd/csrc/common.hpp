@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "../../include/realcam_hip.h"
+#include "per_device.hpp"
 
 namespace rc {
 
@@ -173,21 +174,43 @@ __device__ __forceinline__ float apply_act(float v, int act, float slope) {
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // Function attributes (dynamic-LDS limit) and device properties are PER DEVICE in HIP: per-process `static bool` flags would leave a
-// second GPU touched by the same process without them.  Small per-device tables instead (index = hipGetDevice(), < 64).
+// second GPU touched by the same process without them.  Small per-device tables of atomics instead (index = hipGetDevice(), < 64).
 inline int current_device() {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 0;
     return dev;
 }
-struct PerDeviceFlag {
-    bool done[64] = {};
-    bool test_and_set() { const int d = current_device(); const bool was = done[d]; done[d] = true; return was; }
-};
 inline int device_cu_count() {
-    static int cus[64] = {};
+    static std::atomic<int> cus[kMaxDevices] = {};
     const int d = current_device();
-    if (!cus[d]) (void)hipDeviceGetAttribute(&cus[d], hipDeviceAttributeMultiprocessorCount, d);
-    return cus[d] > 0 ? cus[d] : 256;
+    int n = cus[d].load(std::memory_order_relaxed);
+    if (n <= 0 && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && n > 0) cus[d].store(n, std::memory_order_relaxed);
+    return n > 0 ? n : 256;
+}
+
+// Grid of a persistent kernel: one block per CU, no more blocks than work items, rounded up to a multiple of 8 (the XCDs).
+inline int persistent_grid(int num_cus, int n_items) { return ((num_cus < n_items ? num_cus : n_items) + 7) / 8 * 8; }
+
+// THE way to launch a kernel that needs more than the default dynamic-LDS limit.  allow_lds<&kernel>(bytes) raises the kernel's limit on the
+// current device unless it already stands at `bytes` or more (one table per kernel: per_device.hpp); launch_lds<&kernel>(...) does that for
+// the launch's own size, launches, and returns the launch's status.  A site that asks for more than its launches use (one limit for every
+// LDS size the kernel runs with) calls allow_lds with that limit first.
+template <auto Kernel>
+int allow_lds(int limit_bytes) {
+    static PerDeviceLimit table;
+    hipError_t err = hipSuccess;
+    const bool ok = table.ensure(current_device(), limit_bytes, [&](int bytes) {
+        err = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        return err == hipSuccess;
+    });
+    return ok ? RC_OK : fail(RC_ERR_HIP, std::string("hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize, ") + std::to_string(limit_bytes) + "): " + hipGetErrorString(err));
+}
+template <auto Kernel, class... A>
+int launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, const A&... args) {
+    if (int e = allow_lds<Kernel>(lds_bytes)) return e;
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, args...);
+    RC_HIP_CHECK(hipGetLastError());
+    return RC_OK;
 }
 
 // exact-erf GELU, 0.5 v (1 + erf(v / sqrt 2)) (nn.GELU() of groupmix.Mlp / tcm.Block), with erf as ONE odd polynomial: w = clamp(v, +-5), t = 2 w^2 / 25 - 1 in [-1, 1],

@@ -506,31 +506,20 @@ int rc_color_block(const void* d_x, int x_dtype, float* d_y, int batch, int cin,
     const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
     const size_t lds = ((size_t)cin + 1) * CB_PX * sizeof(float);
     RC_REQUIRE(lds <= 144 * 1024, "rc_color_block: cin too large");       // cin <= 575 (the LFM colour branch reaches 256)
-    static PerDeviceFlag attr;
-    if (!attr.test_and_set()) {
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&color_block_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&color_block_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&color_block_kernel<f16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-    }
     const size_t g = (size_t)batch * (((size_t)ho * wo + CB_PX - 1) / CB_PX);
     RC_REQUIRE(g < (1ull << 31), "rc_color_block: too many tiles");
     // cout slices (gridDim.y): enough blocks for the chip on the small late maps, never fewer than 4 outputs per thread and slice (same sums, same order: bit-identical)
     int slices = 1;
     while (g * slices < 2 * (size_t)device_cu_count() && cout / (2 * slices) >= 16) slices *= 2;
-    if (x_dtype == RC_F32)
-        hipLaunchKernelGGL(color_block_kernel<float>, dim3((unsigned)g, (unsigned)slices), dim3(256), lds, as_stream(stream),
-                           static_cast<const float*>(d_x), d_y, batch, cin, cout, h, w, ho, wo, d_w, d_b,
-                           d_in_mean, d_in_rstd, d_in_gamma, d_in_beta);
-    else if (x_dtype == RC_BF16)
-        hipLaunchKernelGGL(color_block_kernel<bf16_t>, dim3((unsigned)g, (unsigned)slices), dim3(256), lds, as_stream(stream),
-                           static_cast<const bf16_t*>(d_x), d_y, batch, cin, cout, h, w, ho, wo, d_w, d_b,
-                           d_in_mean, d_in_rstd, d_in_gamma, d_in_beta);
-    else
-        hipLaunchKernelGGL(color_block_kernel<f16_t>, dim3((unsigned)g, (unsigned)slices), dim3(256), lds, as_stream(stream),
-                           static_cast<const f16_t*>(d_x), d_y, batch, cin, cout, h, w, ho, wo, d_w, d_b,
-                           d_in_mean, d_in_rstd, d_in_gamma, d_in_beta);
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    auto launch = [&](auto tag) -> int {                  // one limit (the bound on lds above) for every cin
+        using T = decltype(tag);
+        if (int e_ = allow_lds<&color_block_kernel<T>>(144 * 1024)) return e_;
+        return launch_lds<&color_block_kernel<T>>(dim3((unsigned)g, (unsigned)slices), dim3(256), (int)lds, as_stream(stream),
+                                                  static_cast<const T*>(d_x), d_y, batch, cin, cout, h, w, ho, wo, d_w, d_b,
+                                                  d_in_mean, d_in_rstd, d_in_gamma, d_in_beta);
+    };
+    if (x_dtype == RC_F32) return launch(float{});
+    return x_dtype == RC_BF16 ? launch(bf16_t{}) : launch(f16_t{});
 }
 
 int rc_instance_stats(const float* d_x, float* d_mean, float* d_rstd, int batch, int c, int hw, float eps, void* stream) {

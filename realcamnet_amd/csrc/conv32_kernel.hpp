@@ -578,29 +578,13 @@ template <class K, bool GATED>
 int launch_conv32_g(const ConvArgs& a, hipStream_t stream) {
     const int tiles_y = (a.H + K::TH - 1) / K::TH;
     const int n_items = a.tiles_x * tiles_y * a.batch * (a.n_chunks > 1 ? a.n_ct : 1);
-    int grid = a.num_cus;
-    if (grid > n_items) grid = n_items;
-    grid = (grid + 7) / 8 * 8;
+    const dim3 grid((unsigned)persistent_grid(a.num_cus, n_items));
     // single-chunk layers (the tail) end every stage with an epilogue: its stores are issued under the next stage's MFMAs
     constexpr bool CAN_DEFER = K::NPEND <= K::SA && K::CK == 48;
-    bool deferred = false;
     if constexpr (CAN_DEFER) {
-        if ((a.dbg_flags & 8) == 0 && a.n_chunks == 1) {
-            static PerDeviceFlag attr_set;
-            if (!attr_set.test_and_set())
-                RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv32_kernel<K, GATED, true>), hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES));
-            hipLaunchKernelGGL((conv32_kernel<K, GATED, true>), dim3((unsigned)grid), dim3(K::THREADS), K::LDS_BYTES, stream, a);
-            deferred = true;
-        }
+        if ((a.dbg_flags & 8) == 0 && a.n_chunks == 1) return launch_lds<&conv32_kernel<K, GATED, true>>(grid, dim3(K::THREADS), K::LDS_BYTES, stream, a);
     }
-    if (!deferred) {
-        static PerDeviceFlag attr_set;
-        if (!attr_set.test_and_set())
-            RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv32_kernel<K, GATED, false>), hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES));
-        hipLaunchKernelGGL((conv32_kernel<K, GATED, false>), dim3((unsigned)grid), dim3(K::THREADS), K::LDS_BYTES, stream, a);
-    }
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    return launch_lds<&conv32_kernel<K, GATED, false>>(grid, dim3(K::THREADS), K::LDS_BYTES, stream, a);
 }
 
 template <class K>
@@ -822,15 +806,7 @@ template <class K, bool GATED>
 int launch_conv32s_g(const ConvArgs& a, hipStream_t stream) {
     const int tiles_y = (a.H + K::TH - 1) / K::TH;
     const int n_items = a.tiles_x * tiles_y * a.batch * a.n_ct;
-    int grid = a.num_cus;
-    if (grid > n_items) grid = n_items;
-    grid = (grid + 7) / 8 * 8;
-    static PerDeviceFlag attr_set;
-    if (!attr_set.test_and_set())
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv32s_kernel<K, GATED>), hipFuncAttributeMaxDynamicSharedMemorySize, K::LDS_BYTES));
-    hipLaunchKernelGGL((conv32s_kernel<K, GATED>), dim3((unsigned)grid), dim3(K::THREADS), K::LDS_BYTES, stream, a);
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    return launch_lds<&conv32s_kernel<K, GATED>>(dim3((unsigned)persistent_grid(a.num_cus, n_items)), dim3(K::THREADS), K::LDS_BYTES, stream, a);
 }
 
 template <class K>

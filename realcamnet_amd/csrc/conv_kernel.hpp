@@ -2669,13 +2669,7 @@ constexpr int persist_lds_bytes() { return persist_lds_bytes_c<Cfg>(); }
 
 template <class Cfg, bool FAST>
 int launch_wst(const ConvArgs& a, int grid, hipStream_t stream) {
-    constexpr int WST_LDS = wst_lds_bytes<Cfg>();
-    static PerDeviceFlag attr_thin;                      // function attributes are per device (common.hpp)
-    if (!attr_thin.test_and_set())
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_wst_kernel<Cfg, FAST>), hipFuncAttributeMaxDynamicSharedMemorySize, WST_LDS));
-    hipLaunchKernelGGL((conv_mfma_wst_kernel<Cfg, FAST>), dim3((unsigned)grid), dim3(kWsmThreads), WST_LDS, stream, a);
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    return launch_lds<&conv_mfma_wst_kernel<Cfg, FAST>>(dim3((unsigned)grid), dim3(kWsmThreads), wst_lds_bytes<Cfg>(), stream, a);
 }
 
 template <class Cfg, bool GATED, bool FAST>
@@ -2708,18 +2702,9 @@ int launch_conv_g(const ConvArgs& a, hipStream_t stream) {
                 if (report(0, legacy_slots)) return RC_OK;
                 constexpr int A_LDS = auto_lds_bytes<Cfg>();
                 const int n_items = a.tiles_x * ((a.H + kWsmTH - 1) / kWsmTH) * a.batch;
-                int grid = a.num_cus;
-                if (grid > n_items) grid = n_items;
-                grid = (grid + 7) / 8 * 8;
-                static PerDeviceFlag attr_set;
-                if (!attr_set.test_and_set()) {
-                    RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_auto_kernel<Cfg, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS));
-                    RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_auto_kernel<Cfg, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS));
-                }
-                if (a.ep_key == DD::EP_RES) hipLaunchKernelGGL((conv_mfma_auto_kernel<Cfg, 2>), dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, a);      // residual prefetched
-                else hipLaunchKernelGGL((conv_mfma_auto_kernel<Cfg, 0>), dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, a);
-                RC_HIP_CHECK(hipGetLastError());
-                return RC_OK;
+                const dim3 grid((unsigned)persistent_grid(a.num_cus, n_items));
+                if (a.ep_key == DD::EP_RES) return launch_lds<&conv_mfma_auto_kernel<Cfg, 2>>(grid, dim3(kAutoThreads), A_LDS, stream, a);      // residual prefetched
+                return launch_lds<&conv_mfma_auto_kernel<Cfg, 0>>(grid, dim3(kAutoThreads), A_LDS, stream, a);
             }
         }
         return fail(RC_ERR_UNSUPPORTED, "rc_conv2d: RC_OUT_NHWC_DWT needs a bf16 / fp16 3x3 layer of one Cin chunk and one 32- or 48-wide cout tile (cin == cout == 32 or 48), 16-byte aligned operands");
@@ -2732,17 +2717,7 @@ int launch_conv_g(const ConvArgs& a, hipStream_t stream) {
         if (a.n_chunks == 1 && a.n_ct == 1 && a.cin_vec_ok && (a.persist_ok == 2 || (a.persist_ok == 1 && ws_auto)) && n_tiles < (1 << 24)) {
             if (report(0, legacy_slots)) return RC_OK;
             { int c_; if (int e_ = sums_mode(0, c_)) return e_; }
-            static PerDeviceFlag attr_set;                       // function attributes are per device (common.hpp)
-            if (!attr_set.test_and_set()) {
-                RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_ws_kernel<Cfg, GATED, FAST>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, WS_LDS));
-            }
-            int grid = a.num_cus;
-            if (grid > n_tiles) grid = n_tiles;
-            grid = (grid + 7) / 8 * 8;
-            hipLaunchKernelGGL((conv_mfma_ws_kernel<Cfg, GATED, FAST>), dim3((unsigned)grid), dim3(kWsThreads), WS_LDS, stream, a);
-            RC_HIP_CHECK(hipGetLastError());
-            return RC_OK;
+            return launch_lds<&conv_mfma_ws_kernel<Cfg, GATED, FAST>>(dim3((unsigned)persistent_grid(a.num_cus, n_tiles)), dim3(kWsThreads), WS_LDS, stream, a);
         }
     }
     // (kernel 5 is a bf16 A/B form, off by default: no fp16 instantiation)
@@ -2753,16 +2728,7 @@ int launch_conv_g(const ConvArgs& a, hipStream_t stream) {
             if (report(0, legacy_slots)) return RC_OK;
             constexpr int PSS_LDS = pss_lds_bytes<Cfg>();
             const int n_items = a.tiles_x * ((a.H + kWsmTH - 1) / kWsmTH) * a.batch;
-            static PerDeviceFlag attr_set;
-            if (!attr_set.test_and_set()) {
-                RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_pss_kernel<Cfg>), hipFuncAttributeMaxDynamicSharedMemorySize, PSS_LDS));
-            }
-            int grid = a.num_cus;
-            if (grid > n_items) grid = n_items;
-            grid = (grid + 7) / 8 * 8;
-            hipLaunchKernelGGL((conv_mfma_pss_kernel<Cfg>), dim3((unsigned)grid), dim3(kWsmThreads), PSS_LDS, stream, a);
-            RC_HIP_CHECK(hipGetLastError());
-            return RC_OK;
+            return launch_lds<&conv_mfma_pss_kernel<Cfg>>(dim3((unsigned)persistent_grid(a.num_cus, n_items)), dim3(kWsmThreads), PSS_LDS, stream, a);
         }
     }
     constexpr int WSM_LDS = wsm_lds_bytes<Cfg>();
@@ -2782,20 +2748,11 @@ int launch_conv_g(const ConvArgs& a, hipStream_t stream) {
             if (report(0, legacy_slots)) return RC_OK;
             { int c_; if (int e_ = sums_mode(0, c_)) return e_; }
             const int n_items = a.tiles_x * ((a.H + kWsmTH - 1) / kWsmTH) * a.batch * (a.n_chunks > 1 ? a.n_ct : 1);
-            int grid = a.num_cus;
-            if (grid > n_items) grid = n_items;
-            grid = (grid + 7) / 8 * 8;
+            const int grid = persistent_grid(a.num_cus, n_items);
             if constexpr ((FAST || Cfg::NT <= 3) && wst_eligible<Cfg>()) {   // (with the generic epilogue the 64-wide cout tiles spilled 1-22 registers: those stay on kernel 4)
                 if (a.thin >= (wst_form<Cfg>() == 3 ? 1 : 2)) return launch_wst<Cfg, FAST>(a, grid, stream);   // thin stages: one barrier per stage (kernel 4b), rc_debug_set("thin", 0) for kernel 4
             }
-            static PerDeviceFlag attr_set;                       // function attributes are per device (common.hpp)
-            if (!attr_set.test_and_set()) {
-                RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_wsm_kernel<Cfg, GATED, FAST>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, WSM_LDS));
-            }
-            hipLaunchKernelGGL((conv_mfma_wsm_kernel<Cfg, GATED, FAST>), dim3((unsigned)grid), dim3(kWsmThreads), WSM_LDS, stream, a);
-            RC_HIP_CHECK(hipGetLastError());
-            return RC_OK;
+            return launch_lds<&conv_mfma_wsm_kernel<Cfg, GATED, FAST>>(dim3((unsigned)grid), dim3(kWsmThreads), WSM_LDS, stream, a);
         }
     }
     if constexpr (!GATED && FAST && auto64_eligible<Cfg>()) {
@@ -2807,24 +2764,14 @@ int launch_conv_g(const ConvArgs& a, hipStream_t stream) {
         if (a.auto_impl && key_ok && a.n_chunks == 1 && a.n_ct == 1 && a.cout == Cfg::COUT_TILE && a.cin_vec_ok && a.persist_ok && a.out_mode == RC_OUT_NHWC && n_tiles < (1 << 24)) {
             constexpr int A_LDS = auto64_lds_bytes<Cfg>();
             static_assert(A_LDS <= 160 * 1024, "kernel 7 LDS");
-            int grid = a.num_cus;
-            if (grid * 2 > n_tiles) grid = (n_tiles + 1) / 2;      // two groups of four waves per block, one 8 x 32 tile each
-            grid = (grid + 7) / 8 * 8;
+            const int grid = persistent_grid(a.num_cus, (n_tiles + 1) / 2);      // two groups of four waves per block, one 8 x 32 tile each
             const int cslots = ((k7 & DD::EP_SUMS) && a.sums_compact_ok && grid * 8 < legacy_slots) ? grid * 8 : 0;   // compact sums: (grid x 2 groups) residue classes x 4 waves (small images: the per-tile layout is smaller)
             if (report(7, cslots ? cslots : legacy_slots)) return RC_OK;
             ConvArgs aa = a;
             if (int e_ = sums_mode(cslots, aa.sums_compact)) return e_;
-            static PerDeviceFlag attr_set;
-            if (!attr_set.test_and_set()) {
-                RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_auto64_kernel<Cfg, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS));
-                RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_auto64_kernel<Cfg, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS));
-                RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_auto64_kernel<Cfg, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS));
-            }
-            if (k7 & DD::EP_SUMS) hipLaunchKernelGGL((conv_mfma_auto64_kernel<Cfg, 1>), dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, aa);
-            else if (k7 & DD::EP_RES) hipLaunchKernelGGL((conv_mfma_auto64_kernel<Cfg, 2>), dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, aa);
-            else hipLaunchKernelGGL((conv_mfma_auto64_kernel<Cfg, 0>), dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, aa);
-            RC_HIP_CHECK(hipGetLastError());
-            return RC_OK;
+            if (k7 & DD::EP_SUMS) return launch_lds<&conv_mfma_auto64_kernel<Cfg, 1>>(dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, aa);
+            if (k7 & DD::EP_RES) return launch_lds<&conv_mfma_auto64_kernel<Cfg, 2>>(dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, aa);
+            return launch_lds<&conv_mfma_auto64_kernel<Cfg, 0>>(dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, aa);
         }
     }
     if constexpr (!GATED && FAST && auto_eligible<Cfg>()) {
@@ -2836,37 +2783,22 @@ int launch_conv_g(const ConvArgs& a, hipStream_t stream) {
         if (a.auto_impl && key_ok && mode_ok && a.n_chunks == 1 && a.n_ct == 1 && a.cin_vec_ok && a.persist_ok && a.out_mode == RC_OUT_NHWC && n_tiles < (1 << 24)) {
             constexpr int A_LDS = auto_lds_bytes<Cfg>();
             const int n_items = a.tiles_x * ((a.H + kWsmTH - 1) / kWsmTH) * a.batch;
-            int grid = a.num_cus;
-            if (grid > n_items) grid = n_items;
-            grid = (grid + 7) / 8 * 8;
+            const int grid = persistent_grid(a.num_cus, n_items);
             const bool run_sums = a.ep_key == DD::EP_SUMS || a.ep_key == (DD::EP_RELU | DD::EP_SUMS);
             const int cslots = (run_sums && a.sums_compact_ok && grid * 8 < legacy_slots) ? grid * 8 : 0;             // compact sums: grid residue classes of the region walk x 8 waves
             if (report(6, cslots ? cslots : legacy_slots)) return RC_OK;
             ConvArgs aa = a;
             if (int e_ = sums_mode(cslots, aa.sums_compact)) return e_;
-            static PerDeviceFlag attr_set;
-            if (!attr_set.test_and_set()) {
-                RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_auto_kernel<Cfg, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS));
-                RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_auto_kernel<Cfg, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS));
-                RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_auto_kernel<Cfg, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, A_LDS));
-            }
-            if (run_sums)
-                hipLaunchKernelGGL((conv_mfma_auto_kernel<Cfg, 1>), dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, aa);
-            else if (a.ep_key == DD::EP_RES || a.ep_key == (DD::EP_GATE | DD::EP_RES))
-                hipLaunchKernelGGL((conv_mfma_auto_kernel<Cfg, 2>), dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, aa);
-            else
-                hipLaunchKernelGGL((conv_mfma_auto_kernel<Cfg, 0>), dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, aa);
-            RC_HIP_CHECK(hipGetLastError());
-            return RC_OK;
+            if (run_sums) return launch_lds<&conv_mfma_auto_kernel<Cfg, 1>>(dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, aa);
+            if (a.ep_key == DD::EP_RES || a.ep_key == (DD::EP_GATE | DD::EP_RES))
+                return launch_lds<&conv_mfma_auto_kernel<Cfg, 2>>(dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, aa);
+            return launch_lds<&conv_mfma_auto_kernel<Cfg, 0>>(dim3((unsigned)grid), dim3(kAutoThreads), A_LDS, stream, aa);
         }
     }
     if constexpr (P_OK && !GATED) {
         if (a.n_chunks == 1 && a.cout_packed <= persist_bias_slots<Cfg>() && a.persist_ok && n_tiles < (1 << 24)) {
-            int grid = persist_blocks_per_cu<Cfg>() * a.num_cus;
             const bool one_per_cu = (a.dbg_flags & 64) != 0 && P_LDS <= 80 * 1024;      // occupancy experiment: LDS padded so that ONE block fits a CU
-            if (one_per_cu) grid = a.num_cus;
-            if (grid > n_tiles) grid = n_tiles;
-            grid = (grid + 7) / 8 * 8;
+            const int grid = persistent_grid((one_per_cu ? 1 : persist_blocks_per_cu<Cfg>()) * a.num_cus, n_tiles);
             // the carried-sums (RUN) form of this kernel: fast epilogue, bf16, >= 3 cout tiles per block, one cout tile per layer
             const bool run_sums = FAST && sizeof(typename Cfg::elem) == 2 && Cfg::NT >= 3 && a.n_ct == 1 &&
                                   (a.ep_key == ConvDev<Cfg>::EP_SUMS || a.ep_key == (ConvDev<Cfg>::EP_RELU | ConvDev<Cfg>::EP_SUMS));
@@ -2878,27 +2810,15 @@ int launch_conv_g(const ConvArgs& a, hipStream_t stream) {
             const int lds_res = P_LDS + (a.n_ct - 1) * (int)Cfg::CHUNK_W_BYTES;
             aa.w_resident = (a.n_ct > 1 && lds_res <= 80 * 1024 && !(a.dbg_flags & 128)) ? 1 : 0;       // conv_flags 128: A/B
             const int lds_bytes = one_per_cu ? 100 * 1024 : (aa.w_resident ? lds_res : P_LDS);
-            static PerDeviceFlag attr_set;                       // function attributes are per device (common.hpp)
-            if (!attr_set.test_and_set()) {
-                RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_persist_kernel<Cfg, GATED, FAST>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS > 100 * 1024 ? P_LDS : 100 * 1024));
-            }
-            hipLaunchKernelGGL((conv_mfma_persist_kernel<Cfg, GATED, FAST>), dim3((unsigned)grid), dim3(kThreads), lds_bytes, stream, aa);
-            RC_HIP_CHECK(hipGetLastError());
-            return RC_OK;
+            // one limit for every size this kernel is launched with (resident weights, the one-per-CU padding)
+            if (int e_ = allow_lds<&conv_mfma_persist_kernel<Cfg, GATED, FAST>>(P_LDS > 100 * 1024 ? P_LDS : 100 * 1024)) return e_;
+            return launch_lds<&conv_mfma_persist_kernel<Cfg, GATED, FAST>>(dim3((unsigned)grid), dim3(kThreads), lds_bytes, stream, aa);
         }
     }
     if (report(0, legacy_slots)) return RC_OK;
     { int c_; if (int e_ = sums_mode(0, c_)) return e_; }
-    static PerDeviceFlag attr_set;                       // function attributes are per device (common.hpp)
-    if (!attr_set.test_and_set()) {
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<Cfg, GATED, FAST>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES));
-    }
     dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.n_ct), (unsigned)a.batch, 1);
-    hipLaunchKernelGGL((conv_mfma_kernel<Cfg, GATED, FAST>), grid, dim3(kThreads), Cfg::LDS_BYTES, stream, a);
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    return launch_lds<&conv_mfma_kernel<Cfg, GATED, FAST>>(grid, dim3(kThreads), Cfg::LDS_BYTES, stream, a);
 }
 
 template <class Cfg>

@@ -472,17 +472,8 @@ __global__ __launch_bounds__(THREADS) void conv_pair_kernel(const PairArgs a) {
 
 template <bool GATED, int E1, int E2>
 int launch(const PairArgs& a, int num_cus, hipStream_t stream) {
-    static PerDeviceFlag attr_set;
-    if (!attr_set.test_and_set()) {
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pair_kernel<GATED, E1, E2>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    }
-    const int n_tiles = a.tiles_x * a.tiles_y * a.batch;
-    int grid = num_cus < n_tiles ? num_cus : n_tiles;
-    grid = (grid + 7) / 8 * 8;
-    hipLaunchKernelGGL((conv_pair_kernel<GATED, E1, E2>), dim3((unsigned)grid), dim3(THREADS), LDS_BYTES, stream, a);
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    const int grid = persistent_grid(num_cus, a.tiles_x * a.tiles_y * a.batch);
+    return launch_lds<&conv_pair_kernel<GATED, E1, E2>>(dim3((unsigned)grid), dim3(THREADS), LDS_BYTES, stream, a);
 }
 
 }  // namespace pair
@@ -890,17 +881,8 @@ __global__ __launch_bounds__(THREADS) void conv_pair2_kernel(const PairArgs a) {
 
 template <bool GATED, int E1, int E2>
 int launch(const PairArgs& a, int num_cus, hipStream_t stream) {
-    static PerDeviceFlag attr_set;
-    if (!attr_set.test_and_set()) {
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pair2_kernel<GATED, E1, E2>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    }
-    const int n_tiles = a.tiles_x * a.tiles_y * a.batch;
-    int grid = num_cus < n_tiles ? num_cus : n_tiles;
-    grid = (grid + 7) / 8 * 8;
-    hipLaunchKernelGGL((conv_pair2_kernel<GATED, E1, E2>), dim3((unsigned)grid), dim3(THREADS), LDS_BYTES, stream, a);
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    const int grid = persistent_grid(num_cus, a.tiles_x * a.tiles_y * a.batch);
+    return launch_lds<&conv_pair2_kernel<GATED, E1, E2>>(dim3((unsigned)grid), dim3(THREADS), LDS_BYTES, stream, a);
 }
 
 }  // namespace pair2

@@ -550,12 +550,8 @@ int rc_dwconv2d(const void* d_x, int x_stride_c, int x_c0, void* d_y, int y_stri
     RC_REQUIRE(n_w % 4 == 0, "rc_dwconv2d: n_w must be a multiple of 4");
 #define RC_DW_LAUNCH(TT, KK)                                                                                              \
     do {                                                                                                                  \
-        static PerDeviceFlag attr_set;                                                                                     \
-        if (!attr_set.test_and_set()) {                                                                                                  \
-            RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv2d_kernel<TT, KK>),                     \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                    \
-        }                                                                                                                 \
-        hipLaunchKernelGGL((dwconv2d_kernel<TT, KK>), dim3((unsigned)blocks), dim3(64 * vb), lds, as_stream(stream),      \
+        if (int e_ = allow_lds<&dwconv2d_kernel<TT, KK>>(160 * 1024)) return e_;                                          \
+        return launch_lds<&dwconv2d_kernel<TT, KK>>(dim3((unsigned)blocks), dim3(64 * vb), (int)lds, as_stream(stream),   \
                            static_cast<const TT*>(d_x), x_stride_c, x_c0, static_cast<TT*>(d_y), y_stride_c, y_c0, batch, \
                            H, W, n_ch, d_wT, n_w, d_bias, n_rep, x_rep_stride, y_rep_stride, w_rep_stride, add_identity,  \
                            d_kvec, vb, tiles_x, tiles_y);                                                                 \
@@ -564,8 +560,6 @@ int rc_dwconv2d(const void* d_x, int x_stride_c, int x_c0, void* d_y, int y_stri
     if (dtype == RC_F32) { RC_DW_K(float) } else { RC_DW_K(bf16_t) }
 #undef RC_DW_K
 #undef RC_DW_LAUNCH
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
 }
 
 int rc_layernorm(const void* d_x, void* d_y, int dtype, long long tokens, int c, const float* d_gamma,
@@ -607,12 +601,8 @@ int rc_gma_pointwise(const void* d_qkv, const void* d_dw, const void* d_dwl, int
     const unsigned gx = (unsigned)(n_tiles < 1024 ? n_tiles : 1024);
 #define RC_PW_LAUNCH(TT, SG, TK)                                                                                        \
     do {                                                                                                                \
-        static PerDeviceFlag attr;                                                                                       \
-        if (!attr.test_and_set()) {                                                                                                    \
-            RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gma_pointwise_kernel<TT, SG, TK>),          \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                  \
-        }                                                                                                               \
-        hipLaunchKernelGGL((gma_pointwise_kernel<TT, SG, TK>), dim3(gx), dim3(kPwWaves * 64), lds, as_stream(stream),   \
+        if (int e_ = allow_lds<&gma_pointwise_kernel<TT, SG, TK>>(160 * 1024)) return e_;                               \
+        return launch_lds<&gma_pointwise_kernel<TT, SG, TK>>(dim3(gx), dim3(kPwWaves * 64), (int)lds, as_stream(stream), \
                            static_cast<const TT*>(d_qkv), static_cast<const TT*>(d_dw), static_cast<const TT*>(d_dwl),  \
                            dw_tok_stride, dw_rep_stride, dwl_tok_stride, dwl_rep_stride, static_cast<TT*>(d_qkvp), static_cast<TT*>(d_loc), (size_t)tokens, c, d_pw, d_bn_scale,      \
                            d_bn_shift, d_pwl, d_ln_g, d_ln_b);                                                          \
@@ -625,8 +615,6 @@ int rc_gma_pointwise(const void* d_qkv, const void* d_dw, const void* d_dwl, int
 #undef RC_PW_SEG
 #undef RC_PW_TOK
 #undef RC_PW_LAUNCH
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
 }
 
 int rc_gma_kv_blocks(int n_tok) {

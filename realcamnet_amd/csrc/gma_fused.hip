@@ -518,20 +518,12 @@ int rc_gma_ln_qkv(const void* d_x, void* d_qkv, long long tokens, const void* d_
     RC_REQUIRE(tokens >= 1, "rc_gma_ln_qkv: no tokens");
     constexpr int MT = n_mtiles(3 * kC);
     const size_t lds = (size_t)MT * tile_bytes(kC) + 4 * (MT * 16 + 2 * kC);
-    int dev = 0;
-    RC_HIP_CHECK(hipGetDevice(&dev));
-    static bool attr[64] = {};                                            // function attributes are per device
-    if (dev >= 0 && dev < 64 && !attr[dev]) {
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gma_ln_qkv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-        attr[dev] = true;
-    }
+    if (int e_ = allow_lds<&gma_ln_qkv_kernel>(64 * 1024)) return e_;
     const size_t n_tiles = ((size_t)tokens + 63) / 64;
     size_t blocks = (n_tiles + 3) / 4;
     if (blocks > 256 * 3) blocks = 256 * 3;
-    hipLaunchKernelGGL(gma_ln_qkv_kernel, dim3((unsigned)blocks), dim3(kQkvThreads), lds, as_stream(stream), static_cast<const bf16_t*>(d_x),
-                       static_cast<bf16_t*>(d_qkv), (size_t)tokens, d_wpacked, d_bias_packed, d_ln_gamma, d_ln_beta, eps);
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    return launch_lds<&gma_ln_qkv_kernel>(dim3((unsigned)blocks), dim3(kQkvThreads), (int)lds, as_stream(stream), static_cast<const bf16_t*>(d_x),
+                                          static_cast<bf16_t*>(d_qkv), (size_t)tokens, d_wpacked, d_bias_packed, d_ln_gamma, d_ln_beta, eps);
 }
 
 int rc_gma_tail(const void* d_qkvp, const void* d_convv, const void* d_loc, const void* d_x, const float* d_ktv, void* d_ktv_frags,
@@ -552,28 +544,16 @@ int rc_gma_tail(const void* d_qkvp, const void* d_convv, const void* d_loc, cons
     a.ln_g = d_ln_gamma; a.ln_b = d_ln_beta; a.eps = eps; a.n_tok = n_tok; a.batch = batch;
     hipLaunchKernelGGL(gma_ktv_pack_kernel, dim3(batch), dim3(512), 0, as_stream(stream), d_ktv, static_cast<uint4*>(d_ktv_frags));
     const long long n_tiles = (long long)((n_tok + 63) / 64) * batch;
-    int dev = 0;
-    RC_HIP_CHECK(hipGetDevice(&dev));
-    RC_REQUIRE(dev >= 0 && dev < 64, "rc_gma_tail: device index out of range");
-    static int cus[64] = {};
-    if (!cus[dev]) RC_HIP_CHECK(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
-    const int num_cus = cus[dev];
+    const int num_cus = device_cu_count();
     long long blocks = (n_tiles + kTailWaves - 1) / kTailWaves;
     if (blocks > num_cus) blocks = num_cus;                               // one 8-wave block per CU (154 KB of LDS), grid-stride over tiles
 #define RC_TAIL_LAUNCH(CO)                                                                                                          \
     do {                                                                                                                            \
-        static bool attr[64] = {};                                                                                                  \
-        if (!attr[dev]) {                                                                                                           \
-            RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gma_tail_kernel<CO>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                             160 * 1024));                                                                          \
-            attr[dev] = true;                                                                                                       \
-        }                                                                                                                           \
-        hipLaunchKernelGGL((gma_tail_kernel<CO>), dim3((unsigned)blocks), dim3(kTailThreads), tail_lds_bytes<CO>(), as_stream(stream), a); \
+        if (int e_ = allow_lds<&gma_tail_kernel<CO>>(160 * 1024)) return e_;                                                        \
+        return launch_lds<&gma_tail_kernel<CO>>(dim3((unsigned)blocks), dim3(kTailThreads), (int)tail_lds_bytes<CO>(), as_stream(stream), a); \
     } while (0)
     if (cout == 0) RC_TAIL_LAUNCH(0); else RC_TAIL_LAUNCH(192);
 #undef RC_TAIL_LAUNCH
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
 }
 
 }  // extern "C"
@@ -1336,23 +1316,13 @@ extern "C" int rc_gma_qkv_aggregate(const void* d_x, const void* d_wq_natural, c
     a.wq = d_wq_natural; a.bq = d_bq; a.ln1_g = d_ln1_g; a.ln1_b = d_ln1_b; a.eps = eps;
     a.toep = static_cast<const char*>(d_toeplitz); a.pw = d_pw; a.pwl = d_pwl;
     a.bn_scale = d_bn_scale; a.bn_shift = d_bn_shift; a.ln_g = d_ln_g; a.ln_b = d_ln_b;
-    int dev = 0;
-    RC_HIP_CHECK(hipGetDevice(&dev));
-    RC_REQUIRE(dev >= 0 && dev < 64, "rc_gma_qkv_aggregate: device index out of range");
-    static int cus[64] = {};
-    static bool attr[64] = {};
-    if (!cus[dev]) RC_HIP_CHECK(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
-    if (!attr[dev]) {
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gma_qkv_agg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr[dev] = true;
-    }
+    const int num_cus = device_cu_count();
+    if (int e_ = allow_lds<&gma_qkv_agg_kernel>(160 * 1024)) return e_;
     if (d_kmax) RC_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_kmax), (int)0xff800000u /* -inf */, (size_t)batch * 64, as_stream(stream)));
-    int blocks = a.n_tiles < cus[dev] ? a.n_tiles : cus[dev];                // one 8-wave block per CU, a contiguous run of tiles each
+    int blocks = a.n_tiles < num_cus ? a.n_tiles : num_cus;                  // one 8-wave block per CU, a contiguous run of tiles each
     a.tiles_per_block = (a.n_tiles + blocks - 1) / blocks;
     blocks = (a.n_tiles + a.tiles_per_block - 1) / a.tiles_per_block;
-    hipLaunchKernelGGL(gma_qkv_agg_kernel, dim3((unsigned)blocks), dim3(QA_THREADS), QA_LDS, as_stream(stream), a);
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    return launch_lds<&gma_qkv_agg_kernel>(dim3((unsigned)blocks), dim3(QA_THREADS), QA_LDS, as_stream(stream), a);
 }
 
 // ---- depth-wise 3x3 (+ bias, + identity) of NHWC maps whose channel count is a multiple of 16: rc_dwconv2d's bf16 3x3 single-rep case
@@ -1616,22 +1586,12 @@ extern "C" int rc_gma_in_cpe(const void* d_d1, const void* d_w_in_natural, const
     RC_REQUIRE(n_tiles < (1ll << 31), "rc_gma_in_cpe: too many tiles");
     a.n_tiles = (int)n_tiles;
     a.w_in = d_w_in_natural; a.b_in = d_b_in; a.toep = static_cast<const char*>(d_toeplitz3); a.b_cpe = d_b_cpe;
-    int dev = 0;
-    RC_HIP_CHECK(hipGetDevice(&dev));
-    RC_REQUIRE(dev >= 0 && dev < 64, "rc_gma_in_cpe: device index out of range");
-    static int cus[64] = {};
-    static bool attr[64] = {};
-    if (!cus[dev]) RC_HIP_CHECK(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
-    if (!attr[dev]) {
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gma_in_cpe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr[dev] = true;
-    }
-    int blocks = a.n_tiles < cus[dev] ? a.n_tiles : cus[dev];
+    const int num_cus = device_cu_count();
+    if (int e_ = allow_lds<&gma_in_cpe_kernel>(160 * 1024)) return e_;
+    int blocks = a.n_tiles < num_cus ? a.n_tiles : num_cus;
     a.tiles_per_block = (a.n_tiles + blocks - 1) / blocks;
     blocks = (a.n_tiles + a.tiles_per_block - 1) / a.tiles_per_block;
-    hipLaunchKernelGGL(gma_in_cpe_kernel, dim3((unsigned)blocks), dim3(GI_THREADS), GI_LDS, as_stream(stream), a);
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    return launch_lds<&gma_in_cpe_kernel>(dim3((unsigned)blocks), dim3(GI_THREADS), GI_LDS, as_stream(stream), a);
 }
 
 // =====================================================================================================================================
@@ -2059,18 +2019,14 @@ extern "C" int rc_lsc_chain(const void* d_x, int cin0, const void* d_blob, int c
     if (grid > cap) grid = cap;
 #define RC_LSC(CC, HH)                                                                                                                    \
     do {                                                                                                                                  \
-        static PerDeviceFlag attr;                                                                                                        \
-        if (!attr.test_and_set())                                                                                                         \
-            RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&lsc_chain_kernel<CC, HH>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); \
-        hipLaunchKernelGGL((lsc_chain_kernel<CC, HH>), dim3((unsigned)grid), dim3(lsc_threads<CC>()), lds, as_stream(stream), a);              \
+        if (int e_ = allow_lds<&lsc_chain_kernel<CC, HH>>(150 * 1024)) return e_;                                                    \
+        return launch_lds<&lsc_chain_kernel<CC, HH>>(dim3((unsigned)grid), dim3(lsc_threads<CC>()), (int)lds, as_stream(stream), a); \
     } while (0)
     if (c == 32) { if (d_raw) RC_LSC(32, true); else RC_LSC(32, false); }            // the ISPUNet family's width
     else if (c == 48) { if (d_raw) RC_LSC(48, true); else RC_LSC(48, false); }
     else if (c == 64) { if (d_raw) RC_LSC(64, true); else RC_LSC(64, false); }
     else RC_LSC(128, false);
 #undef RC_LSC
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
 }
 
 
@@ -2327,15 +2283,11 @@ extern "C" int rc_ln_mlp(const void* d_x, void* d_out, long long tokens, int c, 
     if (grid > cap) grid = cap;
 #define RC_MLP(CC)                                                                                                                         \
     do {                                                                                                                                   \
-        static PerDeviceFlag attr;                                                                                                         \
-        if (!attr.test_and_set())                                                                                                          \
-            RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ln_mlp_kernel<CC>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)); \
-        hipLaunchKernelGGL((ln_mlp_kernel<CC>), dim3((unsigned)grid), dim3(kMlpThreads), lds, as_stream(stream), a);                       \
+        if (int e_ = allow_lds<&ln_mlp_kernel<CC>>(80 * 1024)) return e_;                                               \
+        return launch_lds<&ln_mlp_kernel<CC>>(dim3((unsigned)grid), dim3(kMlpThreads), (int)lds, as_stream(stream), a); \
     } while (0)
     if (c == 32) RC_MLP(32); else RC_MLP(64);
 #undef RC_MLP
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
 }
 
 // =====================================================================================================================================
@@ -2425,15 +2377,11 @@ static int ln_linear_launch(const void* d_x, void* d_out, long long tokens, int 
     if (grid > cap) grid = cap;
 #define RC_LL(CC)                                                                                                                          \
     do {                                                                                                                                   \
-        static PerDeviceFlag attr;                                                                                                         \
-        if (!attr.test_and_set())                                                                                                          \
-            RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ln_linear_kernel<CC>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024)); \
-        hipLaunchKernelGGL((ln_linear_kernel<CC>), dim3((unsigned)grid), dim3(kMlpThreads), lds, as_stream(stream), a);                    \
+        if (int e_ = allow_lds<&ln_linear_kernel<CC>>(80 * 1024)) return e_;                                               \
+        return launch_lds<&ln_linear_kernel<CC>>(dim3((unsigned)grid), dim3(kMlpThreads), (int)lds, as_stream(stream), a); \
     } while (0)
     if (c == 32) RC_LL(32); else RC_LL(64);
 #undef RC_LL
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
 }
 
 // =====================================================================================================================================

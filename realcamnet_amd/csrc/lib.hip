@@ -159,15 +159,14 @@ __global__ __launch_bounds__(256) void lds_poison_kernel(unsigned pattern, int w
 }
 }  // namespace rc
 
-extern "C" {
-
-int rc_debug_mfma_peak(int waves_per_simd, int iters, double* tflops, double* memtime_ticks_per_mfma) {
+// The two MFMA peak probes (16x16x32 and 32x32x16 bf16) are one measurement around another kernel pair: `nacc` independent accumulators (= MFMAs per
+// wave and loop iteration) of `mfma_flops` each.
+template <auto PowerKernel, auto PeakKernel>
+static int mfma_peak_run(const char* bad_args, int nacc, double mfma_flops, int waves_per_simd, int iters, double* tflops, double* memtime_ticks_per_mfma) {
     const bool random_ops = waves_per_simd > 10;             // 11 / 12: random operands that change from MFMA to MFMA (power, not clock, limits those)
     if (random_ops) waves_per_simd -= 10;
-    RC_REQUIRE(tflops != nullptr && iters >= 1 && waves_per_simd >= 1 && waves_per_simd <= 2, "rc_debug_mfma_peak: bad arguments");
-    int dev = 0, cus = 0;
-    RC_HIP_CHECK(hipGetDevice(&dev));
-    RC_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    RC_REQUIRE(tflops != nullptr && iters >= 1 && waves_per_simd >= 1 && waves_per_simd <= 2, bad_args);
+    const int cus = rc::device_cu_count();
     float* sink = nullptr; long long* cyc = nullptr;
     RC_HIP_CHECK(hipMalloc(&sink, 4)); RC_HIP_CHECK(hipMalloc(&cyc, 8));
     hipEvent_t e0, e1;
@@ -175,8 +174,8 @@ int rc_debug_mfma_peak(int waves_per_simd, int iters, double* tflops, double* me
     const int grid = cus * waves_per_simd;                // 256 threads = 4 waves = one per SIMD
     for (int rep = 0; rep < 3; ++rep) {                   // first passes bring the clocks up
         RC_HIP_CHECK(hipEventRecord(e0, nullptr));
-        if (random_ops) hipLaunchKernelGGL(rc::mfma_power_kernel<16>, dim3(grid), dim3(256), 0, nullptr, sink, iters);
-        else hipLaunchKernelGGL(rc::mfma_peak_kernel, dim3(grid), dim3(256), 0, nullptr, sink, iters, cyc);
+        if (random_ops) hipLaunchKernelGGL(PowerKernel, dim3(grid), dim3(256), 0, nullptr, sink, iters);
+        else hipLaunchKernelGGL(PeakKernel, dim3(grid), dim3(256), 0, nullptr, sink, iters, cyc);
         RC_HIP_CHECK(hipEventRecord(e1, nullptr));
         RC_HIP_CHECK(hipEventSynchronize(e1));
     }
@@ -184,47 +183,25 @@ int rc_debug_mfma_peak(int waves_per_simd, int iters, double* tflops, double* me
     RC_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
     long long h = 0;
     RC_HIP_CHECK(hipMemcpy(&h, cyc, 8, hipMemcpyDeviceToHost));
-    *tflops = (double)grid * 4 * iters * 16 * 16384.0 / (ms * 1e-3) / 1e12;
-    if (memtime_ticks_per_mfma) *memtime_ticks_per_mfma = (double)h / ((double)iters * 16 * waves_per_simd);
+    *tflops = (double)grid * 4 * iters * nacc * mfma_flops / (ms * 1e-3) / 1e12;
+    if (memtime_ticks_per_mfma) *memtime_ticks_per_mfma = (double)h / ((double)iters * nacc * waves_per_simd);
     (void)hipFree(sink); (void)hipFree(cyc); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     return RC_OK;
+}
+
+extern "C" {
+
+int rc_debug_mfma_peak(int waves_per_simd, int iters, double* tflops, double* memtime_ticks_per_mfma) {
+    return mfma_peak_run<&rc::mfma_power_kernel<16>, &rc::mfma_peak_kernel>("rc_debug_mfma_peak: bad arguments", 16, 16384.0, waves_per_simd, iters, tflops, memtime_ticks_per_mfma);
 }
 
 int rc_debug_poison_lds(unsigned pattern, void* stream) {
     constexpr int kBytes = 160 * 1024;
-    static rc::PerDeviceFlag attr;
-    if (!attr.test_and_set())
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rc::lds_poison_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kBytes));
-    hipLaunchKernelGGL(rc::lds_poison_kernel, dim3((unsigned)(rc::device_cu_count() * 4)), dim3(256), kBytes, static_cast<hipStream_t>(stream), pattern, kBytes / 4);
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    return rc::launch_lds<&rc::lds_poison_kernel>(dim3((unsigned)(rc::device_cu_count() * 4)), dim3(256), kBytes, static_cast<hipStream_t>(stream), pattern, kBytes / 4);
 }
 
 int rc_debug_mfma_peak32(int waves_per_simd, int iters, double* tflops, double* memtime_ticks_per_mfma) {
-    const bool random_ops = waves_per_simd > 10;
-    if (random_ops) waves_per_simd -= 10;
-    RC_REQUIRE(tflops != nullptr && iters >= 1 && waves_per_simd >= 1 && waves_per_simd <= 2, "rc_debug_mfma_peak32: bad arguments");
-    const int cus = rc::device_cu_count();
-    float* sink = nullptr; long long* cyc = nullptr;
-    RC_HIP_CHECK(hipMalloc(&sink, 4)); RC_HIP_CHECK(hipMalloc(&cyc, 8));
-    hipEvent_t e0, e1;
-    RC_HIP_CHECK(hipEventCreate(&e0)); RC_HIP_CHECK(hipEventCreate(&e1));
-    const int grid = cus * waves_per_simd;
-    for (int rep = 0; rep < 3; ++rep) {
-        RC_HIP_CHECK(hipEventRecord(e0, nullptr));
-        if (random_ops) hipLaunchKernelGGL(rc::mfma_power_kernel<32>, dim3(grid), dim3(256), 0, nullptr, sink, iters);
-        else hipLaunchKernelGGL(rc::mfma_peak32_kernel, dim3(grid), dim3(256), 0, nullptr, sink, iters, cyc);
-        RC_HIP_CHECK(hipEventRecord(e1, nullptr));
-        RC_HIP_CHECK(hipEventSynchronize(e1));
-    }
-    float ms = 0.f;
-    RC_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    long long h = 0;
-    RC_HIP_CHECK(hipMemcpy(&h, cyc, 8, hipMemcpyDeviceToHost));
-    *tflops = (double)grid * 4 * iters * 8 * 32768.0 / (ms * 1e-3) / 1e12;
-    if (memtime_ticks_per_mfma) *memtime_ticks_per_mfma = (double)h / ((double)iters * 8 * waves_per_simd);
-    (void)hipFree(sink); (void)hipFree(cyc); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return RC_OK;
+    return mfma_peak_run<&rc::mfma_power_kernel<32>, &rc::mfma_peak32_kernel>("rc_debug_mfma_peak32: bad arguments", 8, 32768.0, waves_per_simd, iters, tflops, memtime_ticks_per_mfma);
 }
 
 int rc_debug_hbm_probe(const void* src, void* dst, size_t bytes, int mode, int nt, int contiguous, int blocks, int iters,

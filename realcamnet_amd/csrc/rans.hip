@@ -659,18 +659,16 @@ int rc_rans_decode_chunks(const void* d_stream, long long stream_bytes, const lo
     const Tables t{d_cdf, cdf_stride, n_cdfs, d_cdf_sizes, d_cdf_offsets};
     const size_t lds = (size_t)(3 * n_cdfs + 2) * 4 + (size_t)kDecLdsEntries * 2;
     if (g_dec_lds && n_cdfs >= 1 && n_cdfs <= 1024 && cdf_stride >= 2) {       // tables in LDS (falls back to global probes inside the kernel if they do not fit)
-        static PerDeviceFlag attr;
-        if (!attr.test_and_set())
-            RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_chunks_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+        if (int e_ = allow_lds<&decode_chunks_lds_kernel>(150 * 1024)) return e_;
         // chunks per wave: as few as keeps every CU busy with two blocks -- a wave executes every branch any of its lanes takes, and the chunk count
         // (1 350 for a 4K latent) leaves most of the chip idle either way: 1.50 -> 1.42 ms
         long lanes = (n_chunks + 2 * device_cu_count() - 1) / (2 * device_cu_count());
         lanes = lanes < 1 ? 1 : (lanes > 64 ? 64 : lanes);
-        hipLaunchKernelGGL(decode_chunks_lds_kernel, dim3((unsigned)((n_chunks + lanes - 1) / lanes)), dim3(64), lds, as_stream(stream), static_cast<const uint8_t*>(d_stream),
-                           stream_bytes, d_offsets, d_indexes, (long)n, chunk, t, d_symbols, d_err, n_chunks, (int)lanes);
-    } else
-        hipLaunchKernelGGL(decode_chunks_kernel, dim3((unsigned)((n_chunks + 63) / 64)), dim3(64), 0, as_stream(stream), static_cast<const uint8_t*>(d_stream),
-                           stream_bytes, d_offsets, d_indexes, (long)n, chunk, t, d_symbols, d_err, n_chunks);
+        return launch_lds<&decode_chunks_lds_kernel>(dim3((unsigned)((n_chunks + lanes - 1) / lanes)), dim3(64), (int)lds, as_stream(stream), static_cast<const uint8_t*>(d_stream),
+                                                     stream_bytes, d_offsets, d_indexes, (long)n, chunk, t, d_symbols, d_err, n_chunks, (int)lanes);
+    }
+    hipLaunchKernelGGL(decode_chunks_kernel, dim3((unsigned)((n_chunks + 63) / 64)), dim3(64), 0, as_stream(stream), static_cast<const uint8_t*>(d_stream),
+                       stream_bytes, d_offsets, d_indexes, (long)n, chunk, t, d_symbols, d_err, n_chunks);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

@@ -383,14 +383,9 @@ long long* conv_dbg_ptr();
 template <int NCW, int NNT, bool DBG = false>
 static int wino_launch_f32(const WinoArgs& a, int num_cus, hipStream_t stream) {
     using C = WinoCfg<NCW, NNT>;
-    static PerDeviceFlag attr_set;
-    if (!attr_set.test_and_set())
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_f32_kernel<NCW, NNT, DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES));
     const int per_cu = NNT == 1 && NCW == 4 ? 3 : 2;                        // resident blocks per CU (registers, LDS)
     const int grid = a.n_items < per_cu * num_cus ? a.n_items : per_cu * num_cus;
-    hipLaunchKernelGGL((wino_f32_kernel<NCW, NNT, DBG>), dim3(grid), dim3(C::THREADS), C::LDS_BYTES, stream, a);
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    return launch_lds<&wino_f32_kernel<NCW, NNT, DBG>>(dim3(grid), dim3(C::THREADS), C::LDS_BYTES, stream, a);
 }
 
 // cout tiles (of 16) per block for a layer: the widest of 4 / 3 / 2 / 1 that divides cout / 16

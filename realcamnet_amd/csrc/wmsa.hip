@@ -375,13 +375,9 @@ static int window_attention_impl(const void* d_qkv, const float* d_relpos, void*
     const size_t lds = (size_t)kWmsaWaves * (2 * 64 * (head_dim + 1) + (2 * window - 1) * (2 * window - 1)) * sizeof(float);
 #define RC_WM(TT, HD, WS)                                                                                                 \
     do {                                                                                                                  \
-        static PerDeviceFlag attr;                                                                                         \
-        if (!attr.test_and_set()) {                                                                                                      \
-            RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&wmsa_kernel<TT, HD, WS>),                     \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));                     \
-        }                                                                                                                 \
-        hipLaunchKernelGGL((wmsa_kernel<TT, HD, WS>), dim3((unsigned)blocks), dim3(kWmsaWaves * 64), lds, as_stream(stream), \
-                           static_cast<const TT*>(d_qkv), d_relpos, static_cast<TT*>(d_out), batch, H, W, C, shift);     \
+        if (int e_ = allow_lds<&wmsa_kernel<TT, HD, WS>>(96 * 1024)) return e_;                                           \
+        return launch_lds<&wmsa_kernel<TT, HD, WS>>(dim3((unsigned)blocks), dim3(kWmsaWaves * 64), (int)lds, as_stream(stream), \
+                                                    static_cast<const TT*>(d_qkv), d_relpos, static_cast<TT*>(d_out), batch, H, W, C, shift); \
     } while (0)
 #define RC_WM_HD(TT, WS) do { if (head_dim == 8) RC_WM(TT, 8, WS); else if (head_dim == 16) RC_WM(TT, 16, WS); else RC_WM(TT, 32, WS); } while (0)
 #define RC_WM_WS(TT) do { if (window == 8) RC_WM_HD(TT, 8); else RC_WM_HD(TT, 4); } while (0)
@@ -389,6 +385,4 @@ static int window_attention_impl(const void* d_qkv, const float* d_relpos, void*
 #undef RC_WM_WS
 #undef RC_WM_HD
 #undef RC_WM
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
 }

@@ -174,21 +174,11 @@ extern "C" int rc_gi_exp(const void* d_d1, const void* d_w_in_natural, const flo
     RC_REQUIRE(n_tiles < (1ll << 31), "rc_gi_exp: too many tiles");
     a.n_tiles = (int)n_tiles;
     a.w_in = d_w_in_natural; a.b_in = d_b_in; a.toep = static_cast<const char*>(d_toeplitz3); a.b_cpe = d_b_cpe;
-    int dev = 0;
-    RC_HIP_CHECK(hipGetDevice(&dev));
-    RC_REQUIRE(dev >= 0 && dev < 64, "rc_gi_exp: device index out of range");
-    static int cus[64] = {};
-    static bool attr[64] = {};
-    if (!cus[dev]) RC_HIP_CHECK(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
-    if (!attr[dev]) {
-        RC_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gi_exp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr[dev] = true;
-    }
-    int blocks = a.n_tiles < cus[dev] ? a.n_tiles : cus[dev];
+    const int num_cus = device_cu_count();
+    if (int e_ = allow_lds<&gi_exp_kernel>(160 * 1024)) return e_;
+    int blocks = a.n_tiles < num_cus ? a.n_tiles : num_cus;
     a.tiles_per_block = (a.n_tiles + blocks - 1) / blocks;
     blocks = (a.n_tiles + a.tiles_per_block - 1) / a.tiles_per_block;
-    hipLaunchKernelGGL(gi_exp_kernel, dim3((unsigned)blocks), dim3(GX_THREADS), GX_LDS, as_stream(stream), a);
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    return launch_lds<&gi_exp_kernel>(dim3((unsigned)blocks), dim3(GX_THREADS), GX_LDS, as_stream(stream), a);
 }
 
