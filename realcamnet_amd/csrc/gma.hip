@@ -527,6 +527,7 @@ int rc_dwconv2d(const void* d_x, int x_stride_c, int x_c0, void* d_y, int y_stri
                 void* stream) {
     RC_REQUIRE(d_x && d_y && d_wT, "rc_dwconv2d: null pointer");
     RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_dwconv2d: bad dtype");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && reinterpret_cast<uintptr_t>(d_y) % 16 == 0, "rc_dwconv2d: misaligned tensor");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(batch >= 1 && H >= 1 && W >= 1 && n_ch >= U && n_rep >= 1, "rc_dwconv2d: bad shape");
     RC_REQUIRE(ksize == 3 || ksize == 5 || ksize == 7, "rc_dwconv2d: kernel size must be 3, 5 or 7");
@@ -566,6 +567,7 @@ int rc_layernorm(const void* d_x, void* d_y, int dtype, long long tokens, int c,
                  const float* d_beta, float eps, void* stream) {
     RC_REQUIRE(d_x && d_y && d_gamma && d_beta, "rc_layernorm: null pointer");
     RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_layernorm: bad dtype");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && reinterpret_cast<uintptr_t>(d_y) % 16 == 0, "rc_layernorm: misaligned tensor");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(tokens >= 1 && c >= U && c % U == 0 && c / U <= 64, "rc_layernorm: C must be a multiple of 16 bytes, at most 64 vectors");
     const size_t threads = (size_t)tokens * 16;
@@ -585,6 +587,7 @@ int rc_gma_pointwise(const void* d_qkv, const void* d_dw, const void* d_dwl, int
     RC_REQUIRE(d_qkv && d_dw && d_dwl && d_qkvp && d_loc && d_pw && d_bn_scale && d_bn_shift && d_pwl && d_ln_g && d_ln_b,
                "rc_gma_pointwise: null pointer");
     RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_gma_pointwise: bad dtype");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_qkv) % 16 == 0 && reinterpret_cast<uintptr_t>(d_dw) % 16 == 0 && reinterpret_cast<uintptr_t>(d_dwl) % 16 == 0 && reinterpret_cast<uintptr_t>(d_qkvp) % 16 == 0 && reinterpret_cast<uintptr_t>(d_loc) % 16 == 0, "rc_gma_pointwise: misaligned tensor");
     RC_REQUIRE(tokens >= 1 && c >= 10 && c % 5 == 0, "rc_gma_pointwise: C must be a multiple of 5");
     const int seg = c / 5;
     RC_REQUIRE(seg == 16 || seg == 40 || seg == 8 || seg == 24 || seg == 32, "rc_gma_pointwise: C/5 must be one of 8, 16, 24, 32, 40 (dims 40..200)");
@@ -634,6 +637,7 @@ static int gma_kv_impl(const void* d_qkvp, size_t plane, int dtype, int batch, i
     RC_REQUIRE(d_qkvp && d_scratch && d_ktv, "rc_gma_kv: null pointer");
     RC_REQUIRE(plane == 0 || (dtype == RC_BF16 && (heads * ch) % 16 == 0), "rc_gma_kv_planar: bf16 with whole 16-channel segments only");
     RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_gma_kv: bad dtype");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_qkvp) % 16 == 0, "rc_gma_kv: misaligned tensor");
     const int U = dtype == RC_F32 ? 4 : 8;
     RC_REQUIRE(batch >= 1 && batch <= 65535 && n_tok >= 1 && heads >= 1 && ch >= 1 && ch <= 32 && heads * ch * ch <= 256 * 16 && heads * ch <= kGThreads /* one thread owns Z[c] */ &&
                (heads * ch) % U == 0 && (heads * ch) / U <= kGThreads, "rc_gma_kv: unsupported head geometry");

@@ -515,6 +515,7 @@ int rc_chain_pack_bias(const float* b, int cout, float* dst) {
 int rc_gma_ln_qkv(const void* d_x, void* d_qkv, long long tokens, const void* d_wpacked, const float* d_bias_packed,
                   const float* d_ln_gamma, const float* d_ln_beta, float eps, void* stream) {
     RC_REQUIRE(d_x && d_qkv && d_wpacked && d_ln_gamma && d_ln_beta, "rc_gma_ln_qkv: null pointer");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && reinterpret_cast<uintptr_t>(d_qkv) % 16 == 0 && reinterpret_cast<uintptr_t>(d_wpacked) % 16 == 0, "rc_gma_ln_qkv: misaligned tensor");
     RC_REQUIRE(tokens >= 1, "rc_gma_ln_qkv: no tokens");
     constexpr int MT = n_mtiles(3 * kC);
     const size_t lds = (size_t)MT * tile_bytes(kC) + 4 * (MT * 16 + 2 * kC);
@@ -532,6 +533,8 @@ int rc_gma_tail(const void* d_qkvp, const void* d_convv, const void* d_loc, cons
                 const void* d_w_out, const float* d_b_out, int cout, void* d_out, void* stream) {
     RC_REQUIRE(d_qkvp && d_convv && d_loc && d_x && d_ktv && d_ktv_frags && d_w_proj && d_b_proj && d_ln_gamma && d_ln_beta && d_w_fc1 &&
                d_b_fc1 && d_w_fc2 && d_b_fc2 && d_out, "rc_gma_tail: null pointer");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_qkvp) % 16 == 0 && reinterpret_cast<uintptr_t>(d_convv) % 16 == 0 && reinterpret_cast<uintptr_t>(d_loc) % 16 == 0 && reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && reinterpret_cast<uintptr_t>(d_ktv_frags) % 16 == 0 && reinterpret_cast<uintptr_t>(d_w_proj) % 16 == 0 && reinterpret_cast<uintptr_t>(d_w_fc1) % 16 == 0 && reinterpret_cast<uintptr_t>(d_w_fc2) % 16 == 0 && reinterpret_cast<uintptr_t>(d_res) % 16 == 0 && reinterpret_cast<uintptr_t>(d_w_out) % 16 == 0 && reinterpret_cast<uintptr_t>(d_out) % 16 == 0,
+               "rc_gma_tail: misaligned tensor");
     RC_REQUIRE(batch >= 1 && n_tok >= 1, "rc_gma_tail: bad shape");
     RC_REQUIRE(cout == 0 || cout == 192, "rc_gma_tail: the output conv is built for 0 (none) or 192 channels");
     if (cout) RC_REQUIRE(d_res && d_w_out && d_b_out, "rc_gma_tail: output conv needs residual, weights and bias");
@@ -580,8 +583,12 @@ constexpr int AG_LDS = (AG_TH + 6) * ((AG_TW + 6) * AG_PS + AG_RPAD);
 
 // float max through the integer atomics (any finite / -inf start value): non-negative floats order like ints, negative ones like
 // reversed unsigneds.  A maximum does not depend on the order of its operands, so the result is deterministic.
+// The branch is on the SIGN BIT, not on v >= 0.f: -0.0f (what Hardswish returns for every x <= -3) compares >= 0 but its pattern as an int is
+// INT_MIN, which never wins a signed maximum -- a channel of -0.0 kept the -inf seed (and rc_gma_kv_mfma then formed exp(k + inf)).  As an
+// unsigned, 0x80000000 is below every negative float and above every non-negative one, so on the unsigned-minimum side -0.0 orders as the
+// zero it is: above all negatives, never replacing a positive value or +0.0.
 __device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
-    if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
+    if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
     else atomicMin(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
 }
 
@@ -867,6 +874,7 @@ extern "C" int rc_gma_aggregate(const void* d_qkv, void* d_qkvp, void* d_loc, in
     using namespace rc::gf;
     RC_REQUIRE(d_qkv && d_qkvp && d_loc && d_dw3 && d_dw5 && d_dw7 && d_dwl && d_pw && d_pwl && d_bn_scale && d_bn_shift && d_ln_g && d_ln_b,
                "rc_gma_aggregate: null pointer");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_qkv) % 16 == 0 && reinterpret_cast<uintptr_t>(d_qkvp) % 16 == 0 && reinterpret_cast<uintptr_t>(d_loc) % 16 == 0, "rc_gma_aggregate: misaligned tensor");
     RC_REQUIRE(batch >= 1 && H >= 1 && W >= 1, "rc_gma_aggregate: bad shape");
     AggArgs a;
     a.qkv = static_cast<const bf16_t*>(d_qkv); a.qkvp = static_cast<bf16_t*>(d_qkvp); a.loc = static_cast<bf16_t*>(d_loc);
@@ -888,6 +896,7 @@ extern "C" int rc_gma_crpe(const void* d_qkvp, void* d_convv, int batch, int H, 
     using namespace rc;
     using namespace rc::gf;
     RC_REQUIRE(d_qkvp && d_convv && d_taps0 && d_taps1 && d_taps2 && d_taps3 && d_bias, "rc_gma_crpe: null pointer");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_qkvp) % 16 == 0 && reinterpret_cast<uintptr_t>(d_convv) % 16 == 0, "rc_gma_crpe: misaligned tensor");
     RC_REQUIRE(batch >= 1 && H >= 1 && W >= 1, "rc_gma_crpe: bad shape");
     CrpeArgs a;
     a.qkvp = static_cast<const bf16_t*>(d_qkvp); a.convv = static_cast<bf16_t*>(d_convv);
@@ -1303,6 +1312,7 @@ extern "C" int rc_gma_qkv_aggregate(const void* d_x, const void* d_wq_natural, c
     using namespace rc::gf;
     RC_REQUIRE(d_x && d_wq_natural && d_ln1_g && d_ln1_b && d_qkvp && d_loc && d_toeplitz && d_pw && d_pwl && d_bn_scale && d_bn_shift && d_ln_g && d_ln_b,
                "rc_gma_qkv_aggregate: null pointer");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && reinterpret_cast<uintptr_t>(d_wq_natural) % 16 == 0 && reinterpret_cast<uintptr_t>(d_qkvp) % 16 == 0 && reinterpret_cast<uintptr_t>(d_loc) % 16 == 0 && reinterpret_cast<uintptr_t>(d_toeplitz) % 16 == 0, "rc_gma_qkv_aggregate: misaligned tensor");
     RC_REQUIRE(batch >= 1 && H >= 1 && W >= 1, "rc_gma_qkv_aggregate: bad shape");
     QaArgs a;
     a.x = static_cast<const bf16_t*>(d_x); a.qkvp = static_cast<bf16_t*>(d_qkvp); a.loc = static_cast<bf16_t*>(d_loc); a.kmax = d_kmax;
@@ -1577,6 +1587,8 @@ extern "C" int rc_gma_in_cpe(const void* d_d1, const void* d_w_in_natural, const
     using namespace rc;
     using namespace rc::gf;
     RC_REQUIRE(d_d1 && d_w_in_natural && d_toeplitz3 && d_x, "rc_gma_in_cpe: null pointer");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_d1) % 16 == 0 && reinterpret_cast<uintptr_t>(d_w_in_natural) % 16 == 0 && reinterpret_cast<uintptr_t>(d_toeplitz3) % 16 == 0 &&
+               reinterpret_cast<uintptr_t>(d_x) % 16 == 0, "rc_gma_in_cpe: misaligned tensor");
     RC_REQUIRE(batch >= 1 && H >= 1 && W >= 1, "rc_gma_in_cpe: bad shape");
     RC_REQUIRE((long long)H * W * GI_CIN * 2 < (1ll << 31), "rc_gma_in_cpe: a 192-channel image must stay below 2 GiB (32-bit buffer offsets)");
     GiArgs a;
@@ -2143,6 +2155,7 @@ extern "C" int rc_gma_kv_mfma(const void* d_qkvp, int batch, int n_tok, float sc
     using namespace rc;
     using namespace rc::gf;
     RC_REQUIRE(d_qkvp && d_kmax && d_scratch && d_ktv, "rc_gma_kv_mfma: null pointer");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_qkvp) % 16 == 0, "rc_gma_kv_mfma: misaligned tensor");
     RC_REQUIRE(batch >= 1 && batch <= 65535 && n_tok >= 1, "rc_gma_kv_mfma: bad shape");
     const int nblk = rc_gma_kv_mfma_blocks(n_tok);
     const int L = ((n_tok + nblk - 1) / nblk + KV_TILE - 1) / KV_TILE * KV_TILE;

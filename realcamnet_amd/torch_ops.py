@@ -48,14 +48,28 @@ def _none(x: Tensor) -> Tensor:
     return x.new_empty((0,))
 
 
-def define(schema: str, alloc, launch):
+def require_acts(op: str, dtype, *tensors) -> None:
+    """The GroupMix kernels read their activation tensors as dense arrays of ONE storage dtype (the fused dim-80 kernels: bf16, their C ABI has no dtype argument).
+    Refuse, before anything is allocated or launched, a tensor of another dtype (it would be read as raw bits) or a strided view (it would be read as if dense)."""
+    for t in tensors:
+        if t is None:
+            continue
+        if t.dtype != dtype:
+            raise TypeError(f"realcam::{op}: activation tensor of dtype {t.dtype}, expected {dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"realcam::{op}: non-contiguous activation tensor (shape {tuple(t.shape)}, strides {t.stride()})")
+
+
+def define(schema: str, alloc, launch, acts=None):
     """Register `realcam::<schema>`: alloc(*args) -> outputs (shared by the CUDA and the fake kernel), launch(outs, *args)
-    enqueues the C-ABI call."""
+    enqueues the C-ABI call.  acts(*args) -> (dtype, activation tensors ...): checked by require_acts before the CUDA kernel allocates."""
     name = schema.split("(")[0]
     SCHEMAS[name] = schema
     _LIB.define(schema)
 
     def cuda_impl(*args):
+        if acts is not None:
+            require_acts(name, *acts(*args))
         outs = alloc(*args)
         launch(outs, *args)
         return outs
@@ -606,12 +620,12 @@ def _dw_launch(y, x, x_c0, y_tail, y_c0, n_ch, ksize, wT, bias, n_rep, x_rep, y_
 
 define("dwconv2d(Tensor x, int x_c0, int[] y_tail, int y_c0, int n_ch, int ksize, Tensor wT, Tensor? bias, int n_rep, int x_rep, int y_rep, "
        "int w_rep, bool add_identity, Tensor? kvec) -> Tensor",
-       lambda x, x_c0, y_tail, *a: x.new_empty((*x.shape[:3], *y_tail)), _dw_launch)
+       lambda x, x_c0, y_tail, *a: x.new_empty((*x.shape[:3], *y_tail)), _dw_launch, acts=lambda x, *a: (x.dtype, x))
 
 define("layernorm(Tensor x, Tensor gamma, Tensor beta, float eps) -> Tensor",
        lambda x, g, b, eps: torch.empty_like(x),
        lambda out, x, g, b, eps: check(lib().rc_layernorm(x.data_ptr(), out.data_ptr(), _dt(x), x.numel() // x.shape[-1], x.shape[-1], g.data_ptr(),
-                                                          b.data_ptr(), float(eps), _stream()), "rc_layernorm"))
+                                                          b.data_ptr(), float(eps), _stream()), "rc_layernorm"), acts=lambda x, *a: (x.dtype, x))
 
 
 def _gpw_launch(outs, qkv, dwc, pw, scale, shift, pwl, ln_g, ln_b):
@@ -626,7 +640,7 @@ def _gpw_launch(outs, qkv, dwc, pw, scale, shift, pwl, ln_g, ln_b):
 
 define("gma_pointwise(Tensor qkv, Tensor dwc, Tensor pw, Tensor bn_scale, Tensor bn_shift, Tensor pwl, Tensor ln_g, Tensor ln_b) -> (Tensor, Tensor)",
        lambda qkv, dwc, *a: (qkv.new_empty((*qkv.shape[:3], 3, 4 * (qkv.shape[3] // 15))), qkv.new_empty((*qkv.shape[:3], qkv.shape[3] // 15))),
-       _gpw_launch)
+       _gpw_launch, acts=lambda qkv, dwc, *a: (qkv.dtype, qkv, dwc))
 
 
 def _planar(qkvp) -> bool:
@@ -646,13 +660,13 @@ def _gkv_launch(ktv, qkvp, heads, ch, scale):
 
 define("gma_kv(Tensor qkvp, int heads, int ch, float scale) -> Tensor",
        lambda qkvp, heads, ch, scale: qkvp.new_empty((qkvp.shape[1] if _planar(qkvp) else qkvp.shape[0], heads, ch, ch), dtype=torch.float32),
-       _gkv_launch)
+       _gkv_launch, acts=lambda qkvp, *a: (qkvp.dtype, qkvp))
 
 define("gma_apply(Tensor qkvp, Tensor convv, Tensor loc, Tensor ktv, int heads, int ch, int seg) -> Tensor",
        lambda qkvp, convv, loc, ktv, heads, ch, seg: qkvp.new_empty((*qkvp.shape[:3], heads * ch + seg)),
        lambda out, qkvp, convv, loc, ktv, heads, ch, seg: check(
            lib().rc_gma_apply(qkvp.data_ptr(), convv.data_ptr(), loc.data_ptr(), ktv.data_ptr(), out.data_ptr(), _dt(qkvp), qkvp.shape[0],
-                              qkvp.shape[1] * qkvp.shape[2], heads, ch, seg, _stream()), "rc_gma_apply"))
+                              qkvp.shape[1] * qkvp.shape[2], heads, ch, seg, _stream()), "rc_gma_apply"), acts=lambda qkvp, convv, loc, *a: (qkvp.dtype, qkvp, convv, loc))
 
 
 # ---- a17: window attention ------------------------------------------------------------------------------------------------------
@@ -697,7 +711,7 @@ define("gma_ln_qkv(Tensor x, Tensor wpacked, Tensor bias_packed, Tensor ln_gamma
        lambda x, wp, bp, g, b, eps: x.new_empty((15, *x.shape[:-1], 16)),         # planar by 16-channel segment
        lambda out, x, wp, bp, g, b, eps: check(lib().rc_gma_ln_qkv(x.data_ptr(), out.data_ptr(), x.numel() // x.shape[-1], wp.data_ptr(),
                                                                    bp.data_ptr(), g.data_ptr(), b.data_ptr(), float(eps), _stream()),
-                                               "rc_gma_ln_qkv"))
+                                               "rc_gma_ln_qkv"), acts=lambda x, *a: (torch.bfloat16, x))
 
 
 def _tail_alloc(qkvp, convv, loc, x, ktv, w_proj, b_proj, ln_g, ln_b, eps, w_fc1, b_fc1, w_fc2, b_fc2, res, w_out, b_out):
@@ -716,7 +730,7 @@ def _tail_launch(out, qkvp, convv, loc, x, ktv, w_proj, b_proj, ln_g, ln_b, eps,
 
 define("gma_tail(Tensor qkvp, Tensor convv, Tensor loc, Tensor x, Tensor ktv, Tensor w_proj, Tensor b_proj, Tensor ln_gamma, Tensor ln_beta, "
        "float eps, Tensor w_fc1, Tensor b_fc1, Tensor w_fc2, Tensor b_fc2, Tensor? res, Tensor? w_out, Tensor? b_out) -> Tensor",
-       _tail_alloc, _tail_launch)
+       _tail_alloc, _tail_launch, acts=lambda qkvp, convv, loc, x, *a: (torch.bfloat16, qkvp, convv, loc, x, a[10]))
 
 
 define("gma_aggregate(Tensor qkv, Tensor dw3, Tensor dw5, Tensor dw7, Tensor dwl, Tensor pw, Tensor pwl, Tensor bn_scale, Tensor bn_shift, "
@@ -726,7 +740,7 @@ define("gma_aggregate(Tensor qkv, Tensor dw3, Tensor dw5, Tensor dw7, Tensor dwl
        lambda outs, qkv, dw3, dw5, dw7, dwl, pw, pwl, sc, sh, lg, lb: check(
            lib().rc_gma_aggregate(qkv.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), qkv.shape[1], qkv.shape[2], qkv.shape[3], dw3.data_ptr(),
                                   dw5.data_ptr(), dw7.data_ptr(), dwl.data_ptr(), pw.data_ptr(), pwl.data_ptr(), sc.data_ptr(), sh.data_ptr(),
-                                  lg.data_ptr(), lb.data_ptr(), outs[2].data_ptr(), _stream()), "rc_gma_aggregate"))
+                                  lg.data_ptr(), lb.data_ptr(), outs[2].data_ptr(), _stream()), "rc_gma_aggregate"), acts=lambda qkv, *a: (torch.bfloat16, qkv))
 
 
 def _cpackn_launch(wp, weight):
@@ -763,7 +777,7 @@ define("dw_toeplitz_pack(Tensor taps, int ksize) -> Tensor",                    
 define("gma_in_cpe(Tensor d1, Tensor w_in_natural, Tensor? b_in, Tensor toeplitz3, Tensor? b_cpe) -> Tensor",      # (B, H, W, 192) -> (B, H, W, 80)
        lambda d1, *a: d1.new_empty((*d1.shape[:3], 80)),
        lambda out, d1, w, bi, toep, bc: check(lib().rc_gma_in_cpe(d1.data_ptr(), w.data_ptr(), _p(bi), toep.data_ptr(), _p(bc), out.data_ptr(), d1.shape[0], d1.shape[1],
-                                                                  d1.shape[2], _stream()), "rc_gma_in_cpe"))
+                                                                  d1.shape[2], _stream()), "rc_gma_in_cpe"), acts=lambda d1, *a: (torch.bfloat16, d1))
 
 define("gma_qkv_aggregate(Tensor x, Tensor wq_natural, Tensor? bq, Tensor ln1_gamma, Tensor ln1_beta, float eps, Tensor toeplitz, "
        "Tensor pw, Tensor pwl, Tensor bn_scale, Tensor bn_shift, Tensor ln_gamma, Tensor ln_beta) -> (Tensor, Tensor, Tensor)",
@@ -773,7 +787,7 @@ define("gma_qkv_aggregate(Tensor x, Tensor wq_natural, Tensor? bq, Tensor ln1_ga
            lib().rc_gma_qkv_aggregate(x.data_ptr(), wq.data_ptr(), _p(bq), g1.data_ptr(), b1.data_ptr(), float(eps), outs[0].data_ptr(),
                                       outs[1].data_ptr(), x.shape[0], x.shape[1], x.shape[2], toep.data_ptr(), pw.data_ptr(), pwl.data_ptr(),
                                       sc.data_ptr(), sh.data_ptr(), lg.data_ptr(), lb.data_ptr(), outs[2].data_ptr(), _stream()),
-           "rc_gma_qkv_aggregate"))
+           "rc_gma_qkv_aggregate"), acts=lambda x, *a: (torch.bfloat16, x))
 
 
 def _kvm_launch(ktv, qkvp, kmax, scale):
@@ -783,13 +797,13 @@ def _kvm_launch(ktv, qkvp, kmax, scale):
 
 
 define("gma_kv_mfma(Tensor qkvp, Tensor kmax, float scale) -> Tensor",
-       lambda qkvp, kmax, scale: qkvp.new_empty((qkvp.shape[1], 8, 8, 8), dtype=torch.float32), _kvm_launch)
+       lambda qkvp, kmax, scale: qkvp.new_empty((qkvp.shape[1], 8, 8, 8), dtype=torch.float32), _kvm_launch, acts=lambda qkvp, *a: (torch.bfloat16, qkvp))
 
 define("gma_crpe(Tensor qkvp, Tensor taps0, Tensor taps1, Tensor taps2, Tensor taps3, Tensor bias) -> Tensor",
        lambda qkvp, *a: qkvp.new_empty((4, *qkvp.shape[1:4], 16)),                 # segment-planar in and out
        lambda out, qkvp, t0, t1, t2, t3, bias: check(
            lib().rc_gma_crpe(qkvp.data_ptr(), out.data_ptr(), qkvp.shape[1], qkvp.shape[2], qkvp.shape[3], t0.data_ptr(), t1.data_ptr(),
-                             t2.data_ptr(), t3.data_ptr(), bias.data_ptr(), _stream()), "rc_gma_crpe"))
+                             t2.data_ptr(), t3.data_ptr(), bias.data_ptr(), _stream()), "rc_gma_crpe"), acts=lambda qkvp, *a: (torch.bfloat16, qkvp))
 
 
 # ---- f3: entropy coding (csrc/rans.hip) ------------------------------------------------------------------------------------------------
