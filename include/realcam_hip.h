@@ -178,6 +178,36 @@ size_t rc_yuv_frame_bytes(const rc_out_format* fmt, int h, int w);
  * Odd h / w, a pitch below the row's bytes, overlapping planes, a misaligned d_dst: RC_ERR_INVALID before any launch. */
 int rc_yuv_encode(const void* d_src, int src_dtype, const rc_out_format* fmt, void* d_dst, int batch, int H, int W, int h, int w, void* stream);
 
+/* ---- scaled and cropped renditions (ABI 15, additive): a window of the same planar result, downscaled, between the tail and the encoders --
+ * One network pass, any number of outputs: each is a window (ROI) of the cropped result, a size and -- through rc_rgb_encode /
+ * rc_yuv_encode on what this stage returns -- a format.  The stage is separable and only ever downscales: per axis 1 <= ROI / out <= 8. */
+typedef enum rc_resize_filter {
+    RC_FILTER_AREA = 0,      /* fractional coverage of the output pixel's footprint (F.interpolate mode="area" at integer ratios) */
+    RC_FILTER_BILINEAR = 1   /* the antialiased triangle of F.interpolate(mode="bilinear", antialias=True, align_corners=False) */
+} rc_resize_filter;
+#define RC_RESIZE_MAX_TAPS 20   /* the longest weight list of an axis (bilinear at ratio 7.5 needs 16) */
+#define RC_RESIZE_MAX_RATIO 8
+
+/* HOST function: the tables of ONE axis.  ROI length n at offset off in the source, output length m (m <= n <= 8 m), scale s = n / m.
+ * Everything in double, no contraction; for output index i the source indices k (inside the ROI, 0 <= k < n) and raw weights are
+ *   AREA      k = floor(i s) .. min(n, ceil((i + 1) s)) - 1;              max(0, min(k + 1, (i + 1) s) - max(k, i s))
+ *   BILINEAR  c = s (i + 0.5); k = max(0, int(c - s + 0.5)) .. min(n, int(c + s + 0.5)) - 1;   max(0, 1 - |(k - c + 0.5) / s|)
+ * Zero weights at either end are dropped, the rest are summed in list order and divided by that sum (double), then rounded to fp32 once.
+ * first[i] = off + the first k kept.  weights: m * RC_RESIZE_MAX_TAPS floats of room; written as [m][*taps], each list padded with zeros
+ * to *taps, the axis's longest list.  A list that would exceed RC_RESIZE_MAX_TAPS, m > n (upscaling) or n > 8 m: RC_ERR_INVALID. */
+int rc_resize_taps(int filter, int n, int off, int m, int* first, float* weights, int* taps);
+
+/* src (B,3,H,W) RC_F32 / RC_BF16 / RC_F16 planar; dst (B,3,h,w) RC_F32, or src_dtype (rounded to nearest even once, at the store).
+ * d_first_y / d_wy ([h] / [h][taps_y]) and d_first_x / d_wx ([w] / [w][taps_x]): DEVICE copies of rc_resize_taps' tables, first indices
+ * into the source plane.  fp32, every product and every sum rounded on its own, in list order (no fused multiply-add):
+ *   t[y][j] = (..((wx[j][0] src[y][fx[j]]) + (wx[j][1] src[y][fx[j] + 1])) + ..)      for each source row y the output needs
+ *   o[i][j] = (..((wy[i][0] t[fy[i]][j]) + (wy[i][1] t[fy[i] + 1][j])) + ..)
+ * over the weights of a list that are not zero (the padding is skipped, never multiplied).  No clamp, no NaN rule: the weights are
+ * non-negative and sum to 1.  One launch; taps_y, taps_x in 1 .. RC_RESIZE_MAX_TAPS; a list's rows must lie within 8 x 8 + 20 source
+ * rows of the first row of its tile of 8 output rows (rc_resize_taps' tables do). */
+int rc_resize(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, int batch, int H, int W, int h, int w, const int* d_first_y,
+              const float* d_wy, int taps_y, const int* d_first_x, const float* d_wx, int taps_x, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

@@ -24,6 +24,8 @@ RC_YUV_NV12, RC_YUV_P010, RC_YUV_I420 = 0, 1, 2
 RC_MATRIX_BT601, RC_MATRIX_BT709, RC_MATRIX_BT2020 = 0, 1, 2
 RC_RANGE_LIMITED, RC_RANGE_FULL = 0, 1
 RC_SITING_LEFT, RC_SITING_CENTER = 0, 1
+RC_FILTER_AREA, RC_FILTER_BILINEAR = 0, 1
+RC_RESIZE_MAX_TAPS, RC_RESIZE_MAX_RATIO = 20, 8
 
 
 class ConvDesc(C.Structure):
@@ -98,6 +100,8 @@ _SIGS = {
     "rc_out_format_size": (_SZ, []),
     "rc_yuv_frame_bytes": (_SZ, [C.POINTER(OutFormatDesc), _I, _I]),
     "rc_yuv_encode": (C.c_int, [_P, _I, C.POINTER(OutFormatDesc), _P, _I, _I, _I, _I, _I, _P]),
+    "rc_resize_taps": (C.c_int, [_I, _I, _I, _I, _P, _P, C.POINTER(C.c_int)]),
+    "rc_resize": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

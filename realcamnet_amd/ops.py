@@ -535,6 +535,45 @@ def yuv_encode(y: torch.Tensor, fmt, crop_hw: Optional[Tuple[int, int]] = None):
     return YuvFrames(buf, tuple(views))
 
 
+_RESIZE_TABLES = {}      # (Resize, frame h, frame w, device) -> the four device tables of rc_resize_taps
+
+
+def resize_tables(rs, h: int, w: int, device):
+    """first_y (h',) int32, wy (h',Ty) fp32, first_x (w',), wx (w',Tx) on `device` for the Resize `rs` of an (h, w) frame: built by
+    rc_resize_taps and copied to the device once per (geometry, device), then kept -- a warmed-up ops.resize makes no host-to-device copy."""
+    device = torch.device(device)
+    key = (rs, int(h), int(w), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    hit = _RESIZE_TABLES.get(key)
+    if hit is None:
+        (fy, wy, _), (fx, wx, _) = rs.taps(int(h), int(w))
+        hit = _RESIZE_TABLES[key] = tuple(torch.from_numpy(a).to(device) for a in (fy, wy, fx, wx))
+    return hit
+
+
+def resize(y: torch.Tensor, rs, crop_hw: Optional[Tuple[int, int]] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Planar result (B,3,H,W), cropped to crop_hw, -> (B,3,*rs.size): the Resize's window of it, downscaled by its filter (rc_resize; the
+    arithmetic is fixed in include/realcam_hip.h).  out_dtype: torch.float32, or y's dtype (rounded to nearest even once).  One launch."""
+    from .resize import MAX_TAPS, Resize
+    if not isinstance(rs, Resize):
+        raise TypeError(f"resize: rs must be a Resize, got {type(rs).__name__}")
+    y = _req(y, "resize input")
+    if y.dim() != 4 or y.shape[1] != 3:
+        raise ValueError(f"resize: expected (B,3,H,W), got {tuple(y.shape)}")
+    _dt(y)
+    if out_dtype not in (torch.float32, y.dtype):
+        raise ValueError(f"resize: out_dtype must be torch.float32 or the source's {y.dtype}, got {out_dtype}")
+    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
+    if h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]:
+        raise ValueError(f"resize: crop {(h, w)} exceeds the source {tuple(y.shape[2:])}")
+    rs.window(h, w)
+    if isinstance(y, FakeTensor):                              # a trace: shapes only, nothing is built, copied or kept
+        tables = (y.new_empty((rs.size[0],), dtype=torch.int32), y.new_empty((rs.size[0], MAX_TAPS), dtype=torch.float32),
+                  y.new_empty((rs.size[1],), dtype=torch.int32), y.new_empty((rs.size[1], MAX_TAPS), dtype=torch.float32))
+    else:
+        tables = resize_tables(rs, h, w, y.device)
+    return _R.resize(y, *tables, out_dtype)
+
+
 def make_coord(b: int, h: int, w: int, device=None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """Normalised pixel-coordinate map (B,2,h,w) in [-1,1], channel 0 = y, channel 1 = x: the lens-shading branch's input x[2]
     (upstream never published its generator; build convention).  Plain tensor construction, no kernel."""

@@ -395,15 +395,17 @@ class raw_compression_tcm_final(nn.Module):
         return self._forward_nhwc(ops.to_nhwc(raw, dtype=dt), cond, ops.to_nhwc(coord, dtype=dt))
 
     def forward_mosaic(self, mosaic, cond, coord, pad_to: int = 128, black_level: float = 0.0, white_level: float = 1.0, cond_hw=(256, 256),
-                       raw_format=None, out_format=None):
+                       raw_format=None, out_format=None, outputs=None):
         """Bayer mosaic (B,1,2h,2w), cond (B,4,hc,wc), coord (B,2,h,w) -> the same dict as forward().  The packed RAW and coord are
         zero-padded bottom/right to a multiple of `pad_to` (128: window 4 at 1/32 of the packed size), x_hat
         is NOT cropped (it is the decoder's output for the padded frame).  raw_format: the sensor frame's layout (see
-        LiteISP._DwtUNet.forward_mosaic); out_format must stay None: x_hat is the padded decoder output, not an image to encode."""
+        LiteISP._DwtUNet.forward_mosaic); out_format and outputs must stay None: x_hat is the padded decoder output, not an image to encode."""
         if self.training:
             raise RuntimeError("realcamnet_amd is an inference path: call .eval() first")
         if out_format is not None:
             raise ValueError("raw_compression_tcm_final.forward_mosaic returns the codec's dict: out_format is not supported")
+        if outputs is not None:
+            raise ValueError("raw_compression_tcm_final.forward_mosaic returns the codec's dict: outputs is not supported")
         dt = self._act_dtype()
         from .LiteISP import _ingest, _mosaic_hw
         mh, mw = _mosaic_hw(mosaic, raw_format)

@@ -1,0 +1,123 @@
+"""Scaled and cropped renditions of forward_mosaic's result: the `Resize` of an `Output` (include/realcam_hip.h, rc_resize_taps / rc_resize).
+
+Pure Python: validation raises ValueError / TypeError and never touches the GPU or the library; only `taps()` calls the library's host
+function rc_resize_taps, which holds the one copy of the filter arithmetic.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional, Tuple
+
+from . import _lib
+from .out_format import OutFormat
+
+FILTERS = {"area": _lib.RC_FILTER_AREA, "bilinear": _lib.RC_FILTER_BILINEAR}
+MAX_TAPS = _lib.RC_RESIZE_MAX_TAPS
+MAX_RATIO = _lib.RC_RESIZE_MAX_RATIO
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _check_axis(what: str, n: int, m: int) -> None:
+    if m > n:
+        raise ValueError(f"Resize: {what} {n} -> {m} is an upscale; the stage downscales or keeps the size (1 <= ratio <= {MAX_RATIO})")
+    if n > MAX_RATIO * m:
+        raise ValueError(f"Resize: {what} {n} -> {m} is a ratio of {n / m:.3g}, above the limit of {MAX_RATIO}")
+
+
+def axis_taps(n: int, off: int, m: int, filter: str = "area"):
+    """The tables of one axis (rc_resize_taps): ROI length n at offset off, output length m -> (first int32 [m], weights float32 [m, T], T)
+    as NumPy arrays, T being the axis's longest list; shorter lists are padded with zeros."""
+    import numpy as np
+    if filter not in FILTERS:
+        raise ValueError(f"Resize.filter must be one of {sorted(FILTERS)}, got {filter!r}")
+    if not all(_is_int(v) for v in (n, off, m)) or n < 1 or m < 1 or off < 0:
+        raise ValueError(f"axis_taps: bad lengths (n, off, m) = {(n, off, m)!r}")
+    _check_axis("axis", n, m)
+    first = np.empty(m, dtype=np.int32)
+    weights = np.empty(m * MAX_TAPS, dtype=np.float32)
+    t = C.c_int(0)
+    lib = _lib.load()
+    if lib.rc_resize_taps(FILTERS[filter], n, off, m, first.ctypes.data, weights.ctypes.data, C.byref(t)) != 0:
+        raise ValueError(f"rc_resize_taps({filter!r}, n={n}, off={off}, m={m}): {lib.rc_last_error().decode(errors='replace')}")
+    return first, weights[:m * t.value].reshape(m, t.value).copy(), t.value
+
+
+@dataclass(frozen=True)
+class Resize:
+    """One rendition's geometry: a window of the cropped network result, downscaled.
+
+    size    (h, w) of the output.
+    roi     (y0, x0, rh, rw) in pixels of the cropped network result; None: all of it.
+    filter  "area" (fractional coverage: box averaging at integer ratios) or "bilinear" (the antialiased triangle of
+            F.interpolate(mode="bilinear", antialias=True)).
+    Per axis 1 <= roi / size <= 8: the stage downscales or keeps the size.
+    """
+
+    size: Tuple[int, int]
+    roi: Optional[Tuple[int, int, int, int]] = None
+    filter: str = "area"
+
+    def __post_init__(self):
+        sz = self.size
+        if not isinstance(sz, (tuple, list)) or len(sz) != 2 or not all(_is_int(v) for v in sz) or min(sz) < 1:
+            raise ValueError(f"Resize.size must be (h, w) with positive integers, got {sz!r}")
+        object.__setattr__(self, "size", (sz[0], sz[1]))
+        if not isinstance(self.filter, str) or self.filter not in FILTERS:
+            raise ValueError(f"Resize.filter must be one of {sorted(FILTERS)}, got {self.filter!r}")
+        r = self.roi
+        if r is not None:
+            if not isinstance(r, (tuple, list)) or len(r) != 4 or not all(_is_int(v) for v in r) or r[0] < 0 or r[1] < 0 or r[2] < 1 or r[3] < 1:
+                raise ValueError(f"Resize.roi must be (y0, x0, rh, rw) with y0, x0 >= 0 and rh, rw >= 1, got {r!r}")
+            object.__setattr__(self, "roi", tuple(r))
+            _check_axis("height", r[2], sz[0])
+            _check_axis("width", r[3], sz[1])
+
+    def window(self, h: int, w: int) -> Tuple[int, int, int, int]:
+        """The ROI (y0, x0, rh, rw) inside an (h, w) frame, checked: inside the frame, and each axis's ratio within 1 .. 8."""
+        y0, x0, rh, rw = self.roi if self.roi is not None else (0, 0, h, w)
+        if y0 + rh > h or x0 + rw > w:
+            raise ValueError(f"Resize.roi {(y0, x0, rh, rw)} lies outside the ({h}, {w}) frame")
+        _check_axis("height", rh, self.size[0])
+        _check_axis("width", rw, self.size[1])
+        return y0, x0, rh, rw
+
+    def taps(self, h: int, w: int):
+        """((first_y, wy, Ty), (first_x, wx, Tx)) for an (h, w) frame: axis_taps of the two axes, first indices into the frame."""
+        y0, x0, rh, rw = self.window(h, w)
+        return axis_taps(rh, y0, self.size[0], self.filter), axis_taps(rw, x0, self.size[1], self.filter)
+
+
+@dataclass(frozen=True)
+class Output:
+    """One entry of forward_mosaic(outputs=[...]): an optional Resize of the float result, then its format.
+
+    format  None (the planar float tensor), "rgb8" / "rgb16" (interleaved uint8 / uint16) or an OutFormat (a YuvFrames).
+    resize  None (the result's own size) or a Resize.
+    """
+
+    format: object = None
+    resize: Optional[Resize] = None
+
+    def __post_init__(self):
+        f = self.format
+        if f is not None and not isinstance(f, (str, OutFormat)):
+            raise TypeError(f"Output.format must be None, 'rgb8', 'rgb16' or an OutFormat, got {type(f).__name__}")
+        if isinstance(f, str) and f not in ("rgb8", "rgb16"):
+            raise ValueError(f"Output.format must be None, 'rgb8', 'rgb16' or an OutFormat, got {f!r}")
+        if self.resize is not None and not isinstance(self.resize, Resize):
+            raise TypeError(f"Output.resize must be None or a Resize, got {type(self.resize).__name__}")
+        if isinstance(f, OutFormat) and self.resize is not None and (self.resize.size[0] % 2 or self.resize.size[1] % 2):
+            raise ValueError(f"Output: 4:2:0 ({f.layout}) needs an even height and width, Resize.size is {self.resize.size}")
+
+    def plan(self, h: int, w: int) -> Tuple[int, int]:
+        """The (h, w) this output has for an (h, w) result; every refusal that depends on the frame is raised here, before any launch."""
+        if self.resize is not None:
+            self.resize.window(h, w)
+            h, w = self.resize.size
+        if isinstance(self.format, OutFormat):
+            self.format.plane_layout(h, w)
+        return h, w

@@ -166,6 +166,19 @@ def _yuv_launch(out, y, layout, matrix, range_, siting, pitch, rows, h, w):
 # matrix / range / siting: the rc_yuv_* enums; pitch in bytes, rows = allocated Y rows
 define("yuv_encode(Tensor y, int layout, int matrix, int vrange, int siting, int pitch, int rows, int h, int w) -> Tensor", _yuv_alloc, _yuv_launch)
 
+def _resize_launch(out, y, first_y, wy, first_x, wx, dtype):
+    for name, t, dt, n in (("first_y", first_y, torch.int32, out.shape[2]), ("wy", wy, torch.float32, out.shape[2]),
+                           ("first_x", first_x, torch.int32, out.shape[3]), ("wx", wx, torch.float32, out.shape[3])):
+        if t.dtype != dt or t.device != y.device or not t.is_contiguous() or t.shape[0] != n:
+            raise ValueError(f"realcam::resize: table {name} must be a contiguous {dt} tensor of {n} rows on {y.device}")
+    check(lib().rc_resize(y.data_ptr(), _dt(y), out.data_ptr(), _DT[dtype], y.shape[0], y.shape[2], y.shape[3], out.shape[2], out.shape[3],
+                          first_y.data_ptr(), wy.data_ptr(), wy.shape[1], first_x.data_ptr(), wx.data_ptr(), wx.shape[1], _stream()), "rc_resize")
+
+
+# y (B,3,H,W) planar -> (B,3,h,w) of `dtype` (fp32 or y's); the device tables of rc_resize_taps: first_y (h,) int32, wy (h,Ty) fp32, first_x (w,), wx (w,Tx)
+define("resize(Tensor y, Tensor first_y, Tensor wy, Tensor first_x, Tensor wx, ScalarType dtype) -> Tensor",
+       lambda y, first_y, wy, first_x, wx, dtype: y.new_empty((y.shape[0], 3, wy.shape[0], wx.shape[0]), dtype=dtype), _resize_launch)
+
 define("nchw_to_nhwc(Tensor x, ScalarType dtype, int hp, int wp) -> Tensor",
        lambda x, dtype, hp, wp: x.new_empty((x.shape[0], hp, wp, x.shape[1]), dtype=dtype),
        lambda out, x, dtype, hp, wp: check(lib().rc_nchw_to_nhwc(x.data_ptr(), _dt(x), out.data_ptr(), _DT[dtype], x.shape[0], x.shape[1],
