@@ -208,6 +208,29 @@ int rc_resize_taps(int filter, int n, int off, int m, int* first, float* weights
 int rc_resize(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, int batch, int H, int W, int h, int w, const int* d_first_y,
               const float* d_wy, int taps_y, const int* d_first_x, const float* d_wx, int taps_x, void* stream);
 
+/* ---- colour looks (ABI 15, additive): the same planar result through a 3D LUT, between the scaler and the encoders ------------------------
+ * A look is a table of n x n x n nodes (the .cube format's LUT_3D_SIZE n, unit domain), interpolated tetrahedrally. */
+#define RC_LUT3D_MIN_SIZE 2
+#define RC_LUT3D_MAX_SIZE 65
+
+/* src (B,3,H,W) RC_F32 / RC_BF16 / RC_F16 planar R,G,B, cropped to (h,w); dst (B,3,h,w) planar, RC_F32 or src_dtype.
+ * d_lut: DEVICE table of n^3 entries of 4 floats -- R, G, B and one pad float that is ignored -- 16-byte aligned, so one vertex is one
+ * 16-byte load; node (ir, ig, ib) is entry ir + n (ig + n ib): R varies fastest, the order of a .cube file's rows.  L[.] below is an entry.
+ * fp32, every product and every sum rounded on its own (no fused multiply-add):
+ *   1. r,g,b = float(src), NaN -> 0, clamped to [0,1]                                          (step 1 of rc_yuv_encode)
+ *   2. per channel c:  p = c float(n-1);  i = min(int(floor(p)), n-2);  f = p - float(i)       (exact; c = 1 gives i = n-2, f = 1)
+ *   3. the axes ordered by fraction, ties fixed:
+ *        fr >= fg:  fg >= fb: (r,g,b);  else fr >= fb: (r,b,g);  else (b,r,g)
+ *        else:      fb >= fg: (b,g,r);  else fb >= fr: (g,b,r);  else (g,r,b)
+ *      ordered axes a1, a2, a3 with fractions f1 >= f2 >= f3, e_a the unit step along axis a:
+ *        V0 = L[i],  V1 = L[i + e_a1],  V2 = L[i + e_a1 + e_a2],  V3 = L[i + (1,1,1)]
+ *        w0 = 1 - f1,  w1 = f1 - f2,  w2 = f2 - f3,  w3 = f3
+ *   4. per output channel  o = (((w0 V0) + (w1 V1)) + (w2 V2)) + (w3 V3)
+ * No output clamp and no NaN rule: the table is finite, the weights lie in [0,1], and the encoders clamp.  o is stored as fp32, or
+ * rounded to nearest even once into src_dtype.  Step 2 clamps the indices to [0, n-2] after the NaN rule: no input makes the kernel
+ * read outside the table.  One launch.  n outside 2 .. 65, a bad dtype, h > H or w > W: RC_ERR_INVALID before any launch. */
+int rc_lut3d(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, const float* d_lut, int n, int batch, int H, int W, int h, int w, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

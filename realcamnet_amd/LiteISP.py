@@ -316,10 +316,16 @@ def _plan_outputs(outputs, out_format, hw):
 
 def _emit(y, bits, outs):
     """The single result of the out_format route, or the list of renditions of `outs` in the order given: each an optional ops.resize
-    (fp32) of the one float result, then the encoders of _encode."""
+    (fp32) of the one float result, then an optional colour look (ops.lut3d, fp32), then the encoders of _encode."""
     if outs is None:
         return _encode(y, bits)
-    return [_encode(y if o.resize is None else ops.resize(y, o.resize), _out_bits(o.format)) for o in outs]
+    res = []
+    for o in outs:
+        t = y if o.resize is None else ops.resize(y, o.resize)
+        if o.look is not None:
+            t = ops.lut3d(t, o.look)
+        res.append(_encode(t, _out_bits(o.format)))
+    return res
 
 
 class _DwtUNet(nn.Module):
@@ -432,8 +438,9 @@ class _DwtUNet(nn.Module):
         raw_format (a RawFormat): the sensor frame's CFA phase, storage (MIPI RAW10 / RAW12 lines: (B,[1,]2h,line_bytes) uint8) and
         per-position levels.  out_format "rgb8" / "rgb16": the result as interleaved (B,2h,2w,3) uint8 / uint16; an OutFormat: a YuvFrames
         (one NV12 / P010 / I420 encoder surface per frame, and views of its planes).
-        outputs [Output(format, resize), ...] instead of out_format: one network pass, then per Output an optional scaled / cropped
-        rendition (ops.resize, fp32) in its own format; returns the list in the order given."""
+        outputs [Output(format, resize, look), ...] instead of out_format: one network pass, then per Output an optional scaled / cropped
+        rendition (ops.resize, fp32) and an optional colour look (a Lut3D: ops.lut3d, fp32) in its own format; returns the list in the
+        order given."""
         if self.training:
             raise RuntimeError("realcamnet_amd is an inference path: call .eval() first")
         bits = _out_bits(out_format)

@@ -26,6 +26,7 @@ RC_RANGE_LIMITED, RC_RANGE_FULL = 0, 1
 RC_SITING_LEFT, RC_SITING_CENTER = 0, 1
 RC_FILTER_AREA, RC_FILTER_BILINEAR = 0, 1
 RC_RESIZE_MAX_TAPS, RC_RESIZE_MAX_RATIO = 20, 8
+RC_LUT3D_MIN_SIZE, RC_LUT3D_MAX_SIZE = 2, 65
 
 
 class ConvDesc(C.Structure):
@@ -102,6 +103,7 @@ _SIGS = {
     "rc_yuv_encode": (C.c_int, [_P, _I, C.POINTER(OutFormatDesc), _P, _I, _I, _I, _I, _I, _P]),
     "rc_resize_taps": (C.c_int, [_I, _I, _I, _I, _P, _P, C.POINTER(C.c_int)]),
     "rc_resize": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
+    "rc_lut3d": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

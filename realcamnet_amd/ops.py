@@ -574,6 +574,43 @@ def resize(y: torch.Tensor, rs, crop_hw: Optional[Tuple[int, int]] = None, out_d
     return _R.resize(y, *tables, out_dtype)
 
 
+_LUT3D_TABLES = {}       # (Lut3D, device) -> the packed device table of rc_lut3d
+
+
+def lut3d_table(lut, device):
+    """The (N^3, 4) fp32 table of the Lut3D `lut` on `device` (R, G, B and a pad float per node): packed and copied once per (lut, device),
+    then kept -- a warmed-up ops.lut3d makes no host-to-device copy."""
+    device = torch.device(device)
+    key = (lut, device.type, device.index if device.index is not None else torch.cuda.current_device())
+    hit = _LUT3D_TABLES.get(key)
+    if hit is None:
+        hit = _LUT3D_TABLES[key] = torch.from_numpy(lut.packed()).to(device)
+    return hit
+
+
+def lut3d(y: torch.Tensor, lut, crop_hw: Optional[Tuple[int, int]] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Planar result (B,3,H,W), cropped to crop_hw, -> (B,3,h,w) through the colour look `lut` (a Lut3D), tetrahedral interpolation
+    (rc_lut3d; the arithmetic is fixed in include/realcam_hip.h).  out_dtype: torch.float32, or y's dtype (rounded to nearest even once).
+    One launch."""
+    from .look import Lut3D
+    if not isinstance(lut, Lut3D):
+        raise TypeError(f"lut3d: lut must be a Lut3D, got {type(lut).__name__}")
+    y = _req(y, "lut3d input")
+    if y.dim() != 4 or y.shape[1] != 3:
+        raise ValueError(f"lut3d: expected (B,3,H,W), got {tuple(y.shape)}")
+    _dt(y)
+    if out_dtype not in (torch.float32, y.dtype):
+        raise ValueError(f"lut3d: out_dtype must be torch.float32 or the source's {y.dtype}, got {out_dtype}")
+    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
+    if y.shape[0] < 1 or h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]:
+        raise ValueError(f"lut3d: crop {(h, w)} of the source {tuple(y.shape)} is empty or exceeds it")
+    if isinstance(y, FakeTensor):                              # a trace: shapes only, nothing is built, copied or kept
+        table = y.new_empty((lut.size ** 3, 4), dtype=torch.float32)
+    else:
+        table = lut3d_table(lut, y.device)
+    return _R.lut3d(y, table, lut.size, h, w, out_dtype)
+
+
 def make_coord(b: int, h: int, w: int, device=None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """Normalised pixel-coordinate map (B,2,h,w) in [-1,1], channel 0 = y, channel 1 = x: the lens-shading branch's input x[2]
     (upstream never published its generator; build convention).  Plain tensor construction, no kernel."""

@@ -10,6 +10,7 @@ from dataclasses import dataclass
 from typing import Optional, Tuple
 
 from . import _lib
+from .look import Lut3D
 from .out_format import OutFormat
 
 FILTERS = {"area": _lib.RC_FILTER_AREA, "bilinear": _lib.RC_FILTER_BILINEAR}
@@ -93,14 +94,16 @@ class Resize:
 
 @dataclass(frozen=True)
 class Output:
-    """One entry of forward_mosaic(outputs=[...]): an optional Resize of the float result, then its format.
+    """One entry of forward_mosaic(outputs=[...]): an optional Resize of the float result, an optional colour look, then its format.
 
     format  None (the planar float tensor), "rgb8" / "rgb16" (interleaved uint8 / uint16) or an OutFormat (a YuvFrames).
     resize  None (the result's own size) or a Resize.
+    look    None or a Lut3D, applied after the resize and before the encoder (ops.lut3d; with format None the looked tensor is fp32).
     """
 
     format: object = None
     resize: Optional[Resize] = None
+    look: Optional[Lut3D] = None
 
     def __post_init__(self):
         f = self.format
@@ -110,6 +113,8 @@ class Output:
             raise ValueError(f"Output.format must be None, 'rgb8', 'rgb16' or an OutFormat, got {f!r}")
         if self.resize is not None and not isinstance(self.resize, Resize):
             raise TypeError(f"Output.resize must be None or a Resize, got {type(self.resize).__name__}")
+        if self.look is not None and not isinstance(self.look, Lut3D):
+            raise TypeError(f"Output.look must be None or a Lut3D, got {type(self.look).__name__}")
         if isinstance(f, OutFormat) and self.resize is not None and (self.resize.size[0] % 2 or self.resize.size[1] % 2):
             raise ValueError(f"Output: 4:2:0 ({f.layout}) needs an even height and width, Resize.size is {self.resize.size}")
 

@@ -179,6 +179,18 @@ def _resize_launch(out, y, first_y, wy, first_x, wx, dtype):
 define("resize(Tensor y, Tensor first_y, Tensor wy, Tensor first_x, Tensor wx, ScalarType dtype) -> Tensor",
        lambda y, first_y, wy, first_x, wx, dtype: y.new_empty((y.shape[0], 3, wy.shape[0], wx.shape[0]), dtype=dtype), _resize_launch)
 
+
+def _lut3d_launch(out, y, table, n, h, w, dtype):
+    if table.dtype != torch.float32 or table.device != y.device or not table.is_contiguous() or table.numel() != 4 * n ** 3:
+        raise ValueError(f"realcam::lut3d: the table must be a contiguous float32 tensor of {n}^3 x 4 values on {y.device}")
+    check(lib().rc_lut3d(y.data_ptr(), _dt(y), out.data_ptr(), _DT[dtype], table.data_ptr(), n, y.shape[0], y.shape[2], y.shape[3], h, w, _stream()),
+          "rc_lut3d")
+
+
+# y (B,3,H,W) planar, cropped to (h,w), -> (B,3,h,w) of `dtype` (fp32 or y's); table (n^3, 4) fp32 on the device: R, G, B, pad per node, R fastest
+define("lut3d(Tensor y, Tensor table, int n, int h, int w, ScalarType dtype) -> Tensor",
+       lambda y, table, n, h, w, dtype: y.new_empty((y.shape[0], 3, h, w), dtype=dtype), _lut3d_launch)
+
 define("nchw_to_nhwc(Tensor x, ScalarType dtype, int hp, int wp) -> Tensor",
        lambda x, dtype, hp, wp: x.new_empty((x.shape[0], hp, wp, x.shape[1]), dtype=dtype),
        lambda out, x, dtype, hp, wp: check(lib().rc_nchw_to_nhwc(x.data_ptr(), _dt(x), out.data_ptr(), _DT[dtype], x.shape[0], x.shape[1],
