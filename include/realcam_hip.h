@@ -231,6 +231,49 @@ int rc_resize(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, int 
  * read outside the table.  One launch.  n outside 2 .. 65, a bad dtype, h > H or w > W: RC_ERR_INVALID before any launch. */
 int rc_lut3d(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, const float* d_lut, int n, int batch, int H, int W, int h, int w, void* stream);
 
+/* ---- geometric correction (ABI 15, additive): the same planar result resampled through a coarse mesh, in front of the scaler --------------
+ * Replaces: F.grid_sample(result.float(), dense (B, oh, ow, 2) grid, align_corners=True) after the network -- lens distortion correction,
+ * a 90 degree orientation, a flip, per-frame stabilisation -- and with it the dense grid in HBM and the fp32 copy of the frame.
+ * The mesh holds one source position per `cell` output pixels and is interpolated bilinearly; the source is sampled bilinearly or with
+ * the bicubic kernel of A = -0.75 (F.grid_sample(mode="bicubic"), OpenCV INTER_CUBIC). */
+typedef enum rc_warp_interp {
+    RC_WARP_BILINEAR = 0,
+    RC_WARP_BICUBIC = 1
+} rc_warp_interp;
+typedef enum rc_warp_border {
+    RC_WARP_CLAMP = 0,       /* a tap outside the frame reads the nearest pixel of the frame (grid_sample padding_mode="border") */
+    RC_WARP_CONSTANT = 1     /* a tap outside the frame is fill[channel] (padding_mode="zeros" when the fill is 0) */
+} rc_warp_border;
+#define RC_WARP_MIN_CELL_LOG2 3   /* cell = 8, 16, 32 or 64 output pixels */
+#define RC_WARP_MAX_CELL_LOG2 6
+#define RC_WARP_MAX_DIM 8388608   /* h, w, oh, ow <= 2^23: every coordinate and w + 1, h + 1 are exact in fp32 */
+
+/* src (B,3,H,W) RC_F32 / RC_BF16 / RC_F16 planar, cropped to the frame (h,w); dst (B,3,oh,ow) planar, RC_F32 or src_dtype; oh, ow >= 1
+ * are free (upscaling is allowed).  cell = 1 << cell_log2.
+ * d_mesh: DEVICE fp32, 8-byte aligned, mesh_batch (1: shared by every frame, or batch: one per frame) meshes of Gh x Gw nodes of two
+ * floats, Gh = ceil(oh / cell) + 1, Gw = ceil(ow / cell) + 1, row-major; node (j, i) = (sx, sy) is the source position, in pixels of the
+ * frame with an integer at a pixel's centre, that output pixel (x, y) = (i cell, j cell) samples.  Nodes need not be finite (step 2).
+ * fp32, every product, sum and difference rounded on its own (no fused multiply-add); for output pixel (x, y), per frame:
+ *   1. i = x >> cell_log2, u = float(x & (cell-1)) (1/cell);  j = y >> cell_log2, v = float(y & (cell-1)) (1/cell)       (all exact)
+ *      per component (sx, then sy) with m00 = node(j,i), m10 = node(j,i+1), m01 = node(j+1,i), m11 = node(j+1,i+1):
+ *        top = ((1-u) m00) + (u m10);  bot = ((1-u) m01) + (u m11);  s = ((1-v) top) + (v bot)
+ *   2. guard: NaN -> -2; then sx = min(max(sx, -2), float(w+1)), sy = min(max(sy, -2), float(h+1)).  Every tap index below is also
+ *      clamped into the frame or tested against it: no mesh -- NaN, +-inf, 1e30 -- makes the kernel read outside its buffer.
+ *   3. x0 = int(floor(sx)), tx = sx - float(x0);  y0 = int(floor(sy)), ty = sy - float(y0)                               (exact)
+ *   4. taps, per axis with t = tx or ty:
+ *        BILINEAR  offsets 0, 1      weights 1-t, t
+ *        BICUBIC   offsets -1, 0, 1, 2   weights c2(t+1), c1(t), c1(1-t), c2(2-t)
+ *                  c1(x) = (((1.25 x) - 2.25) x) x + 1;   c2(x) = ((((-0.75 x) + 3.75) x) - 6) x + 3      (exactly 0, 1, 0, 0 at t = 0)
+ *      a tap whose column x0 + offset lies outside [0, w) or whose row lies outside [0, h) reads the pixel at the index clamped into the
+ *      frame (CLAMP) or is fill[channel] (CONSTANT); 16-bit samples are widened exactly.
+ *   5. per tap row k:  r_k = (..((wx_0 s_k0) + (wx_1 s_k1)) + ..) in offset order;  o = (..((wy_0 r_0) + (wy_1 r_1)) + ..)
+ * No output clamp and no NaN rule for samples (the look and the encoders have theirs).  o is stored as fp32, or rounded to nearest even
+ * once into src_dtype.  An identity mesh returns the frame exactly (up to the sign of a zero).  One launch.
+ * A bad dtype, interp, border or cell, mesh_batch other than 1 or batch, a non-finite fill, h > H, w > W, a dimension above
+ * RC_WARP_MAX_DIM, a source plane of 2^29 samples or more, a null or misaligned pointer: RC_ERR_INVALID before any launch. */
+int rc_warp(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, const float* d_mesh, int mesh_batch, int cell_log2, int interp,
+            int border, float fill_r, float fill_g, float fill_b, int batch, int H, int W, int h, int w, int oh, int ow, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

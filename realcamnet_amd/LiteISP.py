@@ -315,13 +315,15 @@ def _plan_outputs(outputs, out_format, hw):
 
 
 def _emit(y, bits, outs):
-    """The single result of the out_format route, or the list of renditions of `outs` in the order given: each an optional ops.resize
-    (fp32) of the one float result, then an optional colour look (ops.lut3d, fp32), then the encoders of _encode."""
+    """The single result of the out_format route, or the list of renditions of `outs` in the order given: each an optional ops.warp (fp32)
+    of the one float result, then an optional ops.resize (fp32), then an optional colour look (ops.lut3d, fp32), then the encoders of
+    _encode."""
     if outs is None:
         return _encode(y, bits)
     res = []
     for o in outs:
-        t = y if o.resize is None else ops.resize(y, o.resize)
+        t = y if o.warp is None else ops.warp(y, o.warp)
+        t = t if o.resize is None else ops.resize(t, o.resize)
         if o.look is not None:
             t = ops.lut3d(t, o.look)
         res.append(_encode(t, _out_bits(o.format)))
@@ -438,7 +440,8 @@ class _DwtUNet(nn.Module):
         raw_format (a RawFormat): the sensor frame's CFA phase, storage (MIPI RAW10 / RAW12 lines: (B,[1,]2h,line_bytes) uint8) and
         per-position levels.  out_format "rgb8" / "rgb16": the result as interleaved (B,2h,2w,3) uint8 / uint16; an OutFormat: a YuvFrames
         (one NV12 / P010 / I420 encoder surface per frame, and views of its planes).
-        outputs [Output(format, resize, look), ...] instead of out_format: one network pass, then per Output an optional scaled / cropped
+        outputs [Output(format, resize, look, warp), ...] instead of out_format: one network pass, then per Output, in this order, an optional
+        geometric correction (a Warp: ops.warp, fp32 out, whose size is the frame the next stages see), an optional scaled / cropped
         rendition (ops.resize, fp32) and an optional colour look (a Lut3D: ops.lut3d, fp32) in its own format; returns the list in the
         order given."""
         if self.training:

@@ -27,6 +27,9 @@ RC_SITING_LEFT, RC_SITING_CENTER = 0, 1
 RC_FILTER_AREA, RC_FILTER_BILINEAR = 0, 1
 RC_RESIZE_MAX_TAPS, RC_RESIZE_MAX_RATIO = 20, 8
 RC_LUT3D_MIN_SIZE, RC_LUT3D_MAX_SIZE = 2, 65
+RC_WARP_BILINEAR, RC_WARP_BICUBIC = 0, 1
+RC_WARP_CLAMP, RC_WARP_CONSTANT = 0, 1
+RC_WARP_MIN_CELL_LOG2, RC_WARP_MAX_CELL_LOG2, RC_WARP_MAX_DIM = 3, 6, 1 << 23
 
 
 class ConvDesc(C.Structure):
@@ -104,6 +107,7 @@ _SIGS = {
     "rc_resize_taps": (C.c_int, [_I, _I, _I, _I, _P, _P, C.POINTER(C.c_int)]),
     "rc_resize": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "rc_lut3d": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "rc_warp": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

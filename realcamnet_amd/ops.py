@@ -7,6 +7,7 @@ There is NO fallback: CPU tensors or a missing library raise.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional, Tuple
 
 import numpy as np
@@ -609,6 +610,71 @@ def lut3d(y: torch.Tensor, lut, crop_hw: Optional[Tuple[int, int]] = None, out_d
     else:
         table = lut3d_table(lut, y.device)
     return _R.lut3d(y, table, lut.size, h, w, out_dtype)
+
+
+_WARP_MESHES = {}        # (Warp, device) -> the device mesh of rc_warp
+
+
+def warp_mesh(wp, device):
+    """The (1, Gh, Gw, 2) fp32 mesh of the Warp `wp` on `device`: copied once per (warp, device), then kept -- a warmed-up ops.warp makes no
+    host-to-device copy."""
+    device = torch.device(device)
+    key = (wp, device.type, device.index if device.index is not None else torch.cuda.current_device())
+    hit = _WARP_MESHES.get(key)
+    if hit is None:
+        hit = _WARP_MESHES[key] = torch.from_numpy(wp.packed()).to(device)
+    return hit
+
+
+def warp(y: torch.Tensor, warp_or_mesh, size: Optional[Tuple[int, int]] = None, cell: int = 16, interp: str = "bilinear", border: str = "clamp",
+         fill=(0.0, 0.0, 0.0), crop_hw: Optional[Tuple[int, int]] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Planar result (B,3,H,W), cropped to crop_hw, -> (B,3,oh,ow): resampled through a coarse mesh of source positions (rc_warp; the
+    arithmetic is fixed in include/realcam_hip.h).  out_dtype: torch.float32, or y's dtype (rounded to nearest even once).  One launch.
+    warp_or_mesh: a Warp -- it carries size, cell, interp, border and fill itself (`size` must stay None, the other four are not looked
+    at), and its mesh is kept on the device per (warp, device); or a CUDA fp32 tensor (Gh, Gw, 2) or (Bm, Gh, Gw, 2) with Bm = 1 or B (one
+    mesh per frame: stabilisation), used in place, with `size` = (oh, ow) required.  A mesh tensor's nodes need not be finite: the kernel
+    guards every coordinate and every index."""
+    from .warp import BORDERS, INTERPS, Warp, _cell, _hw, mesh_shape
+    y = _req(y, "warp input")
+    if y.dim() != 4 or y.shape[1] != 3:
+        raise ValueError(f"warp: expected (B,3,H,W), got {tuple(y.shape)}")
+    _dt(y)
+    if out_dtype not in (torch.float32, y.dtype):
+        raise ValueError(f"warp: out_dtype must be torch.float32 or the source's {y.dtype}, got {out_dtype}")
+    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
+    if y.shape[0] < 1 or h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]:
+        raise ValueError(f"warp: crop {(h, w)} of the source {tuple(y.shape)} is empty or exceeds it")
+    if isinstance(warp_or_mesh, Warp):
+        wp = warp_or_mesh
+        if size is not None:
+            raise ValueError("warp: size belongs to the mesh-tensor form; a Warp carries its own")
+        wp.check_source(h, w)
+        size, cell, interp, border, fill = wp.size, wp.cell, wp.interp, wp.border, wp.fill
+        if isinstance(y, FakeTensor):                          # a trace: shapes only, nothing is built, copied or kept
+            mesh = y.new_empty((1, *mesh_shape(size, cell), 2), dtype=torch.float32)
+        else:
+            mesh = warp_mesh(wp, y.device)
+    elif isinstance(warp_or_mesh, torch.Tensor):
+        mesh = warp_or_mesh
+        if size is None:
+            raise ValueError("warp: size = (oh, ow) is required with a mesh tensor")
+        size, cell = _hw("size", size), _cell(cell)
+        if not isinstance(interp, str) or interp not in INTERPS:
+            raise ValueError(f"warp: interp must be one of {sorted(INTERPS)}, got {interp!r}")
+        if not isinstance(border, str) or border not in BORDERS:
+            raise ValueError(f"warp: border must be one of {sorted(BORDERS)}, got {border!r}")
+        if not isinstance(fill, (tuple, list)) or len(fill) != 3 or not all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) for v in fill):
+            raise ValueError(f"warp: fill must be three finite numbers (R, G, B), got {fill!r}")
+        want = (*mesh_shape(size, cell), 2)
+        if mesh.dim() == 3:
+            mesh = mesh.unsqueeze(0)
+        if mesh.dtype != torch.float32 or mesh.device != y.device or mesh.dim() != 4 or tuple(mesh.shape[1:]) != want or mesh.shape[0] not in (1, y.shape[0]):
+            raise ValueError(f"warp: the mesh must be a float32 tensor {want} or (1 or {y.shape[0]}, *{want}) on {y.device} for size {size} at cell {cell}, "
+                             f"got {tuple(warp_or_mesh.shape)} {mesh.dtype} on {mesh.device}")
+        mesh = mesh.contiguous()
+    else:
+        raise TypeError(f"warp: warp_or_mesh must be a Warp or a mesh tensor, got {type(warp_or_mesh).__name__}")
+    return _R.warp(y, mesh, cell, INTERPS[interp], BORDERS[border], [float(v) for v in fill], h, w, size[0], size[1], out_dtype)
 
 
 def make_coord(b: int, h: int, w: int, device=None, dtype: torch.dtype = torch.float32) -> torch.Tensor:

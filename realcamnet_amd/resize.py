@@ -12,6 +12,7 @@ from typing import Optional, Tuple
 from . import _lib
 from .look import Lut3D
 from .out_format import OutFormat
+from .warp import Warp
 
 FILTERS = {"area": _lib.RC_FILTER_AREA, "bilinear": _lib.RC_FILTER_BILINEAR}
 MAX_TAPS = _lib.RC_RESIZE_MAX_TAPS
@@ -94,16 +95,19 @@ class Resize:
 
 @dataclass(frozen=True)
 class Output:
-    """One entry of forward_mosaic(outputs=[...]): an optional Resize of the float result, an optional colour look, then its format.
+    """One entry of forward_mosaic(outputs=[...]): an optional Warp of the float result, an optional Resize, an optional colour look, then
+    its format.
 
     format  None (the planar float tensor), "rgb8" / "rgb16" (interleaved uint8 / uint16) or an OutFormat (a YuvFrames).
     resize  None (the result's own size) or a Resize.
     look    None or a Lut3D, applied after the resize and before the encoder (ops.lut3d; with format None the looked tensor is fp32).
+    warp    None or a Warp, applied first (ops.warp, fp32): the resize's window and the format then see a frame of warp.size.
     """
 
     format: object = None
     resize: Optional[Resize] = None
     look: Optional[Lut3D] = None
+    warp: Optional[Warp] = None
 
     def __post_init__(self):
         f = self.format
@@ -115,11 +119,18 @@ class Output:
             raise TypeError(f"Output.resize must be None or a Resize, got {type(self.resize).__name__}")
         if self.look is not None and not isinstance(self.look, Lut3D):
             raise TypeError(f"Output.look must be None or a Lut3D, got {type(self.look).__name__}")
+        if self.warp is not None and not isinstance(self.warp, Warp):
+            raise TypeError(f"Output.warp must be None or a Warp, got {type(self.warp).__name__}")
         if isinstance(f, OutFormat) and self.resize is not None and (self.resize.size[0] % 2 or self.resize.size[1] % 2):
             raise ValueError(f"Output: 4:2:0 ({f.layout}) needs an even height and width, Resize.size is {self.resize.size}")
+        if isinstance(f, OutFormat) and self.resize is None and self.warp is not None and (self.warp.size[0] % 2 or self.warp.size[1] % 2):
+            raise ValueError(f"Output: 4:2:0 ({f.layout}) needs an even height and width, Warp.size is {self.warp.size} and no Resize follows it")
 
     def plan(self, h: int, w: int) -> Tuple[int, int]:
         """The (h, w) this output has for an (h, w) result; every refusal that depends on the frame is raised here, before any launch."""
+        if self.warp is not None:
+            self.warp.check_source(h, w)
+            h, w = self.warp.size
         if self.resize is not None:
             self.resize.window(h, w)
             h, w = self.resize.size

@@ -191,6 +191,22 @@ def _lut3d_launch(out, y, table, n, h, w, dtype):
 define("lut3d(Tensor y, Tensor table, int n, int h, int w, ScalarType dtype) -> Tensor",
        lambda y, table, n, h, w, dtype: y.new_empty((y.shape[0], 3, h, w), dtype=dtype), _lut3d_launch)
 
+def _warp_launch(out, y, mesh, cell, interp, border, fill, h, w, oh, ow, dtype):
+    gh, gw = -(-oh // cell) + 1, -(-ow // cell) + 1
+    if (mesh.dtype != torch.float32 or mesh.device != y.device or not mesh.is_contiguous() or mesh.dim() != 4 or tuple(mesh.shape[1:]) != (gh, gw, 2)
+            or mesh.shape[0] not in (1, y.shape[0])):
+        raise ValueError(f"realcam::warp: the mesh must be a contiguous float32 tensor (1 or {y.shape[0]}, {gh}, {gw}, 2) on {y.device}, got {tuple(mesh.shape)} {mesh.dtype}")
+    if cell not in (8, 16, 32, 64) or len(fill) != 3:
+        raise ValueError(f"realcam::warp: cell must be 8, 16, 32 or 64 and fill three floats, got {cell!r}, {fill!r}")
+    check(lib().rc_warp(y.data_ptr(), _dt(y), out.data_ptr(), _DT[dtype], mesh.data_ptr(), mesh.shape[0], cell.bit_length() - 1, interp, border,
+                        float(fill[0]), float(fill[1]), float(fill[2]), y.shape[0], y.shape[2], y.shape[3], h, w, oh, ow, _stream()), "rc_warp")
+
+
+# y (B,3,H,W) planar, cropped to the frame (h,w), -> (B,3,oh,ow) of `dtype` (fp32 or y's); mesh (1 or B, Gh, Gw, 2) fp32 on the device: the source
+# position (sx, sy) per `cell` output pixels; interp / border: the rc_warp_* enums; fill: R, G, B of the constant border
+define("warp(Tensor y, Tensor mesh, int cell, int interp, int border, float[] fill, int h, int w, int oh, int ow, ScalarType dtype) -> Tensor",
+       lambda y, mesh, cell, interp, border, fill, h, w, oh, ow, dtype: y.new_empty((y.shape[0], 3, oh, ow), dtype=dtype), _warp_launch)
+
 define("nchw_to_nhwc(Tensor x, ScalarType dtype, int hp, int wp) -> Tensor",
        lambda x, dtype, hp, wp: x.new_empty((x.shape[0], hp, wp, x.shape[1]), dtype=dtype),
        lambda out, x, dtype, hp, wp: check(lib().rc_nchw_to_nhwc(x.data_ptr(), _dt(x), out.data_ptr(), _DT[dtype], x.shape[0], x.shape[1],
