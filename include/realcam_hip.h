@@ -777,7 +777,8 @@ int rc_window_attention_planar8_ok(int dtype, int batch, int H, int W, int C, in
  * 32x32x16 MFMA forms (0 none, 4 = where measured faster, 1 / 2 / 3 = everywhere eligible in one of three forms; set BEFORE
  * packing: the packed weight order depends on it -- and on no other knob: such a layer runs its own kernel in every "persist" mode); "pair_impl" [0] which of the two rc_conv_pair kernels; "pss" [0] the
  * 48 -> 192 + PixelShuffle layer with its output staged through LDS; "dw3_seg16" [1] rc_dwconv2d's bf16 3x3 single-rep
- * case on 16-channel segments; "conv_flags" knock-outs for timing experiments (1 no stores, 8 stores into one 4 MB
+ * case on 16-channel segments; "wmsa_mfma" [1] rc_window_attention's bf16 8 x 8-window calls on the matrix cores (0: the one-lane-per-query kernel, which such a
+ * call otherwise reaches only past 2^31 elements per image; rc_window_attention_planar8_ok then answers 0 and rc_window_attention_planar8 is refused: the planar layout exists for the matrix-core form only); "conv_flags" knock-outs for timing experiments (1 no stores, 8 stores into one 4 MB
  * window: results are then meaningless; 64 one persistent block per CU instead of two: results unchanged, an occupancy experiment);
  * "persist_auto" [1] the wave-autonomous kernels 6 / 7 (0 off, 1 all but the residual forms of kernel 6, 2 every eligible form); "sums_compact" [1] the compact
  * channel-sum slot layout (rc_conv_sum_slots); "thin" [2] kernel 4b (one barrier per stage) in place of the multi-chunk kernel 4: 1 = only where the stages are thin (weights and tiles by LDS-DMA, tiles two stages

@@ -561,6 +561,7 @@ int rc_gc_symbols(const void* d_y, const void* d_mu, const void* d_scale, int dt
 int rc_gc_dequantize(const int32_t* d_symbols, const void* d_mu, int dtype, int batch, long long hw, int channels, void* d_y_hat, void* stream) {
     RC_REQUIRE(d_symbols && d_mu && d_y_hat, "rc_gc_dequantize: null pointer");
     RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_gc_dequantize: bad dtype");
+    RC_REQUIRE(batch >= 1 && hw >= 1 && channels >= 1, "rc_gc_dequantize: bad shape");
     const long total = (long)batch * channels * hw;
     if (dtype == RC_F32)
         hipLaunchKernelGGL(gc_dequant_kernel<float>, dim3(grid1d(total)), dim3(256), 0, as_stream(stream), d_symbols, static_cast<const float*>(d_mu),
@@ -576,6 +577,7 @@ int rc_eb_symbols(const void* d_z, const float* d_medians, int dtype, int batch,
                   int32_t* d_indexes, void* d_z_hat, void* stream) {
     RC_REQUIRE(d_medians && d_symbols && d_indexes && d_z_hat && (d_z || !encode), "rc_eb_symbols: null pointer");
     RC_REQUIRE(dtype == RC_F32 || dtype == RC_BF16, "rc_eb_symbols: bad dtype");
+    RC_REQUIRE(batch >= 1 && hw >= 1 && channels >= 1, "rc_eb_symbols: bad shape");
     const long total = (long)batch * channels * hw;
     if (dtype == RC_F32)
         hipLaunchKernelGGL(eb_symbols_kernel<float>, dim3(grid1d(total)), dim3(256), 0, as_stream(stream), static_cast<const float*>(d_z), d_medians,
@@ -655,6 +657,7 @@ int rc_rans_decode_chunks(const void* d_stream, long long stream_bytes, const lo
                           int32_t* d_err, void* stream) {
     RC_REQUIRE(d_stream && d_offsets && d_indexes && d_cdf && d_cdf_sizes && d_cdf_offsets && d_symbols && d_err, "rc_rans_decode_chunks: null pointer");
     RC_REQUIRE(n >= 1 && chunk >= 1 && stream_bytes >= 8 && stream_bytes < (1ll << 31), "rc_rans_decode_chunks: bad shape (a container is < 2 GiB)");
+    RC_REQUIRE(cdf_stride >= 2 && n_cdfs >= 1, "rc_rans_decode_chunks: bad table shape");
     const long n_chunks = (n + chunk - 1) / chunk;
     const Tables t{d_cdf, cdf_stride, n_cdfs, d_cdf_sizes, d_cdf_offsets};
     const size_t lds = (size_t)(3 * n_cdfs + 2) * 4 + (size_t)kDecLdsEntries * 2;

@@ -314,6 +314,7 @@ __global__ __launch_bounds__(kWmWaves * 64, 2) void wmsa_mfma_kernel(const bf16_
 
 }  // namespace rc
 
+namespace rc { int g_wmsa_mfma = 1; }   // rc_debug_set("wmsa_mfma", v): 1 (default) bf16 8 x 8-window calls take the matrix-core kernel; 0: wmsa_kernel<bf16_t, HD, 8> (tests: that instantiation is otherwise reached only past 2^31 elements per image)
 using namespace rc;
 
 extern "C" {
@@ -329,7 +330,7 @@ int rc_window_attention_planar8(const void* d_qkv, const float* d_relpos, void* 
     return window_attention_impl(d_qkv, d_relpos, d_out, dtype, batch, H, W, C, head_dim, window, shift, 1, stream);
 }
 int rc_window_attention_planar8_ok(int dtype, int batch, int H, int W, int C, int window) {
-    return dtype == RC_BF16 && window == 8 && batch >= 1 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0 && (long long)batch * (H / 8) * (W / 8) < (1LL << 30) &&
+    return g_wmsa_mfma && dtype == RC_BF16 && window == 8 && batch >= 1 && H >= 8 && W >= 8 && H % 8 == 0 && W % 8 == 0 && (long long)batch * (H / 8) * (W / 8) < (1LL << 30) &&
            (long long)batch * H * W * 3 * C < (1LL << 31);
 }
 }  // extern "C"
@@ -345,7 +346,7 @@ static int window_attention_impl(const void* d_qkv, const float* d_relpos, void*
     if (planar8 && !rc_window_attention_planar8_ok(dtype, batch, H, W, C, window))
         return fail(RC_ERR_UNSUPPORTED, "rc_window_attention_planar8: the segment-planar q / k / v layout exists for the bf16 8 x 8-window matrix-core form with B H W 3C < 2^31");
     // matrix-core form: 32-bit window counts and in-image element offsets (larger maps take the one-lane-per-query kernel below)
-    if (dtype == RC_BF16 && window == 8 && (long long)batch * (H / 8) * (W / 8) < (1LL << 30) && (long long)H * W * 3 * C < (1LL << 31)) {
+    if (g_wmsa_mfma && dtype == RC_BF16 && window == 8 && (long long)batch * (H / 8) * (W / 8) < (1LL << 30) && (long long)H * W * 3 * C < (1LL << 31)) {
         const int nh = C / head_dim;
         const long long n_win = (long long)batch * (H / 8) * (W / 8);
         const int dtiles = (head_dim + 15) / 16;
