@@ -274,6 +274,49 @@ typedef enum rc_warp_border {
 int rc_warp(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, const float* d_mesh, int mesh_batch, int cell_log2, int interp,
             int border, float fill_r, float fill_g, float fill_b, int batch, int H, int W, int h, int w, int oh, int ow, void* stream);
 
+/* ---- frame statistics (ABI 15, additive): histograms and a 3A zone grid of the same planar result, the one stage that is a reduction ------
+ * Replaces: y.float().clamp(0, 1).mul(255).round(), torch.bincount per channel and a pooling pass per sum -- an fp32 copy of the frame
+ * and several passes over it.  What auto-exposure, auto white balance, autofocus, a scope and a scene-change detector read. */
+#define RC_STATS_MAX_GRID 64      /* zones per axis */
+#define RC_STATS_SLOTS 8          /* numbers per zone */
+typedef struct rc_stats_desc {
+    int roi[4];            /* y0, x0, rh, rw: the window of the crop (h,w) that is measured; rh = rw = 0: the whole crop */
+    int grid[2];           /* gy, gx: zones per axis, 1 .. min(64, rh) and 1 .. min(64, rw) */
+    int bits;              /* 8 or 10: codes 0 .. S, S = 2^bits - 1 */
+    int matrix;            /* rc_yuv_matrix: the luma coefficients */
+    int dark;              /* -1 .. S: a pixel that is not clipped is dark if qY <= dark; -1: nothing is dark */
+    int clip;              /* 1 .. 2^bits: a pixel is clipped if max(qR, qG, qB) >= clip; 2^bits: nothing clips */
+    int reserved[4];       /* zero */
+} rc_stats_desc;
+size_t rc_stats_desc_size(void);
+
+/* src (B,3,H,W) RC_F32 / RC_BF16 / RC_F16 planar R,G,B, cropped to (h,w); the ROI (y0, x0, rh, rw) lies inside the crop; pixel (x, y) below
+ * is ROI-relative.  d_hist (B, 4, 2^bits) and d_zones (B, gy, gx, 8), both int64, 8-byte aligned.  Per frame:
+ *   1. r,g,b = float(src), NaN -> 0, clamped to [0,1]                                                   (step 1 of rc_yuv_encode)
+ *   2. Y = ((Kr r) + (Kg g)) + (Kb b) in fp32, every product and every sum rounded on its own (no fused multiply-add); Kr, Kb from
+ *      RC_YUV_KR_KB, Kg = 1 - Kr - Kb in double, each rounded to fp32 once                               (rc_yuv_encode's Y)
+ *   3. codes q(v) = clamp(rint(v S), 0, S), round half to even: integers qR, qG, qB, qY.
+ *      At 8 bits qR, qG, qB are rc_rgb_encode(.., 8)'s bytes and qY is the Y plane of a full-range NV12 surface of the same matrix; at 10
+ *      bits qY is full-range P010's Y code, sample >> 6.
+ *   4. hist[c][k] = the number of ROI pixels whose code in channel c (R, G, B, Y) is k.
+ *   5. pixel (x, y) belongs to zone (floor(y gy / rh), floor(x gx / rw)): zone column i is the columns ceil(i rw / gx) ..
+ *      ceil((i+1) rw / gx) - 1, never empty; rows alike.
+ *   6. a pixel is clipped if max(qR,qG,qB) >= clip; otherwise dark if qY <= dark; otherwise valid.
+ *   7. focus f = dx^2 + dy^2, dx = qY[y][min(x+1, rw-1)] - qY[y][x], dy = qY[min(y+1, rh-1)][x] - qY[y][x]: the neighbour is clamped to the
+ *      ROI, not to the crop or the plane.
+ *   8. zones[j][i][0..7] = count of valid pixels; sum of qR, of qG, of qB over valid pixels; sum of qY over all pixels of the zone; count of
+ *      clipped pixels; count of dark pixels; sum of f over all pixels of the zone.
+ * Everything after step 3 is integer arithmetic: the result does not depend on the order of summation, so it is bit-exact and the same
+ * from run to run although it is accumulated with atomics.  A plane holds fewer than 2^29 samples and f <= 2 * 1023^2, so every total
+ * stays below 2^51.
+ * Every element of both outputs is written: the entry point zeroes them on `stream` itself (the caller does not), then one launch adds.
+ * It keeps no device buffer of its own and is capturable; a graph replay starts from zero again.
+ * Null pointers, a bad dtype, bits or matrix, an ROI outside the crop or with one zero side only, a grid outside 1 .. min(64, side),
+ * thresholds out of range, non-zero reserved, h > H or w > W, outputs not 8-byte aligned, a misaligned source, a plane of 2^29 samples or
+ * more: RC_ERR_INVALID before any launch. */
+int rc_frame_stats(const void* d_src, int src_dtype, const rc_stats_desc* desc, long long* d_hist, long long* d_zones,
+                   int batch, int H, int W, int h, int w, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

@@ -30,6 +30,7 @@ RC_LUT3D_MIN_SIZE, RC_LUT3D_MAX_SIZE = 2, 65
 RC_WARP_BILINEAR, RC_WARP_BICUBIC = 0, 1
 RC_WARP_CLAMP, RC_WARP_CONSTANT = 0, 1
 RC_WARP_MIN_CELL_LOG2, RC_WARP_MAX_CELL_LOG2, RC_WARP_MAX_DIM = 3, 6, 1 << 23
+RC_STATS_MAX_GRID, RC_STATS_SLOTS = 64, 8
 
 
 class ConvDesc(C.Structure):
@@ -83,6 +84,14 @@ class OutFormatDesc(C.Structure):
     ]
 
 
+class StatsDesc(C.Structure):
+    """Mirror of `struct rc_stats_desc`."""
+    _fields_ = [
+        ("roi", C.c_int32 * 4), ("grid", C.c_int32 * 2), ("bits", C.c_int32), ("matrix", C.c_int32), ("dark", C.c_int32), ("clip", C.c_int32),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 def declared_symbols() -> list[str]:
     """Every function the public header declares (used by the CPU-side ABI test)."""
     text = HEADER.read_text()
@@ -108,6 +117,8 @@ _SIGS = {
     "rc_resize": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "rc_lut3d": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "rc_warp": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "rc_stats_desc_size": (_SZ, []),
+    "rc_frame_stats": (C.c_int, [_P, _I, C.POINTER(StatsDesc), _P, _P, _I, _I, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

@@ -677,6 +677,28 @@ def warp(y: torch.Tensor, warp_or_mesh, size: Optional[Tuple[int, int]] = None, 
     return _R.warp(y, mesh, cell, INTERPS[interp], BORDERS[border], [float(v) for v in fill], h, w, size[0], size[1], out_dtype)
 
 
+def frame_stats(y: torch.Tensor, stats, crop_hw: Optional[Tuple[int, int]] = None):
+    """Planar result (B,3,H,W), cropped to crop_hw, -> a FrameStats: the R / G / B / Y code histograms (B,4,2**bits) and the 3A zone grid
+    (B,gy,gx,8) of the Stats `stats`, int64 on the device (rc_frame_stats; the arithmetic is fixed in include/realcam_hip.h).  The frame is
+    read once by one launch; nothing is synchronised."""
+    from .out_format import MATRICES
+    from .stats import FrameStats, Stats
+    if not isinstance(stats, Stats):
+        raise TypeError(f"frame_stats: stats must be a Stats, got {type(stats).__name__}")
+    y = _req(y, "frame_stats input")
+    if y.dim() != 4 or y.shape[1] != 3:
+        raise ValueError(f"frame_stats: expected (B,3,H,W), got {tuple(y.shape)}")
+    _dt(y)
+    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
+    if y.shape[0] < 1 or h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]:
+        raise ValueError(f"frame_stats: crop {(h, w)} of the source {tuple(y.shape)} is empty or exceeds it")
+    if y.shape[2] * y.shape[3] >= 1 << 29:
+        raise ValueError(f"frame_stats: a source plane of {tuple(y.shape[2:])} has 2^29 samples or more")
+    roi = stats.check(h, w)
+    hist, zones = _R.frame_stats(y, h, w, list(roi), stats.grid[0], stats.grid[1], stats.bits, MATRICES[stats.matrix], stats.dark_code, stats.clip_code)
+    return FrameStats(hist, zones, stats, roi)
+
+
 def make_coord(b: int, h: int, w: int, device=None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """Normalised pixel-coordinate map (B,2,h,w) in [-1,1], channel 0 = y, channel 1 = x: the lens-shading branch's input x[2]
     (upstream never published its generator; build convention).  Plain tensor construction, no kernel."""

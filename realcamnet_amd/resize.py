@@ -12,6 +12,7 @@ from typing import Optional, Tuple
 from . import _lib
 from .look import Lut3D
 from .out_format import OutFormat
+from .stats import Stats
 from .warp import Warp
 
 FILTERS = {"area": _lib.RC_FILTER_AREA, "bilinear": _lib.RC_FILTER_BILINEAR}
@@ -98,7 +99,8 @@ class Output:
     """One entry of forward_mosaic(outputs=[...]): an optional Warp of the float result, an optional Resize, an optional colour look, then
     its format.
 
-    format  None (the planar float tensor), "rgb8" / "rgb16" (interleaved uint8 / uint16) or an OutFormat (a YuvFrames).
+    format  None (the planar float tensor), "rgb8" / "rgb16" (interleaved uint8 / uint16), an OutFormat (a YuvFrames) or a Stats (a
+            FrameStats: the statistics of the frame after this output's own warp / resize / look, in place of a picture).
     resize  None (the result's own size) or a Resize.
     look    None or a Lut3D, applied after the resize and before the encoder (ops.lut3d; with format None the looked tensor is fp32).
     warp    None or a Warp, applied first (ops.warp, fp32): the resize's window and the format then see a frame of warp.size.
@@ -111,10 +113,10 @@ class Output:
 
     def __post_init__(self):
         f = self.format
-        if f is not None and not isinstance(f, (str, OutFormat)):
-            raise TypeError(f"Output.format must be None, 'rgb8', 'rgb16' or an OutFormat, got {type(f).__name__}")
+        if f is not None and not isinstance(f, (str, OutFormat, Stats)):
+            raise TypeError(f"Output.format must be None, 'rgb8', 'rgb16', an OutFormat or a Stats, got {type(f).__name__}")
         if isinstance(f, str) and f not in ("rgb8", "rgb16"):
-            raise ValueError(f"Output.format must be None, 'rgb8', 'rgb16' or an OutFormat, got {f!r}")
+            raise ValueError(f"Output.format must be None, 'rgb8', 'rgb16', an OutFormat or a Stats, got {f!r}")
         if self.resize is not None and not isinstance(self.resize, Resize):
             raise TypeError(f"Output.resize must be None or a Resize, got {type(self.resize).__name__}")
         if self.look is not None and not isinstance(self.look, Lut3D):
@@ -136,4 +138,6 @@ class Output:
             h, w = self.resize.size
         if isinstance(self.format, OutFormat):
             self.format.plane_layout(h, w)
+        if isinstance(self.format, Stats):
+            self.format.check(h, w)
         return h, w

@@ -207,6 +207,25 @@ def _warp_launch(out, y, mesh, cell, interp, border, fill, h, w, oh, ow, dtype):
 define("warp(Tensor y, Tensor mesh, int cell, int interp, int border, float[] fill, int h, int w, int oh, int ow, ScalarType dtype) -> Tensor",
        lambda y, mesh, cell, interp, border, fill, h, w, oh, ow, dtype: y.new_empty((y.shape[0], 3, oh, ow), dtype=dtype), _warp_launch)
 
+def _stats_alloc(y, h, w, roi, gy, gx, bits, matrix, dark, clip):
+    return (y.new_empty((y.shape[0], 4, 1 << bits), dtype=torch.int64), y.new_empty((y.shape[0], gy, gx, _lib.RC_STATS_SLOTS), dtype=torch.int64))
+
+
+def _stats_launch(outs, y, h, w, roi, gy, gx, bits, matrix, dark, clip):
+    hist, zones = outs
+    if len(roi) != 4:
+        raise ValueError(f"realcam::frame_stats: roi must be (y0, x0, rh, rw), got {roi!r}")
+    d = _lib.StatsDesc(roi=(C.c_int32 * 4)(*roi), grid=(C.c_int32 * 2)(gy, gx), bits=bits, matrix=matrix, dark=dark, clip=clip)
+    check(lib().rc_frame_stats(y.data_ptr(), _dt(y), C.byref(d), hist.data_ptr(), zones.data_ptr(), y.shape[0], y.shape[2], y.shape[3], h, w, _stream()),
+          "rc_frame_stats")
+
+
+# y (B,3,H,W) planar, cropped to the frame (h,w) -> hist (B,4,2^bits) and zones (B,gy,gx,8), int64: the code histograms and the 3A zone grid of
+# the region roi = (y0, x0, rh, rw); matrix: the rc_yuv_matrix enum; dark / clip: code thresholds (-1 / 2^bits: none).  The outputs are not
+# zeroed here: the entry point does that on the stream
+define("frame_stats(Tensor y, int h, int w, int[] roi, int gy, int gx, int bits, int matrix, int dark, int clip) -> (Tensor, Tensor)",
+       _stats_alloc, _stats_launch)
+
 define("nchw_to_nhwc(Tensor x, ScalarType dtype, int hp, int wp) -> Tensor",
        lambda x, dtype, hp, wp: x.new_empty((x.shape[0], hp, wp, x.shape[1]), dtype=dtype),
        lambda out, x, dtype, hp, wp: check(lib().rc_nchw_to_nhwc(x.data_ptr(), _dt(x), out.data_ptr(), _DT[dtype], x.shape[0], x.shape[1],
