@@ -317,6 +317,49 @@ size_t rc_stats_desc_size(void);
 int rc_frame_stats(const void* d_src, int src_dtype, const rc_stats_desc* desc, long long* d_hist, long long* d_zones,
                    int batch, int H, int W, int h, int w, void* stream);
 
+/* ---- defective-pixel correction (ABI 15, additive): the first box of the input side, on the mosaic itself, before the ingest ------------
+ * Replaces: unpacking the RAW10 / RAW12 lines into a tensor, eight shifted fp32 planes, masked min / max / direction selects -- a dozen
+ * full-frame passes.  Here one launch over the bytes the ingest reads anyway; the one stage that is a stencil. */
+#define RC_DEFECT_HOT 1           /* rc_defect_desc.flags: the dynamic hot test is on */
+#define RC_DEFECT_COLD 2          /* ... the dynamic cold test is on */
+typedef struct rc_defect_desc {
+    int flags;             /* RC_DEFECT_HOT | RC_DEFECT_COLD, or 0 (then d_map is required: something must be enabled) */
+    float hot_abs, hot_rel;    /* t = hot_abs + hot_rel max(hi - black, 0); both finite and >= 0; in the storage's own units, as the levels */
+    float cold_abs, cold_rel;  /* t = cold_abs + cold_rel max(lo - black, 0) */
+    int reserved[3];       /* zero */
+} rc_defect_desc;
+size_t rc_defect_desc_size(void);
+
+/* src: the mosaic (B, 2h, 2w) as rc_raw_ingest_fmt reads it (fmt: storage, cfa, line_bytes, width, black; white is not looked
+ * at).  d_map: NULL (no static map) or the defect bitmap, one bit per mosaic sample: sample (y, x) is bit x & 31 of dword
+ * x >> 5 of row y, rows map_pitch_bytes apart (a multiple of 4, >= 4 ceil(2w / 32)); one map serves every frame of the batch.
+ * d_dst (B, 2h, 2w), rows dst_pitch_bytes apart (0: dense), frames 2h rows apart: uint16 for RC_RAW_U16 / U8 / MIPI10 / MIPI12, the source
+ * type for RC_RAW_F32 / BF16 / F16; unpacked.  d_counts: NULL or (B, 3) int64: samples replaced from the map, as hot, as cold.
+ *
+ * v(y,x) is the decoded sample as fp32 (counts are exact).  pos = 2 (y & 1) + (x & 1); black[pos] is fmt->black[pos].  The ring of (y,x)
+ * is the eight positions (y + 2dy, x + 2dx), (dy,dx) in {-1,0,1}^2 \ (0,0): the nearest samples of the same colour.  A ring position is
+ * GOOD if it lies inside the frame and is not set in the map.  Every product and every sum is rounded on its own (no fused multiply-add).
+ *   1. a sample set in the map: the pairs, in the order H (x-2, x+2), V (y-2, y+2), D1 ((y-2,x-2), (y+2,x+2)), D2 ((y-2,x+2), (y+2,x-2));
+ *      among the pairs with both ends good the one with the smallest |a - b| (a tie: the first in that order): out = (a + b) 0.5.
+ *      No whole pair: out = the first good neighbour in the order W, E, N, S, NW, NE, SW, SE.  No good neighbour: out = v, not counted.
+ *   2. a sample not set in the map with at least one good ring neighbour; hi = max, lo = min over the good ring:
+ *      hot, if enabled:             t = hot_abs + hot_rel max(hi - black[pos], 0);   v - hi > t: out = hi, counted as hot;
+ *      otherwise cold, if enabled:  t = cold_abs + cold_rel max(lo - black[pos], 0); lo - v > t: out = lo, counted as cold;
+ *      otherwise out = v.  No good neighbour: out = v.
+ *   3. count storages store rint(out), half to even, as uint16 (only step 1's .5 can round); float storages store out rounded to nearest
+ *      even to the source type.  A sample that is not replaced keeps its exact value.
+ * Single pass: neighbours are always source samples, never corrected ones, so the result does not depend on the traversal order and is the
+ * same from run to run; the counts are integer atomics.  Frames holding NaN / Inf are outside this contract (no fault, any value).
+ * d_counts, when given, is zeroed on `stream` by the entry point itself, then one launch adds: capturable, and a graph replay starts from
+ * zero.  The library keeps no device buffer of its own.
+ * Null d_src / fmt / desc / d_dst, an unknown storage or cfa, line_bytes shorter than a row or no multiple of the sample size, fmt->width
+ * other than 0 or 2w, a RAW10 width not divisible by 4, a source misaligned for its sample (MIPI: 4 bytes), a map pitch that is too small
+ * or no multiple of 4 or a map not 4-byte aligned, a dst pitch shorter than a row or no multiple of the sample size, dst misaligned,
+ * d_counts not 8-byte aligned, a threshold that is negative or not finite, unknown flags, non-zero reserved (fmt's too), nothing enabled
+ * (flags == 0 and no map), more than 65535 frames: RC_ERR_INVALID before anything is enqueued. */
+int rc_raw_defects(const void* d_src, const rc_raw_format* fmt, const rc_defect_desc* desc, const void* d_map, int map_pitch_bytes,
+                   void* d_dst, int dst_pitch_bytes, long long* d_counts, int batch, int h, int w, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

@@ -259,8 +259,18 @@ class Color_Condition_GFM_LFM(nn.Module):
 
 def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, raw_format=None):
     """Front end shared by every forward_mosaic: packed NHWC RAW (+ the cond image when the caller did not bring one).
-    raw_format (a RawFormat): the sensor's CFA phase / storage / levels, decoded by the one-launch rc_raw_ingest_fmt."""
+    raw_format (a RawFormat): the sensor's CFA phase / storage / levels, decoded by the one-launch rc_raw_ingest_fmt.
+    raw_format.defects (a Defects): the mosaic is repaired first (ops.raw_defects, one launch) and the ingest then reads the corrected,
+    unpacked mosaic with the same CFA and levels; with defects.counts the (B,3) counts of this call are left in net.defect_counts.
+    A cond the caller supplies is used as it is: it is NOT corrected."""
     need_cond = hasattr(net, "classifier") and cond is None and not getattr(net, "cond_from_raw", False)
+    if raw_format is not None and raw_format.defects is not None:
+        import dataclasses
+        fixed = ops.raw_defects(mosaic, raw_format)
+        if raw_format.defects.counts:
+            fixed, net.__dict__["defect_counts"] = fixed
+        mosaic = fixed
+        raw_format = dataclasses.replace(raw_format, storage="float" if raw_format.storage == "float" else "u16", width=None, defects=None)
     if raw_format is not None:
         a, c = ops.raw_ingest(mosaic, dtype=dt, pad_to=pad_to, black_level=black_level, white_level=white_level, cond_hw=cond_hw,
                               raw_format=raw_format)

@@ -31,6 +31,7 @@ RC_WARP_BILINEAR, RC_WARP_BICUBIC = 0, 1
 RC_WARP_CLAMP, RC_WARP_CONSTANT = 0, 1
 RC_WARP_MIN_CELL_LOG2, RC_WARP_MAX_CELL_LOG2, RC_WARP_MAX_DIM = 3, 6, 1 << 23
 RC_STATS_MAX_GRID, RC_STATS_SLOTS = 64, 8
+RC_DEFECT_HOT, RC_DEFECT_COLD = 1, 2
 
 
 class ConvDesc(C.Structure):
@@ -92,6 +93,14 @@ class StatsDesc(C.Structure):
     ]
 
 
+class DefectDesc(C.Structure):
+    """Mirror of `struct rc_defect_desc`."""
+    _fields_ = [
+        ("flags", C.c_int32), ("hot_abs", C.c_float), ("hot_rel", C.c_float), ("cold_abs", C.c_float), ("cold_rel", C.c_float),
+        ("reserved", C.c_int32 * 3),
+    ]
+
+
 def declared_symbols() -> list[str]:
     """Every function the public header declares (used by the CPU-side ABI test)."""
     text = HEADER.read_text()
@@ -119,6 +128,8 @@ _SIGS = {
     "rc_warp": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_stats_desc_size": (_SZ, []),
     "rc_frame_stats": (C.c_int, [_P, _I, C.POINTER(StatsDesc), _P, _P, _I, _I, _I, _I, _I, _P]),
+    "rc_defect_desc_size": (_SZ, []),
+    "rc_raw_defects": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(DefectDesc), _P, _I, _P, _I, _P, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

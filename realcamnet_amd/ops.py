@@ -479,6 +479,8 @@ def _raw_ingest_fmt(mosaic, dtype, pad_to, black_level, white_level, cond_hw, fm
     if not isinstance(mosaic, torch.Tensor):
         raise TypeError("mosaic: expected a tensor")
     _, w2 = fmt.validate(mosaic.shape)
+    if fmt.defects is not None:
+        raise ValueError("raw_ingest does not correct defects: run ops.raw_defects first and ingest its result (forward_mosaic does both)")
     want = _RAW_TENSOR_DTYPE.get(fmt.storage)
     if want is None:
         _dt(mosaic)
@@ -496,6 +498,46 @@ def _raw_ingest_fmt(mosaic, dtype, pad_to, black_level, white_level, cond_hw, fm
         mosaic = mosaic[:, 0]
     return _R.raw_ingest_fmt(mosaic, dtype, int(pad_to), storage, CFAS[fmt.cfa], int(w2), list(fmt.blacks()), float(fmt.white_level),
                              int(cond_hw[0]), int(cond_hw[1]))
+
+
+def raw_defects(mosaic: torch.Tensor, raw_format, defects=None):
+    """Defective-pixel correction on the mosaic itself, in front of the ingest (rc_raw_defects; the arithmetic is fixed in
+    include/realcam_hip.h): a sensor frame as `raw_format` (a RawFormat) describes it -> the corrected mosaic (B,2h,2w), unpacked and dense:
+    uint16 for the u16 / u8 / mipi10 / mipi12 storages, the frame's own dtype for float.  `defects` (a Defects; default: raw_format.defects)
+    names the static map and the hot / cold thresholds; with defects.counts the result is (mosaic, counts), counts (B,3) int64 on the
+    device: replaced from the map, as hot, as cold.  One launch; the map's bitmap is kept on the device per (map, device); nothing is
+    synchronised.  Frames holding NaN / Inf are outside the contract."""
+    from .defects import Defects
+    from .raw_format import CFAS, RawFormat
+    if not isinstance(raw_format, RawFormat):
+        raise TypeError(f"raw_defects: raw_format must be a RawFormat, got {type(raw_format).__name__}")
+    defects = raw_format.defects if defects is None else defects
+    if not isinstance(defects, Defects):
+        raise TypeError(f"raw_defects: defects must be a Defects (or raw_format.defects set), got {type(defects).__name__}")
+    if not isinstance(mosaic, torch.Tensor):
+        raise TypeError("mosaic: expected a tensor")
+    h2, w2 = raw_format.validate(mosaic.shape)
+    defects.check(h2, w2)
+    want = _RAW_TENSOR_DTYPE.get(raw_format.storage)
+    if want is None:
+        _dt(mosaic)
+        storage = _DT[mosaic.dtype]                         # RC_RAW_F32 / BF16 / F16 are the rc_dtype values
+    else:
+        if mosaic.dtype != want:
+            raise TypeError(f"raw_format storage {raw_format.storage!r} takes a {want} tensor, got {mosaic.dtype}")
+        storage = _RAW_STORAGE[raw_format.storage]
+    mosaic = _req(mosaic, "mosaic")
+    if mosaic.dim() == 4:
+        mosaic = mosaic[:, 0]
+    words = None
+    if defects.map is not None:
+        if isinstance(mosaic, FakeTensor):                     # a trace: shapes only, nothing is built, copied or kept
+            words = mosaic.new_empty(defects.map.words.shape, dtype=torch.int32)
+        else:
+            words = defects.map.device_words(mosaic.device)
+    out, counts = _R.raw_defects(mosaic, words, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), defects.flags,
+                                 list(defects.thresholds()), defects.counts)
+    return (out, counts) if defects.counts else out
 
 
 def rgb_encode(y: torch.Tensor, bits: int, crop_hw: Optional[Tuple[int, int]] = None) -> torch.Tensor:

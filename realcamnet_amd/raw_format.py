@@ -28,6 +28,8 @@ class RawFormat:
     width        mosaic width 2w in samples; required for the MIPI storages (the tensor's last dimension is the line stride).
     black_level  one float, or four in CFA-position order (DNG BlackLevel order).
     white_level  must exceed every black level.
+    defects      None, or a Defects: forward_mosaic repairs the mosaic (ops.raw_defects: a static map and / or hot / cold thresholds, in
+                 this storage's own units) before it ingests it.  A map must have the mosaic's size.
     """
 
     cfa: str = "RGGB"
@@ -35,6 +37,7 @@ class RawFormat:
     width: Optional[int] = None
     black_level: Union[float, Tuple[float, float, float, float]] = 0.0
     white_level: float = 1.0
+    defects: Optional[object] = None
 
     @property
     def packed(self) -> bool:
@@ -85,4 +88,9 @@ class RawFormat:
             raise ValueError(f"RAW10 packs 4 samples in 5 bytes: the mosaic width must be a multiple of 4, got {w2}")
         if self.packed and x < self.min_line_bytes(w2):
             raise ValueError(f"{self.storage} line of {w2} samples needs {self.min_line_bytes(w2)} bytes, the tensor's lines have {x}")
+        if self.defects is not None:
+            from .defects import Defects
+            if not isinstance(self.defects, Defects):
+                raise TypeError(f"RawFormat.defects must be None or a Defects, got {type(self.defects).__name__}")
+            self.defects.check(h2, w2)
         return h2, w2

@@ -226,6 +226,36 @@ def _stats_launch(outs, y, h, w, roi, gy, gx, bits, matrix, dark, clip):
 define("frame_stats(Tensor y, int h, int w, int[] roi, int gy, int gx, int bits, int matrix, int dark, int clip) -> (Tensor, Tensor)",
        _stats_alloc, _stats_launch)
 
+_DEFECT_COUNT_STORAGES = (_lib.RC_RAW_U16, _lib.RC_RAW_U8, _lib.RC_RAW_MIPI10, _lib.RC_RAW_MIPI12)
+
+
+def _defects_alloc(src, map_words, storage, cfa, width, black, flags, thr, want_counts):
+    b, h2, _ = src.shape
+    return (src.new_empty((b, h2, width), dtype=torch.uint16 if storage in _DEFECT_COUNT_STORAGES else src.dtype),
+            src.new_empty((b, 3), dtype=torch.int64) if want_counts else _none(src))
+
+
+def _defects_launch(outs, src, map_words, storage, cfa, width, black, flags, thr, want_counts):
+    out, counts = outs
+    b, h2, x = src.shape
+    if len(black) != 4 or len(thr) != 4:
+        raise ValueError(f"realcam::raw_defects: black and thr hold four floats each, got {black!r} and {thr!r}")
+    if src.data_ptr() % 4:
+        src = src.clone()                       # MIPI lines are read as whole dwords from a 4-byte aligned base (a view may start mid-dword)
+    f = _lib.RawFormatDesc(storage=storage, cfa=cfa, line_bytes=x * src.element_size(), width=width, white=0.0)
+    for k in range(4):
+        f.black[k] = float(black[k])
+    d = _lib.DefectDesc(flags=flags, hot_abs=thr[0], hot_rel=thr[1], cold_abs=thr[2], cold_rel=thr[3])
+    check(lib().rc_raw_defects(src.data_ptr(), C.byref(f), C.byref(d), _p(map_words), 0 if map_words is None else 4 * map_words.shape[1],
+                               out.data_ptr(), 0, counts.data_ptr() if want_counts else None, b, h2 // 2, width // 2, _stream()), "rc_raw_defects")
+
+
+# src (B, 2h, X) as raw_ingest_fmt takes it; map_words (2h, ceil(2w / 32)) int32 on the device or None; thr: hot_abs, hot_rel, cold_abs, cold_rel;
+# flags: RC_DEFECT_HOT | RC_DEFECT_COLD -> the corrected mosaic (B, 2h, 2w) (uint16 for the count storages, src's dtype for float) and the
+# (B, 3) int64 counts, (0,) when not wanted.  The counts are not zeroed here: the entry point does that on the stream
+define("raw_defects(Tensor src, Tensor? map_words, int storage, int cfa, int width, float[] black, int flags, float[] thr, bool want_counts) "
+       "-> (Tensor, Tensor)", _defects_alloc, _defects_launch)
+
 define("nchw_to_nhwc(Tensor x, ScalarType dtype, int hp, int wp) -> Tensor",
        lambda x, dtype, hp, wp: x.new_empty((x.shape[0], hp, wp, x.shape[1]), dtype=dtype),
        lambda out, x, dtype, hp, wp: check(lib().rc_nchw_to_nhwc(x.data_ptr(), _dt(x), out.data_ptr(), _DT[dtype], x.shape[0], x.shape[1],
