@@ -360,6 +360,56 @@ size_t rc_defect_desc_size(void);
 int rc_raw_defects(const void* d_src, const rc_raw_format* fmt, const rc_defect_desc* desc, const void* d_map, int map_pitch_bytes,
                    void* d_dst, int dst_pitch_bytes, long long* d_counts, int batch, int h, int w, void* stream);
 
+/* ---- sensor calibration (ABI 15, additive): linearisation, levels, flat-field gain map, white-balance gains, clip -- the second box of
+ * the input side, between the repaired samples and the ingest.
+ * Replaces: unpacking the lines into an fp32 tensor, bucketize + gather for the knee curve, F.interpolate of the gain map per CFA
+ * position, and a multiply per step -- several full-frame fp32 passes.  Here one launch over the bytes as delivered. */
+#define RC_CALIB_GAINS 1          /* rc_calib_desc.flags: gains[] holds the four gains */
+#define RC_CALIB_CLIP 2           /* ... clip_lo / clip_hi are applied */
+#define RC_CALIB_MAX_KNOTS 16
+typedef struct rc_calib_desc {
+    int flags;             /* RC_CALIB_GAINS | RC_CALIB_CLIP, or 0 */
+    int knots;             /* K: 0 (no curve) or 2 .. 16 */
+    int cell;              /* 0 (no gain map) or 8, 16, 32, 64, 128: a node every `cell` samples of a position's own h x w plane */
+    float curve_x[RC_CALIB_MAX_KNOTS];   /* strictly increasing, in the storage's own units */
+    float curve_y[RC_CALIB_MAX_KNOTS];   /* non-decreasing, in linear units: with a curve, fmt->black / white are in these units */
+    float gains[4];        /* CFA-position order, finite and >= 0 (RC_CALIB_GAINS) */
+    float clip_lo, clip_hi;    /* finite, lo < hi (RC_CALIB_CLIP) */
+    int reserved[3];       /* zero */
+} rc_calib_desc;
+size_t rc_calib_desc_size(void);
+
+/* src: the mosaic (B, 2h, 2w) as rc_raw_defects reads it (fmt: storage, cfa, line_bytes, width, black, white).  d_gain_map: NULL, or
+ * (4, Gh, Gw) fp32, dense, one plane per CFA position (0,0), (0,1), (1,0), (1,1), Gh = ceil(h / cell) + 1, Gw = ceil(w / cell) + 1; one map
+ * serves every frame.  d_frame_gains: NULL, or (frame_gains_batch, 4) fp32 on the device, frame_gains_batch = 1 (one row for every frame)
+ * or batch (one row per frame), read by the kernel when it runs: a loop that rewrites them needs no host sync, and a captured graph sees
+ * the new values on replay.  d_dst (B, 2h, 2w) of dst_dtype RC_F32 / RC_BF16 / RC_F16, rows dst_pitch_bytes apart (0: dense), frames 2h rows
+ * apart; unpacked.
+ *
+ * c is the decoded sample as fp32 (counts are exact).  pos = 2 (y & 1) + (x & 1); (Y, X) = (y >> 1, x >> 1); k = log2(cell).  Every product
+ * and every sum is rounded on its own (no fused multiply-add).  A step that is not enabled is skipped; step 2 always runs.
+ *   1. curve    j = the largest index <= K - 2 with x_j <= c, or 0 if c < x_0;  l = y_j + (c - x_j) s_j, where
+ *               s_j = (y_{j+1} - y_j) / (x_{j+1} - x_j) is formed in double on the host and rounded to fp32 once.  The end segments
+ *               extrapolate.  No curve: l = c.
+ *   2. levels   n = (l - black[pos]) inv[pos], inv[pos] = 1.f / (white - black[pos]) in fp32 on the host: rc_raw_ingest_fmt's own.
+ *   3. shading  j0 = Y >> k, i0 = X >> k; fy = (Y & (cell - 1)) 2^-k, fx = (X & (cell - 1)) 2^-k (exact); with g00, g01, g10, g11 the
+ *               nodes (j0, i0), (j0, i0 + 1), (j0 + 1, i0), (j0 + 1, i0 + 1) of plane pos:
+ *               top = g00 + fx (g01 - g00);  bot = g10 + fx (g11 - g10);  g = top + fy (bot - top);  m = n g.
+ *               top and bot depend on the column and the node row only.  A constant map multiplies by exactly that constant.
+ *   4. gains    m = m wb[pos]: desc->gains, or row (frame_gains_batch == 1 ? 0 : frame) of d_frame_gains.
+ *   5. clip     m = min(max(m, clip_lo), clip_hi).
+ *   6. store    round to nearest even into dst_dtype.
+ * Frames holding NaN / Inf are outside this contract (no fault, any value).  One launch, capturable; the library keeps no device buffer.
+ * Null d_src / fmt / desc / d_dst, an unknown storage, cfa or dst dtype, line_bytes shorter than a row or no multiple of the sample size,
+ * fmt->width other than 0 or 2w, a RAW10 width not divisible by 4, a source misaligned for its sample (MIPI: 4 bytes), a dst pitch shorter
+ * than a row or no multiple of the sample size, dst misaligned, a frame of 2 GiB or more (rows x pitch, either side), white <= a black level,
+ * a knot count other than 0 or 2 .. 16, knots out of order or not finite, a cell other than 0, 8 .. 128, a gain map pointer without a cell
+ * or a cell without a pointer, frame_gains_batch other than 1 or batch (0 without d_frame_gains), gains given both ways, a gain that is
+ * negative or not finite, clip_lo >= clip_hi or not finite, unknown flags, non-zero reserved (fmt's too), nothing enabled (no curve, map,
+ * gains or clip), more than 65535 frames: RC_ERR_INVALID before anything is enqueued. */
+int rc_raw_calibrate(const void* d_src, const rc_raw_format* fmt, const rc_calib_desc* desc, const float* d_gain_map, const float* d_frame_gains,
+                     int frame_gains_batch, void* d_dst, int dst_dtype, int dst_pitch_bytes, int batch, int h, int w, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

@@ -262,7 +262,11 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
     raw_format (a RawFormat): the sensor's CFA phase / storage / levels, decoded by the one-launch rc_raw_ingest_fmt.
     raw_format.defects (a Defects): the mosaic is repaired first (ops.raw_defects, one launch) and the ingest then reads the corrected,
     unpacked mosaic with the same CFA and levels; with defects.counts the (B,3) counts of this call are left in net.defect_counts.
-    A cond the caller supplies is used as it is: it is NOT corrected."""
+    raw_format.calibration (a Calibration): the samples (repaired first, when defects is set too: its thresholds apply to the codes as
+    delivered) are then linearised, normalised with the format's levels, flat-fielded, white-balanced and clipped by ops.raw_calibrate (one
+    launch) into an fp32 mosaic, and the ingest reads that with storage "float" and levels 0 / 1: the packed RAW and the cond image are
+    rounded to the network's type once, by the ingest, as without a calibration.
+    A cond the caller supplies is used as it is: it is NOT corrected and NOT calibrated."""
     need_cond = hasattr(net, "classifier") and cond is None and not getattr(net, "cond_from_raw", False)
     if raw_format is not None and raw_format.defects is not None:
         import dataclasses
@@ -271,6 +275,10 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
             fixed, net.__dict__["defect_counts"] = fixed
         mosaic = fixed
         raw_format = dataclasses.replace(raw_format, storage="float" if raw_format.storage == "float" else "u16", width=None, defects=None)
+    if raw_format is not None and raw_format.calibration is not None:
+        import dataclasses
+        mosaic = ops.raw_calibrate(mosaic, raw_format, dtype=torch.float32)
+        raw_format = dataclasses.replace(raw_format, storage="float", width=None, black_level=0.0, white_level=1.0, defects=None, calibration=None)
     if raw_format is not None:
         a, c = ops.raw_ingest(mosaic, dtype=dt, pad_to=pad_to, black_level=black_level, white_level=white_level, cond_hw=cond_hw,
                               raw_format=raw_format)

@@ -32,6 +32,7 @@ RC_WARP_CLAMP, RC_WARP_CONSTANT = 0, 1
 RC_WARP_MIN_CELL_LOG2, RC_WARP_MAX_CELL_LOG2, RC_WARP_MAX_DIM = 3, 6, 1 << 23
 RC_STATS_MAX_GRID, RC_STATS_SLOTS = 64, 8
 RC_DEFECT_HOT, RC_DEFECT_COLD = 1, 2
+RC_CALIB_GAINS, RC_CALIB_CLIP, RC_CALIB_MAX_KNOTS = 1, 2, 16
 
 
 class ConvDesc(C.Structure):
@@ -101,6 +102,14 @@ class DefectDesc(C.Structure):
     ]
 
 
+class CalibDesc(C.Structure):
+    """Mirror of `struct rc_calib_desc`."""
+    _fields_ = [
+        ("flags", C.c_int32), ("knots", C.c_int32), ("cell", C.c_int32), ("curve_x", C.c_float * 16), ("curve_y", C.c_float * 16),
+        ("gains", C.c_float * 4), ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("reserved", C.c_int32 * 3),
+    ]
+
+
 def declared_symbols() -> list[str]:
     """Every function the public header declares (used by the CPU-side ABI test)."""
     text = HEADER.read_text()
@@ -130,6 +139,8 @@ _SIGS = {
     "rc_frame_stats": (C.c_int, [_P, _I, C.POINTER(StatsDesc), _P, _P, _I, _I, _I, _I, _I, _P]),
     "rc_defect_desc_size": (_SZ, []),
     "rc_raw_defects": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(DefectDesc), _P, _I, _P, _I, _P, _I, _I, _I, _P]),
+    "rc_calib_desc_size": (_SZ, []),
+    "rc_raw_calibrate": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(CalibDesc), _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

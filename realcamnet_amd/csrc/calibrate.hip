@@ -1,0 +1,377 @@
+// Sensor calibration on the mosaic (include/realcam_hip.h, rc_raw_calibrate): the sensor frame as rc_raw_defects reads it (any storage,
+// padded lines) -> the linearised, normalised, flat-fielded, white-balanced mosaic (B, 2h, 2w) as fp32 / bf16 / fp16, unpacked.  Pointwise:
+// no halo, no LDS tile, no atomics.
+//
+// raw_calibrate_kernel: grid (pairs of strips, bands of 16 rows, frames), four waves per block.
+//   lane map   a STRIP is 256 columns.  Lane l of a wave holds the 4 consecutive samples 256 s + 4 l .. + 3 of a row.  Every lane's first
+//              column is a multiple of 4: one 4 / 8 / 16-byte load per lane and row for u8 / 16-bit / fp32 samples, 5 bytes of a RAW10
+//              line, 6 of a RAW12 line (whole dwords, as the ingest reads them), one 8- or 16-byte store; ragged frames (a base or pitch
+//              that is no multiple of 4 samples, the last two columns of a width that is 2 mod 4) go sample by sample.
+//   rows       waves 0, 2 of a block walk the even rows of the band downwards, waves 1, 3 the odd rows (waves 0, 1: the block's first
+//              strip; 2, 3: its second), so a wave sees two CFA positions only: its blacks, divisors and gains are six values read once.
+//              The raw bytes of the wave's next row are in flight while it works on this one.  Eight rows per wave: bands of 32 and 64
+//              rows measured slower.
+//   gain map   the lane's 4 samples are 2 plane columns X, X + 1 (X even) of each of the wave's two positions; a cell is >= 8 plane
+//              columns, so they share one node column.  When the node row changes (at most every 16 mosaic rows) the lane fetches the
+//              eight nodes (two positions x four corners; lanes of a cell ask for the same words, out of L2) and forms `top` and `bot` of
+//              its 2 x 2 (position, column) pairs; down the rows only g = top + fy (bot - top) is left.
+//   curve      the knots ride in the kernel's argument block; wave 0 lays them out in LDS once per block (16 slots of x_j, y_j, s_j; x_j of
+//              the unused slots is +inf) and every sample bisects them branch-free: at most four compares, then one 16-byte LDS read.
+// No division, no 64-bit address arithmetic per sample (a frame's offsets fit 32 bits: the entry point checks), no scratch.  The arithmetic
+// is step for step the header's: every product and sum rounded on its own.
+#include "common.hpp"
+
+#include <cmath>
+
+namespace rc {
+
+constexpr int kCalPx = 4, kCalWaves = 4, kCalThreads = 64 * kCalWaves;
+constexpr int kCalSpan = 64 * kCalPx;             // columns of a strip
+constexpr int kCalStrips = kCalWaves / 2;         // strips per block
+constexpr int kCalRows = 16;                      // rows per block
+constexpr int kCalKnots = RC_CALIB_MAX_KNOTS;
+
+enum { kCalElem = 0, kCalMipi10 = 1, kCalMipi12 = 2 };     // how a mosaic row is stored (raw_format.hip's three forms)
+
+struct CalArgs {
+    const uint8_t* src;        // mosaic row r of frame b starts at src + (b * H + r) * line_bytes
+    const float* map;          // (4, Gh, Gw) or null
+    const float* wb;           // (1 or B, 4) or null
+    uint8_t* dst;
+    int H, W;                  // the mosaic's rows and columns (2h, 2w)
+    int line_bytes, dst_pitch;
+    int vec_in, vec_out;       // every lane's 4 samples start on a 4-sample boundary of the source / the destination
+    int nseg;                  // curve segments (knots - 1), 0: no curve
+    int cell_log2, Gw, plane;  // gain map: log2(cell), nodes per row, nodes per position
+    int wb_stride;             // 0 (one row for every frame) or 4
+    int gains, clip;           // host gains on / clip on
+    float black[4], inv[4], gain[4];   // CFA-position order
+    float lo, hi;
+    float cx[kCalKnots], cy[kCalKnots], cs[kCalKnots];     // segment j: x_j, y_j and its slope; cx[j] = +inf past the last segment
+};
+
+struct CalRaw { uint32_t d[4]; };                 // a row's bytes as loaded (or, sample by sample, its 4 values)
+
+// raw_format.hip's load_window: the nb <= 6 bytes at p as a little-endian 64-bit window, read as whole dwords from the 4-byte boundary below p
+__device__ __forceinline__ void cal_window(const uint8_t* p, int nb, uint32_t* out) {
+    const uintptr_t ad = reinterpret_cast<uintptr_t>(p);
+    const uint32_t* d = reinterpret_cast<const uint32_t*>(ad & ~(uintptr_t)3);
+    const int sh = (int)(ad & 3), ndw = (sh + nb + 3) >> 2;
+    const uint32_t w0 = d[0];
+    const uint32_t w1 = ndw > 1 ? d[1] : 0u;
+    const uint32_t w2 = ndw > 2 ? d[2] : 0u;
+    const uint64_t lo = ((uint64_t)w1 << 32) | w0;
+    const uint64_t g = sh ? (lo >> (8 * sh)) | ((uint64_t)w2 << (64 - 8 * sh)) : lo;
+    out[0] = (uint32_t)g;
+    out[1] = (uint32_t)(g >> 32);
+}
+
+// Row y of the frame at columns x0 .. x0 + 3 (n of them inside the frame, n = 2 or 4; `full`: n == 4 and the lane may use one vector load).
+template <int ST, typename TI>
+__device__ __forceinline__ CalRaw cal_load(const uint8_t* frame, uint32_t line_bytes, int y, int x0, int n, bool full) {
+    CalRaw r = {{0u, 0u, 0u, 0u}};
+    const uint8_t* row = frame + (uint32_t)y * line_bytes;
+    if constexpr (ST == kCalElem) {
+        const TI* p = reinterpret_cast<const TI*>(row) + x0;
+        if (full) {
+            if constexpr (sizeof(TI) == 4) {
+                const uint4 q = *reinterpret_cast<const uint4*>(p);
+                r.d[0] = q.x; r.d[1] = q.y; r.d[2] = q.z; r.d[3] = q.w;
+            } else if constexpr (sizeof(TI) == 2) {
+                const uint2 q = *reinterpret_cast<const uint2*>(p);
+                r.d[0] = q.x; r.d[1] = q.y;
+            } else {
+                r.d[0] = *reinterpret_cast<const uint32_t*>(p);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kCalPx; ++k) r.d[k] = k < n ? __float_as_uint(to_f32(p[k])) : 0u;
+        }
+    } else if constexpr (ST == kCalMipi10) {                    // W % 4 == 0: always a whole 5-byte group
+        cal_window(row + (uint32_t)(x0 >> 2) * 5u, 5, r.d);
+    } else {                                                    // two 3-byte groups, or one at the end of a row of 2 mod 4 samples
+        cal_window(row + (uint32_t)(x0 >> 1) * 3u, n == 4 ? 6 : 3, r.d);
+    }
+    return r;
+}
+
+template <int ST, typename TI>
+__device__ __forceinline__ void cal_decode(const CalRaw& r, int n, bool full, float* v) {
+    if constexpr (ST == kCalElem) {
+        if (!full) {
+#pragma unroll
+            for (int k = 0; k < kCalPx; ++k) v[k] = __uint_as_float(r.d[k]);
+        } else if constexpr (__is_same(TI, float)) {
+#pragma unroll
+            for (int k = 0; k < kCalPx; ++k) v[k] = __uint_as_float(r.d[k]);
+        } else if constexpr (__is_same(TI, bf16_t)) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) { v[2 * j] = __uint_as_float(r.d[j] << 16); v[2 * j + 1] = __uint_as_float(r.d[j] & 0xffff0000u); }
+        } else if constexpr (__is_same(TI, f16_t)) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) { v[2 * j] = Vec16<f16_t>::lo(r.d[j]); v[2 * j + 1] = Vec16<f16_t>::hi(r.d[j]); }
+        } else if constexpr (sizeof(TI) == 2) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) { v[2 * j] = (float)(r.d[j] & 0xffffu); v[2 * j + 1] = (float)(r.d[j] >> 16); }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kCalPx; ++k) v[k] = (float)((r.d[0] >> (8 * k)) & 0xffu);
+        }
+    } else if constexpr (ST == kCalMipi10) {
+        const uint32_t lsb = r.d[1] & 0xffu;
+#pragma unroll
+        for (int k = 0; k < kCalPx; ++k) v[k] = (float)((((r.d[0] >> (8 * k)) & 0xffu) << 2) | ((lsb >> (2 * k)) & 3u));
+    } else {
+        const uint64_t g = ((uint64_t)r.d[1] << 32) | r.d[0];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const uint32_t b0 = (uint32_t)(g >> (24 * j)) & 0xffu, b1 = (uint32_t)(g >> (24 * j + 8)) & 0xffu, b2 = (uint32_t)(g >> (24 * j + 16)) & 0xffu;
+            const bool live = j == 0 || n == 4;
+            v[2 * j] = live ? (float)((b0 << 4) | (b2 & 15u)) : 0.f;
+            v[2 * j + 1] = live ? (float)((b1 << 4) | (b2 >> 4)) : 0.f;
+        }
+    }
+}
+
+// Step 1 of the header: segment j is the last one whose x_j <= c (segment 0 below x_1), then l = y_j + (c - x_j) s_j.  kx[j] = x_j, +inf past
+// the last segment, so the bisect over 16 slots needs no bound; seg[j] = (x_j, y_j, s_j, 0).  The steps a short curve cannot need are skipped
+// (wave-uniform: nseg is an argument).
+__device__ __forceinline__ float cal_curve(const float* kx, const float4* seg, int nseg, float c) {
+    int j = 0;
+    if (nseg > 7) j = c >= kx[8] ? 8 : 0;
+    if (nseg > 3) j = c >= kx[j + 4] ? j + 4 : j;
+    if (nseg > 1) {
+        j = c >= kx[j + 2] ? j + 2 : j;
+        j = c >= kx[j + 1] ? j + 1 : j;
+    }
+    const float4 q = seg[j];
+    return __fadd_rn(q.y, __fmul_rn(__fsub_rn(c, q.x), q.z));
+}
+
+template <typename TO>
+__device__ __forceinline__ uint32_t cal_bits(float v) {                            // step 6, as the low bits of a word
+    if constexpr (__is_same(TO, float)) return __float_as_uint(v);
+    else return (uint32_t)__builtin_bit_cast(uint16_t, from_f32<TO>(v));           // round to nearest even
+}
+
+template <typename TO>
+__device__ __forceinline__ void cal_store(TO* o, const float* v, int n, bool full) {
+    if (full) {
+        if constexpr (sizeof(TO) == 4) {
+            *reinterpret_cast<uint4*>(o) = make_uint4(cal_bits<TO>(v[0]), cal_bits<TO>(v[1]), cal_bits<TO>(v[2]), cal_bits<TO>(v[3]));
+        } else {
+            *reinterpret_cast<uint2*>(o) = make_uint2(cal_bits<TO>(v[0]) | (cal_bits<TO>(v[1]) << 16), cal_bits<TO>(v[2]) | (cal_bits<TO>(v[3]) << 16));
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kCalPx; ++k) {
+            if (k < n) {
+                if constexpr (sizeof(TO) == 4) reinterpret_cast<uint32_t*>(o)[k] = cal_bits<TO>(v[k]);
+                else reinterpret_cast<uint16_t*>(o)[k] = (uint16_t)cal_bits<TO>(v[k]);
+            }
+        }
+    }
+}
+
+template <int ST, typename TI, typename TO>
+__global__ void __launch_bounds__(kCalThreads) raw_calibrate_kernel(CalArgs a) {
+    __shared__ float4 seg[kCalKnots];                                              // the curve: 320 bytes, read per sample by its own index
+    __shared__ float kx[kCalKnots];
+    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (a.nseg) {                                                                  // block-uniform
+        if (wv == 0) {                                                             // every lane writes the same 16 slots: no indexed read of the arguments
+#pragma unroll
+            for (int j = 0; j < kCalKnots; ++j) {
+                seg[j] = make_float4(a.cx[j], a.cy[j], a.cs[j], 0.f);
+                kx[j] = a.cx[j];
+            }
+        }
+        __syncthreads();
+    }
+    const int par = wv & 1, strip = blockIdx.x * kCalStrips + (wv >> 1), frame = blockIdx.z;
+    const int x0 = strip * kCalSpan + lane * kCalPx;
+    if (x0 >= a.W) return;                                                         // no barrier and no lane exchange below
+    const int n = min(a.W - x0, kCalPx);                                           // W is even and x0 a multiple of 4: 2 or 4
+    const bool full_in = n == kCalPx && a.vec_in, full_out = n == kCalPx && a.vec_out;
+    const int r0 = blockIdx.y * kCalRows, r1 = min(r0 + kCalRows, a.H);
+    const uint8_t* src = a.src + (size_t)frame * (size_t)a.H * (size_t)a.line_bytes;
+    uint8_t* dst = a.dst + (size_t)frame * (size_t)a.H * (size_t)a.dst_pitch;
+    // r0 is even: y & 1 = par; x0 % 4 = 0: x & 1 = k & 1.  The wave's two positions are 2 par and 2 par + 1
+    const float black[2] = {a.black[2 * par], a.black[2 * par + 1]}, inv[2] = {a.inv[2 * par], a.inv[2 * par + 1]};
+    float wb[2] = {a.gain[2 * par], a.gain[2 * par + 1]};
+    const bool use_wb = a.wb != nullptr || a.gains;
+    if (a.wb) {
+        const float* row = a.wb + frame * a.wb_stride;
+        wb[0] = row[2 * par]; wb[1] = row[2 * par + 1];
+    }
+    const int k = a.cell_log2, cmask = (1 << k) - 1;
+    const float step = __uint_as_float((uint32_t)(127 - k) << 23);                 // 2^-k
+    const int X0 = x0 >> 1;                                                        // even: X0 and X0 + 1 lie in one cell
+    const float fx[2] = {__fmul_rn((float)(X0 & cmask), step), __fmul_rn((float)((X0 + 1) & cmask), step)};
+    const uint32_t node0 = (uint32_t)(X0 >> k);
+    float top[2][2] = {{1.f, 1.f}, {1.f, 1.f}}, bot[2][2] = {{1.f, 1.f}, {1.f, 1.f}};     // [position][column]
+    int node_row = -1;
+
+    int y = r0 + par;
+    if (y >= r1) return;
+    CalRaw ahead = cal_load<ST, TI>(src, (uint32_t)a.line_bytes, y, x0, n, full_in);
+    for (; y < r1; y += 2) {
+        const CalRaw raw = ahead;
+        if (y + 2 < r1) ahead = cal_load<ST, TI>(src, (uint32_t)a.line_bytes, y + 2, x0, n, full_in);     // in flight while this row is worked on
+        float v[kCalPx];
+        cal_decode<ST, TI>(raw, n, full_in, v);
+        float fy = 0.f;
+        if (a.map) {                                                               // wave-uniform
+            const int Y = y >> 1, j0 = Y >> k;
+            fy = __fmul_rn((float)(Y & cmask), step);
+            if (j0 != node_row) {                                                  // wave-uniform: at most every 16 rows
+                node_row = j0;
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    const float* g = a.map + ((uint32_t)(2 * par + p) * (uint32_t)a.plane + (uint32_t)j0 * (uint32_t)a.Gw + node0);
+                    const float g00 = g[0], g01 = g[1], g10 = g[a.Gw], g11 = g[a.Gw + 1];
+                    const float dt = __fsub_rn(g01, g00), db = __fsub_rn(g11, g10);
+#pragma unroll
+                    for (int c = 0; c < 2; ++c) {
+                        top[p][c] = __fadd_rn(g00, __fmul_rn(fx[c], dt));
+                        bot[p][c] = __fadd_rn(g10, __fmul_rn(fx[c], db));
+                    }
+                }
+            }
+        }
+        float o[kCalPx];
+#pragma unroll
+        for (int s = 0; s < kCalPx; ++s) {
+            const int p = s & 1, c = s >> 1;
+            float m = v[s];
+            if (a.nseg) m = cal_curve(kx, seg, a.nseg, m);
+            m = __fmul_rn(__fsub_rn(m, black[p]), inv[p]);
+            if (a.map) m = __fmul_rn(m, __fadd_rn(top[p][c], __fmul_rn(fy, __fsub_rn(bot[p][c], top[p][c]))));
+            if (use_wb) m = __fmul_rn(m, wb[p]);
+            if (a.clip) m = fminf(fmaxf(m, a.lo), a.hi);
+            o[s] = m;
+        }
+        cal_store<TO>(reinterpret_cast<TO*>(dst + (uint32_t)y * (uint32_t)a.dst_pitch) + x0, o, n, full_out);
+    }
+}
+
+}  // namespace rc
+
+using namespace rc;
+
+extern "C" {
+
+size_t rc_calib_desc_size(void) { return sizeof(rc_calib_desc); }
+
+int rc_raw_calibrate(const void* d_src, const rc_raw_format* fmt, const rc_calib_desc* desc, const float* d_gain_map, const float* d_frame_gains,
+                     int frame_gains_batch, void* d_dst, int dst_dtype, int dst_pitch_bytes, int batch, int h, int w, void* stream) {
+    RC_REQUIRE(d_src && fmt && desc && d_dst, "rc_raw_calibrate: null pointer");
+    RC_REQUIRE(batch >= 1 && batch <= 65535 && h >= 1 && w >= 1 && h <= (1 << 20) && w <= (1 << 24), "rc_raw_calibrate: bad shape (empty, more than 65535 frames, or too large)");
+    const int st = fmt->storage;
+    RC_REQUIRE(st >= RC_RAW_F32 && st <= RC_RAW_MIPI12, "rc_raw_calibrate: unknown storage");
+    RC_REQUIRE(fmt->cfa >= RC_CFA_RGGB && fmt->cfa <= RC_CFA_GBRG, "rc_raw_calibrate: unknown cfa");
+    RC_REQUIRE(dst_dtype == RC_F32 || dst_dtype == RC_BF16 || dst_dtype == RC_F16, "rc_raw_calibrate: dst dtype must be RC_F32, RC_BF16 or RC_F16");
+    RC_REQUIRE(fmt->reserved[0] == 0 && fmt->reserved[1] == 0 && fmt->reserved[2] == 0 && fmt->reserved[3] == 0,
+               "rc_raw_calibrate: the format's reserved fields must be zero");
+    RC_REQUIRE(desc->reserved[0] == 0 && desc->reserved[1] == 0 && desc->reserved[2] == 0, "rc_raw_calibrate: reserved fields must be zero");
+    RC_REQUIRE((desc->flags & ~(RC_CALIB_GAINS | RC_CALIB_CLIP)) == 0, "rc_raw_calibrate: unknown flags");
+    for (int p = 0; p < 4; ++p)
+        RC_REQUIRE(std::isfinite(fmt->black[p]) && std::isfinite(fmt->white) && fmt->white > fmt->black[p], "rc_raw_calibrate: white must exceed every black level (all finite)");
+    // the curve
+    const int K = desc->knots;
+    RC_REQUIRE(K == 0 || (K >= 2 && K <= RC_CALIB_MAX_KNOTS), "rc_raw_calibrate: a curve has 2 to 16 knots (0: no curve)");
+    for (int j = 0; j < K; ++j) {
+        RC_REQUIRE(std::isfinite(desc->curve_x[j]) && std::isfinite(desc->curve_y[j]), "rc_raw_calibrate: knots must be finite");
+        RC_REQUIRE(j == 0 || (desc->curve_x[j] > desc->curve_x[j - 1] && desc->curve_y[j] >= desc->curve_y[j - 1]),
+                   "rc_raw_calibrate: knots out of order (x strictly increasing, y non-decreasing)");
+    }
+    // the gain map
+    const int cell = desc->cell;
+    RC_REQUIRE(cell == 0 || cell == 8 || cell == 16 || cell == 32 || cell == 64 || cell == 128, "rc_raw_calibrate: cell must be 8, 16, 32, 64 or 128 (0: no gain map)");
+    RC_REQUIRE((cell != 0) == (d_gain_map != nullptr), "rc_raw_calibrate: a gain map needs both its pointer and its cell");
+    RC_REQUIRE(!d_gain_map || reinterpret_cast<uintptr_t>(d_gain_map) % 4 == 0, "rc_raw_calibrate: the gain map must be 4-byte aligned");
+    // the gains
+    const bool host_gains = (desc->flags & RC_CALIB_GAINS) != 0;
+    RC_REQUIRE(!(host_gains && d_frame_gains), "rc_raw_calibrate: gains given twice (RC_CALIB_GAINS and d_frame_gains)");
+    if (host_gains)
+        for (int p = 0; p < 4; ++p) RC_REQUIRE(std::isfinite(desc->gains[p]) && desc->gains[p] >= 0.f, "rc_raw_calibrate: gains must be finite and >= 0");
+    if (d_frame_gains) {
+        RC_REQUIRE(frame_gains_batch == 1 || frame_gains_batch == batch, "rc_raw_calibrate: frame_gains_batch must be 1 or the batch");
+        RC_REQUIRE(reinterpret_cast<uintptr_t>(d_frame_gains) % 4 == 0, "rc_raw_calibrate: the frame gains must be 4-byte aligned");
+    } else {
+        RC_REQUIRE(frame_gains_batch == 0, "rc_raw_calibrate: frame_gains_batch without d_frame_gains must be 0");
+    }
+    const bool clip = (desc->flags & RC_CALIB_CLIP) != 0;
+    if (clip) RC_REQUIRE(std::isfinite(desc->clip_lo) && std::isfinite(desc->clip_hi) && desc->clip_lo < desc->clip_hi, "rc_raw_calibrate: clip needs finite lo < hi");
+    RC_REQUIRE(K || cell || host_gains || d_frame_gains || clip, "rc_raw_calibrate: nothing enabled (no curve, no gain map, no gains, no clip)");
+    // the source and the destination
+    RC_REQUIRE(fmt->width == 0 || fmt->width == 2 * w, "rc_raw_calibrate: width must be 0 or the mosaic width 2w");
+    const bool mipi = st == RC_RAW_MIPI10 || st == RC_RAW_MIPI12;
+    RC_REQUIRE(st != RC_RAW_MIPI10 || (2 * w) % 4 == 0, "rc_raw_calibrate: RAW10 needs a mosaic width 2w divisible by 4");
+    const int esize = st == RC_RAW_F32 ? 4 : st == RC_RAW_U8 ? 1 : 2;
+    const long long need = st == RC_RAW_MIPI10 ? 2LL * w * 10 / 8 : st == RC_RAW_MIPI12 ? 2LL * w * 12 / 8 : 2LL * w * esize;
+    const long long lb = fmt->line_bytes ? fmt->line_bytes : need;
+    RC_REQUIRE(lb >= need && lb <= 0x7fffffffLL, "rc_raw_calibrate: line_bytes shorter than one mosaic row");
+    RC_REQUIRE(mipi || lb % esize == 0, "rc_raw_calibrate: line_bytes must be a multiple of the sample size");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % (mipi ? 4 : esize) == 0, "rc_raw_calibrate: source misaligned (MIPI: 4 bytes, else one sample)");
+    const int osize = dst_dtype == RC_F32 ? 4 : 2;
+    const long long dp = dst_pitch_bytes ? dst_pitch_bytes : 2LL * w * osize;
+    RC_REQUIRE(dp >= 2LL * w * osize && dp <= 0x7fffffffLL && dp % osize == 0, "rc_raw_calibrate: dst pitch shorter than one row or no multiple of the sample size");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_dst) % osize == 0, "rc_raw_calibrate: dst misaligned");
+    // a frame's byte offsets are formed in 32 bits
+    RC_REQUIRE(2LL * h * lb <= 0x7fffffffLL && 2LL * h * dp <= 0x7fffffffLL, "rc_raw_calibrate: a frame (rows x pitch) must stay below 2 GiB");
+
+    CalArgs a;
+    a.src = static_cast<const uint8_t*>(d_src);
+    a.map = d_gain_map;
+    a.wb = d_frame_gains;
+    a.dst = static_cast<uint8_t*>(d_dst);
+    a.H = 2 * h; a.W = 2 * w;
+    a.line_bytes = (int)lb; a.dst_pitch = (int)dp;
+    a.vec_in = !mipi && reinterpret_cast<uintptr_t>(d_src) % (kCalPx * esize) == 0 && lb % (kCalPx * esize) == 0;
+    a.vec_out = reinterpret_cast<uintptr_t>(d_dst) % (kCalPx * osize) == 0 && dp % (kCalPx * osize) == 0;
+    a.nseg = K ? K - 1 : 0;
+    a.cell_log2 = 0; a.Gw = 0; a.plane = 0;
+    if (cell) {
+        while ((1 << a.cell_log2) < cell) ++a.cell_log2;
+        const int gh = ceil_div(h, cell) + 1;
+        a.Gw = ceil_div(w, cell) + 1;
+        a.plane = gh * a.Gw;                                     // h w < 2^29 (the 2 GiB bound), cell >= 8: four planes fit 32 bits with room
+    }
+    a.wb_stride = d_frame_gains && frame_gains_batch > 1 ? 4 : 0;
+    a.gains = host_gains; a.clip = clip;
+    for (int p = 0; p < 4; ++p) {
+        a.black[p] = fmt->black[p];
+        a.inv[p] = 1.f / (fmt->white - fmt->black[p]);           // rc_raw_ingest_fmt's divisor: (v - black) * (1 / (white - black))
+        a.gain[p] = host_gains ? desc->gains[p] : 1.f;
+    }
+    a.lo = clip ? desc->clip_lo : 0.f; a.hi = clip ? desc->clip_hi : 0.f;
+    for (int j = 0; j < kCalKnots; ++j) {
+        const bool live = j < a.nseg;
+        a.cx[j] = live ? desc->curve_x[j] : INFINITY;
+        a.cy[j] = live ? desc->curve_y[j] : 0.f;
+        a.cs[j] = live ? (float)(((double)desc->curve_y[j + 1] - (double)desc->curve_y[j]) / ((double)desc->curve_x[j + 1] - (double)desc->curve_x[j])) : 0.f;
+    }
+    const hipStream_t s = as_stream(stream);
+    const dim3 grid((unsigned)ceil_div(ceil_div(a.W, kCalSpan), kCalStrips), (unsigned)ceil_div(a.H, kCalRows), (unsigned)batch), block(kCalThreads);
+#define LAUNCH3(ST, TI)                                                                                                \
+    do {                                                                                                               \
+        if (dst_dtype == RC_F32) hipLaunchKernelGGL((raw_calibrate_kernel<ST, TI, float>), grid, block, 0, s, a);      \
+        else if (dst_dtype == RC_BF16) hipLaunchKernelGGL((raw_calibrate_kernel<ST, TI, bf16_t>), grid, block, 0, s, a); \
+        else hipLaunchKernelGGL((raw_calibrate_kernel<ST, TI, f16_t>), grid, block, 0, s, a);                          \
+    } while (0)
+    switch (st) {
+        case RC_RAW_F32: LAUNCH3(kCalElem, float); break;
+        case RC_RAW_BF16: LAUNCH3(kCalElem, bf16_t); break;
+        case RC_RAW_F16: LAUNCH3(kCalElem, f16_t); break;
+        case RC_RAW_U16: LAUNCH3(kCalElem, uint16_t); break;
+        case RC_RAW_U8: LAUNCH3(kCalElem, uint8_t); break;
+        case RC_RAW_MIPI10: LAUNCH3(kCalMipi10, uint8_t); break;
+        default: LAUNCH3(kCalMipi12, uint8_t); break;
+    }
+#undef LAUNCH3
+    RC_HIP_CHECK(hipGetLastError());
+    return RC_OK;
+}
+
+}  // extern "C"

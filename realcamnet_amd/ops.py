@@ -481,6 +481,9 @@ def _raw_ingest_fmt(mosaic, dtype, pad_to, black_level, white_level, cond_hw, fm
     _, w2 = fmt.validate(mosaic.shape)
     if fmt.defects is not None:
         raise ValueError("raw_ingest does not correct defects: run ops.raw_defects first and ingest its result (forward_mosaic does both)")
+    if fmt.calibration is not None:
+        raise ValueError("raw_ingest does not calibrate: run ops.raw_calibrate first and ingest its float result with levels 0 / 1 "
+                         "(forward_mosaic does both)")
     want = _RAW_TENSOR_DTYPE.get(fmt.storage)
     if want is None:
         _dt(mosaic)
@@ -538,6 +541,64 @@ def raw_defects(mosaic: torch.Tensor, raw_format, defects=None):
     out, counts = _R.raw_defects(mosaic, words, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), defects.flags,
                                  list(defects.thresholds()), defects.counts)
     return (out, counts) if defects.counts else out
+
+
+def raw_calibrate(mosaic: torch.Tensor, raw_format, calibration=None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Sensor calibration on the mosaic itself, between the defects stage and the ingest (rc_raw_calibrate; the arithmetic is fixed in
+    include/realcam_hip.h): a sensor frame as `raw_format` (a RawFormat) describes it -> the calibrated mosaic (B,2h,2w) of `dtype` (fp32 /
+    bf16 / fp16), unpacked and dense.  `calibration` (a Calibration; default: raw_format.calibration) names the steps, skipped when None:
+    the linearisation curve, then always n = (l - black[pos]) / (white - black[pos]) with raw_format's levels (in the curve's linear units
+    when there is one), the flat-field gain map, the white-balance gains, the clip.  ops.raw_ingest of the result with storage "float" and
+    levels 0 / 1 continues as the ingest of the frame itself would.  One launch; the gain map is kept on the device per (map, device); a
+    gains tensor is read in place by the kernel; nothing is synchronised.  raw_format.defects must be None: run ops.raw_defects first.
+    Frames holding NaN / Inf are outside the contract."""
+    from .calibration import Calibration
+    from .raw_format import CFAS, RawFormat
+    if not isinstance(raw_format, RawFormat):
+        raise TypeError(f"raw_calibrate: raw_format must be a RawFormat, got {type(raw_format).__name__}")
+    calibration = raw_format.calibration if calibration is None else calibration
+    if not isinstance(calibration, Calibration):
+        raise TypeError(f"raw_calibrate: calibration must be a Calibration (or raw_format.calibration set), got {type(calibration).__name__}")
+    if raw_format.defects is not None:
+        raise ValueError("raw_calibrate does not correct defects: run ops.raw_defects first and calibrate its result (forward_mosaic does both)")
+    if not isinstance(mosaic, torch.Tensor):
+        raise TypeError("mosaic: expected a tensor")
+    h2, w2 = raw_format.validate(mosaic.shape)
+    calibration.check(h2, w2, mosaic.shape[0])
+    if dtype not in _DT:
+        raise TypeError(f"raw_calibrate: dtype must be fp32 / bf16 / fp16, got {dtype}")
+    want = _RAW_TENSOR_DTYPE.get(raw_format.storage)
+    if want is None:
+        _dt(mosaic)
+        storage = _DT[mosaic.dtype]                         # RC_RAW_F32 / BF16 / F16 are the rc_dtype values
+    else:
+        if mosaic.dtype != want:
+            raise TypeError(f"raw_format storage {raw_format.storage!r} takes a {want} tensor, got {mosaic.dtype}")
+        storage = _RAW_STORAGE[raw_format.storage]
+    mosaic = _req(mosaic, "mosaic")
+    if mosaic.dim() == 4:
+        mosaic = mosaic[:, 0]
+    gain_map, cell = None, 0
+    if calibration.shading is not None:
+        cell = calibration.shading.cell
+        if isinstance(mosaic, FakeTensor):                     # a trace: shapes only, nothing is built, copied or kept
+            gain_map = mosaic.new_empty(calibration.shading.gains.shape, dtype=torch.float32)
+        else:
+            gain_map = calibration.shading.device_gains(mosaic.device)
+    frame_gains, host_gains = None, []
+    if calibration.device_gains:
+        frame_gains = calibration.gains
+        if not frame_gains.is_cuda or frame_gains.device != mosaic.device:
+            raise RuntimeError(f"raw_calibrate: the gains tensor is on {frame_gains.device}, the mosaic on {mosaic.device}; give four host numbers "
+                               "or a tensor on the mosaic's device")
+        if not frame_gains.is_contiguous():
+            raise ValueError("raw_calibrate: the gains tensor must be contiguous (it is read in place, not copied)")
+    elif calibration.gains is not None:
+        host_gains = list(calibration.gains)
+    curve = calibration.curve
+    return _R.raw_calibrate(mosaic, gain_map, frame_gains, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), float(raw_format.white_level),
+                            [] if curve is None else list(curve.x), [] if curve is None else list(curve.y), cell, host_gains,
+                            [] if calibration.clip is None else list(calibration.clip), dtype)
 
 
 def rgb_encode(y: torch.Tensor, bits: int, crop_hw: Optional[Tuple[int, int]] = None) -> torch.Tensor:

@@ -30,6 +30,9 @@ class RawFormat:
     white_level  must exceed every black level.
     defects      None, or a Defects: forward_mosaic repairs the mosaic (ops.raw_defects: a static map and / or hot / cold thresholds, in
                  this storage's own units) before it ingests it.  A map must have the mosaic's size.
+    calibration  None, or a Calibration: forward_mosaic then runs ops.raw_calibrate (a linearisation curve, these levels, a flat-field gain
+                 map, white-balance gains, a clip) after the defects stage and ingests its fp32 result.  With a curve, black_level and
+                 white_level are in the curve's linear units.  A gain map must have the node count the mosaic needs.
     """
 
     cfa: str = "RGGB"
@@ -38,6 +41,7 @@ class RawFormat:
     black_level: Union[float, Tuple[float, float, float, float]] = 0.0
     white_level: float = 1.0
     defects: Optional[object] = None
+    calibration: Optional[object] = None
 
     @property
     def packed(self) -> bool:
@@ -93,4 +97,9 @@ class RawFormat:
             if not isinstance(self.defects, Defects):
                 raise TypeError(f"RawFormat.defects must be None or a Defects, got {type(self.defects).__name__}")
             self.defects.check(h2, w2)
+        if self.calibration is not None:
+            from .calibration import Calibration
+            if not isinstance(self.calibration, Calibration):
+                raise TypeError(f"RawFormat.calibration must be None or a Calibration, got {type(self.calibration).__name__}")
+            self.calibration.check(h2, w2, shape[0])
         return h2, w2

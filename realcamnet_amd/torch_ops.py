@@ -256,6 +256,37 @@ def _defects_launch(outs, src, map_words, storage, cfa, width, black, flags, thr
 define("raw_defects(Tensor src, Tensor? map_words, int storage, int cfa, int width, float[] black, int flags, float[] thr, bool want_counts) "
        "-> (Tensor, Tensor)", _defects_alloc, _defects_launch)
 
+
+
+def _calib_launch(out, src, gain_map, frame_gains, storage, cfa, width, black, white, curve_x, curve_y, cell, gains, clip, dtype):
+    b, h2, x = src.shape
+    if len(black) != 4 or len(gains) not in (0, 4) or len(clip) not in (0, 2) or len(curve_x) != len(curve_y) or len(curve_x) > _lib.RC_CALIB_MAX_KNOTS:
+        raise ValueError(f"realcam::raw_calibrate: black holds four floats, gains none or four, clip none or two, the curve at most "
+                         f"{_lib.RC_CALIB_MAX_KNOTS} knots; got {black!r}, {gains!r}, {clip!r}, {curve_x!r}, {curve_y!r}")
+    if storage in (_lib.RC_RAW_MIPI10, _lib.RC_RAW_MIPI12) and src.data_ptr() % 4:
+        src = src.clone()                       # MIPI lines are read as whole dwords from a 4-byte aligned base (a view may start mid-dword)
+    f = _lib.RawFormatDesc(storage=storage, cfa=cfa, line_bytes=x * src.element_size(), width=width, white=float(white))
+    for k in range(4):
+        f.black[k] = float(black[k])
+    d = _lib.CalibDesc(flags=(_lib.RC_CALIB_GAINS if gains else 0) | (_lib.RC_CALIB_CLIP if clip else 0), knots=len(curve_x), cell=cell)
+    for k, (cx, cy) in enumerate(zip(curve_x, curve_y)):
+        d.curve_x[k], d.curve_y[k] = float(cx), float(cy)
+    for k, g in enumerate(gains):
+        d.gains[k] = float(g)
+    if clip:
+        d.clip_lo, d.clip_hi = float(clip[0]), float(clip[1])
+    check(lib().rc_raw_calibrate(src.data_ptr(), C.byref(f), C.byref(d), _p(gain_map), _p(frame_gains), 0 if frame_gains is None else frame_gains.shape[0],
+                                 out.data_ptr(), _DT[dtype], 0, b, h2 // 2, width // 2, _stream()), "rc_raw_calibrate")
+
+
+# src (B, 2h, X) as raw_ingest_fmt takes it; gain_map (4, Gh, Gw) fp32 on the device or None (then cell 0); frame_gains (1 or B, 4) fp32 on the
+# device or None; curve_x / curve_y: the knots or empty; gains: four host gains or empty; clip: (lo, hi) or empty -> the calibrated mosaic
+# (B, 2h, 2w) of `dtype`
+define("raw_calibrate(Tensor src, Tensor? gain_map, Tensor? frame_gains, int storage, int cfa, int width, float[] black, float white, "
+       "float[] curve_x, float[] curve_y, int cell, float[] gains, float[] clip, ScalarType dtype) -> Tensor",
+       lambda src, gain_map, frame_gains, storage, cfa, width, black, white, curve_x, curve_y, cell, gains, clip, dtype:
+       src.new_empty((src.shape[0], src.shape[1], width), dtype=dtype), _calib_launch)
+
 define("nchw_to_nhwc(Tensor x, ScalarType dtype, int hp, int wp) -> Tensor",
        lambda x, dtype, hp, wp: x.new_empty((x.shape[0], hp, wp, x.shape[1]), dtype=dtype),
        lambda out, x, dtype, hp, wp: check(lib().rc_nchw_to_nhwc(x.data_ptr(), _dt(x), out.data_ptr(), _DT[dtype], x.shape[0], x.shape[1],
