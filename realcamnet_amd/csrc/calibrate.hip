@@ -19,7 +19,7 @@
 //              the unused slots is +inf) and every sample bisects them branch-free: at most four compares, then one 16-byte LDS read.
 // No division, no 64-bit address arithmetic per sample (a frame's offsets fit 32 bits: the entry point checks), no scratch.  The arithmetic
 // is step for step the header's: every product and sum rounded on its own.
-#include "common.hpp"
+#include "raw_row.hpp"
 
 #include <cmath>
 
@@ -30,8 +30,7 @@ constexpr int kCalSpan = 64 * kCalPx;             // columns of a strip
 constexpr int kCalStrips = kCalWaves / 2;         // strips per block
 constexpr int kCalRows = 16;                      // rows per block
 constexpr int kCalKnots = RC_CALIB_MAX_KNOTS;
-
-enum { kCalElem = 0, kCalMipi10 = 1, kCalMipi12 = 2 };     // how a mosaic row is stored (raw_format.hip's three forms)
+static_assert(kCalPx == kRowPx, "a lane holds the row reader's 4 samples");
 
 struct CalArgs {
     const uint8_t* src;        // mosaic row r of frame b starts at src + (b * H + r) * line_bytes
@@ -50,89 +49,6 @@ struct CalArgs {
     float cx[kCalKnots], cy[kCalKnots], cs[kCalKnots];     // segment j: x_j, y_j and its slope; cx[j] = +inf past the last segment
 };
 
-struct CalRaw { uint32_t d[4]; };                 // a row's bytes as loaded (or, sample by sample, its 4 values)
-
-// raw_format.hip's load_window: the nb <= 6 bytes at p as a little-endian 64-bit window, read as whole dwords from the 4-byte boundary below p
-__device__ __forceinline__ void cal_window(const uint8_t* p, int nb, uint32_t* out) {
-    const uintptr_t ad = reinterpret_cast<uintptr_t>(p);
-    const uint32_t* d = reinterpret_cast<const uint32_t*>(ad & ~(uintptr_t)3);
-    const int sh = (int)(ad & 3), ndw = (sh + nb + 3) >> 2;
-    const uint32_t w0 = d[0];
-    const uint32_t w1 = ndw > 1 ? d[1] : 0u;
-    const uint32_t w2 = ndw > 2 ? d[2] : 0u;
-    const uint64_t lo = ((uint64_t)w1 << 32) | w0;
-    const uint64_t g = sh ? (lo >> (8 * sh)) | ((uint64_t)w2 << (64 - 8 * sh)) : lo;
-    out[0] = (uint32_t)g;
-    out[1] = (uint32_t)(g >> 32);
-}
-
-// Row y of the frame at columns x0 .. x0 + 3 (n of them inside the frame, n = 2 or 4; `full`: n == 4 and the lane may use one vector load).
-template <int ST, typename TI>
-__device__ __forceinline__ CalRaw cal_load(const uint8_t* frame, uint32_t line_bytes, int y, int x0, int n, bool full) {
-    CalRaw r = {{0u, 0u, 0u, 0u}};
-    const uint8_t* row = frame + (uint32_t)y * line_bytes;
-    if constexpr (ST == kCalElem) {
-        const TI* p = reinterpret_cast<const TI*>(row) + x0;
-        if (full) {
-            if constexpr (sizeof(TI) == 4) {
-                const uint4 q = *reinterpret_cast<const uint4*>(p);
-                r.d[0] = q.x; r.d[1] = q.y; r.d[2] = q.z; r.d[3] = q.w;
-            } else if constexpr (sizeof(TI) == 2) {
-                const uint2 q = *reinterpret_cast<const uint2*>(p);
-                r.d[0] = q.x; r.d[1] = q.y;
-            } else {
-                r.d[0] = *reinterpret_cast<const uint32_t*>(p);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < kCalPx; ++k) r.d[k] = k < n ? __float_as_uint(to_f32(p[k])) : 0u;
-        }
-    } else if constexpr (ST == kCalMipi10) {                    // W % 4 == 0: always a whole 5-byte group
-        cal_window(row + (uint32_t)(x0 >> 2) * 5u, 5, r.d);
-    } else {                                                    // two 3-byte groups, or one at the end of a row of 2 mod 4 samples
-        cal_window(row + (uint32_t)(x0 >> 1) * 3u, n == 4 ? 6 : 3, r.d);
-    }
-    return r;
-}
-
-template <int ST, typename TI>
-__device__ __forceinline__ void cal_decode(const CalRaw& r, int n, bool full, float* v) {
-    if constexpr (ST == kCalElem) {
-        if (!full) {
-#pragma unroll
-            for (int k = 0; k < kCalPx; ++k) v[k] = __uint_as_float(r.d[k]);
-        } else if constexpr (__is_same(TI, float)) {
-#pragma unroll
-            for (int k = 0; k < kCalPx; ++k) v[k] = __uint_as_float(r.d[k]);
-        } else if constexpr (__is_same(TI, bf16_t)) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) { v[2 * j] = __uint_as_float(r.d[j] << 16); v[2 * j + 1] = __uint_as_float(r.d[j] & 0xffff0000u); }
-        } else if constexpr (__is_same(TI, f16_t)) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) { v[2 * j] = Vec16<f16_t>::lo(r.d[j]); v[2 * j + 1] = Vec16<f16_t>::hi(r.d[j]); }
-        } else if constexpr (sizeof(TI) == 2) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) { v[2 * j] = (float)(r.d[j] & 0xffffu); v[2 * j + 1] = (float)(r.d[j] >> 16); }
-        } else {
-#pragma unroll
-            for (int k = 0; k < kCalPx; ++k) v[k] = (float)((r.d[0] >> (8 * k)) & 0xffu);
-        }
-    } else if constexpr (ST == kCalMipi10) {
-        const uint32_t lsb = r.d[1] & 0xffu;
-#pragma unroll
-        for (int k = 0; k < kCalPx; ++k) v[k] = (float)((((r.d[0] >> (8 * k)) & 0xffu) << 2) | ((lsb >> (2 * k)) & 3u));
-    } else {
-        const uint64_t g = ((uint64_t)r.d[1] << 32) | r.d[0];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const uint32_t b0 = (uint32_t)(g >> (24 * j)) & 0xffu, b1 = (uint32_t)(g >> (24 * j + 8)) & 0xffu, b2 = (uint32_t)(g >> (24 * j + 16)) & 0xffu;
-            const bool live = j == 0 || n == 4;
-            v[2 * j] = live ? (float)((b0 << 4) | (b2 & 15u)) : 0.f;
-            v[2 * j + 1] = live ? (float)((b1 << 4) | (b2 >> 4)) : 0.f;
-        }
-    }
-}
-
 // Step 1 of the header: segment j is the last one whose x_j <= c (segment 0 below x_1), then l = y_j + (c - x_j) s_j.  kx[j] = x_j, +inf past
 // the last segment, so the bisect over 16 slots needs no bound; seg[j] = (x_j, y_j, s_j, 0).  The steps a short curve cannot need are skipped
 // (wave-uniform: nseg is an argument).
@@ -146,31 +62,6 @@ __device__ __forceinline__ float cal_curve(const float* kx, const float4* seg, i
     }
     const float4 q = seg[j];
     return __fadd_rn(q.y, __fmul_rn(__fsub_rn(c, q.x), q.z));
-}
-
-template <typename TO>
-__device__ __forceinline__ uint32_t cal_bits(float v) {                            // step 6, as the low bits of a word
-    if constexpr (__is_same(TO, float)) return __float_as_uint(v);
-    else return (uint32_t)__builtin_bit_cast(uint16_t, from_f32<TO>(v));           // round to nearest even
-}
-
-template <typename TO>
-__device__ __forceinline__ void cal_store(TO* o, const float* v, int n, bool full) {
-    if (full) {
-        if constexpr (sizeof(TO) == 4) {
-            *reinterpret_cast<uint4*>(o) = make_uint4(cal_bits<TO>(v[0]), cal_bits<TO>(v[1]), cal_bits<TO>(v[2]), cal_bits<TO>(v[3]));
-        } else {
-            *reinterpret_cast<uint2*>(o) = make_uint2(cal_bits<TO>(v[0]) | (cal_bits<TO>(v[1]) << 16), cal_bits<TO>(v[2]) | (cal_bits<TO>(v[3]) << 16));
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kCalPx; ++k) {
-            if (k < n) {
-                if constexpr (sizeof(TO) == 4) reinterpret_cast<uint32_t*>(o)[k] = cal_bits<TO>(v[k]);
-                else reinterpret_cast<uint16_t*>(o)[k] = (uint16_t)cal_bits<TO>(v[k]);
-            }
-        }
-    }
 }
 
 template <int ST, typename TI, typename TO>
@@ -214,12 +105,13 @@ __global__ void __launch_bounds__(kCalThreads) raw_calibrate_kernel(CalArgs a) {
 
     int y = r0 + par;
     if (y >= r1) return;
-    CalRaw ahead = cal_load<ST, TI>(src, (uint32_t)a.line_bytes, y, x0, n, full_in);
+    const uint32_t line_bytes = (uint32_t)a.line_bytes;
+    RowRaw ahead = row_load<ST, TI>(src + (uint32_t)y * line_bytes, x0, n, full_in);
     for (; y < r1; y += 2) {
-        const CalRaw raw = ahead;
-        if (y + 2 < r1) ahead = cal_load<ST, TI>(src, (uint32_t)a.line_bytes, y + 2, x0, n, full_in);     // in flight while this row is worked on
+        const RowRaw raw = ahead;
+        if (y + 2 < r1) ahead = row_load<ST, TI>(src + (uint32_t)(y + 2) * line_bytes, x0, n, full_in);     // in flight while this row is worked on
         float v[kCalPx];
-        cal_decode<ST, TI>(raw, n, full_in, v);
+        row_decode<ST, TI>(raw, n, full_in, v);
         float fy = 0.f;
         if (a.map) {                                                               // wave-uniform
             const int Y = y >> 1, j0 = Y >> k;
@@ -251,7 +143,7 @@ __global__ void __launch_bounds__(kCalThreads) raw_calibrate_kernel(CalArgs a) {
             if (a.clip) m = fminf(fmaxf(m, a.lo), a.hi);
             o[s] = m;
         }
-        cal_store<TO>(reinterpret_cast<TO*>(dst + (uint32_t)y * (uint32_t)a.dst_pitch) + x0, o, n, full_out);
+        row_store<TO>(reinterpret_cast<TO*>(dst + (uint32_t)y * (uint32_t)a.dst_pitch) + x0, o, n, full_out);
     }
 }
 
@@ -267,12 +159,10 @@ int rc_raw_calibrate(const void* d_src, const rc_raw_format* fmt, const rc_calib
                      int frame_gains_batch, void* d_dst, int dst_dtype, int dst_pitch_bytes, int batch, int h, int w, void* stream) {
     RC_REQUIRE(d_src && fmt && desc && d_dst, "rc_raw_calibrate: null pointer");
     RC_REQUIRE(batch >= 1 && batch <= 65535 && h >= 1 && w >= 1 && h <= (1 << 20) && w <= (1 << 24), "rc_raw_calibrate: bad shape (empty, more than 65535 frames, or too large)");
-    const int st = fmt->storage;
-    RC_REQUIRE(st >= RC_RAW_F32 && st <= RC_RAW_MIPI12, "rc_raw_calibrate: unknown storage");
-    RC_REQUIRE(fmt->cfa >= RC_CFA_RGGB && fmt->cfa <= RC_CFA_GBRG, "rc_raw_calibrate: unknown cfa");
+    RawSource rs;
+    if (const int e = raw_source("rc_raw_calibrate", d_src, fmt, w, &rs)) return e;
+    const long long lb = rs.line_bytes;
     RC_REQUIRE(dst_dtype == RC_F32 || dst_dtype == RC_BF16 || dst_dtype == RC_F16, "rc_raw_calibrate: dst dtype must be RC_F32, RC_BF16 or RC_F16");
-    RC_REQUIRE(fmt->reserved[0] == 0 && fmt->reserved[1] == 0 && fmt->reserved[2] == 0 && fmt->reserved[3] == 0,
-               "rc_raw_calibrate: the format's reserved fields must be zero");
     RC_REQUIRE(desc->reserved[0] == 0 && desc->reserved[1] == 0 && desc->reserved[2] == 0, "rc_raw_calibrate: reserved fields must be zero");
     RC_REQUIRE((desc->flags & ~(RC_CALIB_GAINS | RC_CALIB_CLIP)) == 0, "rc_raw_calibrate: unknown flags");
     for (int p = 0; p < 4; ++p)
@@ -304,16 +194,7 @@ int rc_raw_calibrate(const void* d_src, const rc_raw_format* fmt, const rc_calib
     const bool clip = (desc->flags & RC_CALIB_CLIP) != 0;
     if (clip) RC_REQUIRE(std::isfinite(desc->clip_lo) && std::isfinite(desc->clip_hi) && desc->clip_lo < desc->clip_hi, "rc_raw_calibrate: clip needs finite lo < hi");
     RC_REQUIRE(K || cell || host_gains || d_frame_gains || clip, "rc_raw_calibrate: nothing enabled (no curve, no gain map, no gains, no clip)");
-    // the source and the destination
-    RC_REQUIRE(fmt->width == 0 || fmt->width == 2 * w, "rc_raw_calibrate: width must be 0 or the mosaic width 2w");
-    const bool mipi = st == RC_RAW_MIPI10 || st == RC_RAW_MIPI12;
-    RC_REQUIRE(st != RC_RAW_MIPI10 || (2 * w) % 4 == 0, "rc_raw_calibrate: RAW10 needs a mosaic width 2w divisible by 4");
-    const int esize = st == RC_RAW_F32 ? 4 : st == RC_RAW_U8 ? 1 : 2;
-    const long long need = st == RC_RAW_MIPI10 ? 2LL * w * 10 / 8 : st == RC_RAW_MIPI12 ? 2LL * w * 12 / 8 : 2LL * w * esize;
-    const long long lb = fmt->line_bytes ? fmt->line_bytes : need;
-    RC_REQUIRE(lb >= need && lb <= 0x7fffffffLL, "rc_raw_calibrate: line_bytes shorter than one mosaic row");
-    RC_REQUIRE(mipi || lb % esize == 0, "rc_raw_calibrate: line_bytes must be a multiple of the sample size");
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % (mipi ? 4 : esize) == 0, "rc_raw_calibrate: source misaligned (MIPI: 4 bytes, else one sample)");
+    // the destination
     const int osize = dst_dtype == RC_F32 ? 4 : 2;
     const long long dp = dst_pitch_bytes ? dst_pitch_bytes : 2LL * w * osize;
     RC_REQUIRE(dp >= 2LL * w * osize && dp <= 0x7fffffffLL && dp % osize == 0, "rc_raw_calibrate: dst pitch shorter than one row or no multiple of the sample size");
@@ -328,7 +209,7 @@ int rc_raw_calibrate(const void* d_src, const rc_raw_format* fmt, const rc_calib
     a.dst = static_cast<uint8_t*>(d_dst);
     a.H = 2 * h; a.W = 2 * w;
     a.line_bytes = (int)lb; a.dst_pitch = (int)dp;
-    a.vec_in = !mipi && reinterpret_cast<uintptr_t>(d_src) % (kCalPx * esize) == 0 && lb % (kCalPx * esize) == 0;
+    a.vec_in = !rs.packed && reinterpret_cast<uintptr_t>(d_src) % (kCalPx * rs.esize) == 0 && lb % (kCalPx * rs.esize) == 0;
     a.vec_out = reinterpret_cast<uintptr_t>(d_dst) % (kCalPx * osize) == 0 && dp % (kCalPx * osize) == 0;
     a.nseg = K ? K - 1 : 0;
     a.cell_log2 = 0; a.Gw = 0; a.plane = 0;
@@ -360,14 +241,14 @@ int rc_raw_calibrate(const void* d_src, const rc_raw_format* fmt, const rc_calib
         else if (dst_dtype == RC_BF16) hipLaunchKernelGGL((raw_calibrate_kernel<ST, TI, bf16_t>), grid, block, 0, s, a); \
         else hipLaunchKernelGGL((raw_calibrate_kernel<ST, TI, f16_t>), grid, block, 0, s, a);                          \
     } while (0)
-    switch (st) {
-        case RC_RAW_F32: LAUNCH3(kCalElem, float); break;
-        case RC_RAW_BF16: LAUNCH3(kCalElem, bf16_t); break;
-        case RC_RAW_F16: LAUNCH3(kCalElem, f16_t); break;
-        case RC_RAW_U16: LAUNCH3(kCalElem, uint16_t); break;
-        case RC_RAW_U8: LAUNCH3(kCalElem, uint8_t); break;
-        case RC_RAW_MIPI10: LAUNCH3(kCalMipi10, uint8_t); break;
-        default: LAUNCH3(kCalMipi12, uint8_t); break;
+    switch (fmt->storage) {
+        case RC_RAW_F32: LAUNCH3(kElem, float); break;
+        case RC_RAW_BF16: LAUNCH3(kElem, bf16_t); break;
+        case RC_RAW_F16: LAUNCH3(kElem, f16_t); break;
+        case RC_RAW_U16: LAUNCH3(kElem, uint16_t); break;
+        case RC_RAW_U8: LAUNCH3(kElem, uint8_t); break;
+        case RC_RAW_MIPI10: LAUNCH3(kMipi10, uint8_t); break;
+        default: LAUNCH3(kMipi12, uint8_t); break;
     }
 #undef LAUNCH3
     RC_HIP_CHECK(hipGetLastError());

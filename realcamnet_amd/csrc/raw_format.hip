@@ -5,7 +5,7 @@
 // stride.  Same item split, same arithmetic, same stores: with an RGGB phase and four equal black levels it computes, value
 // for value, what raw_ingest_kernel computes from the same counts.
 // rgb_encode_kernel: planar (B,3,H,W) float result -> interleaved (B,h,w,3) uint8 / uint16, round-half-even and clamped.
-#include "common.hpp"
+#include "raw_row.hpp"
 
 namespace rc {
 
@@ -17,8 +17,6 @@ static inline int rf_grid(size_t n_items, int cap = 1 << 22) {
     if (g > (size_t)cap) g = cap;
     return (int)g;
 }
-
-enum { kElem = 0, kMipi10 = 1, kMipi12 = 2 };   // how a mosaic row is stored: one TI per sample, or MIPI CSI-2 packed bytes
 
 struct IngestArgs {
     const uint8_t* src;        // mosaic row r of frame b starts at src + (b * 2h + r) * line_bytes
@@ -36,25 +34,11 @@ __device__ __forceinline__ float sample(const uint8_t* row, int x) {
         return to_f32(reinterpret_cast<const TI*>(row)[x]);
     } else if constexpr (ST == kMipi10) {
         const uint8_t* g = row + (size_t)(x >> 2) * 5;
-        const int k = x & 3;
-        return (float)(((uint32_t)g[k] << 2) | ((uint32_t)(g[4] >> (2 * k)) & 3u));
+        return raw10_value(g[x & 3], g[4], x & 3);
     } else {
         const uint8_t* g = row + (size_t)(x >> 1) * 3;
-        const int k = x & 1;
-        return (float)(((uint32_t)g[k] << 4) | ((uint32_t)(g[2] >> (4 * k)) & 15u));
+        return raw12_value(g[x & 1], g[2], x & 1);
     }
-}
-
-// Bytes [s, s + nb) (nb <= 6) of a 4-byte aligned buffer as a little-endian 64-bit window, read as whole dwords: only the dwords
-// that hold at least one wanted byte are loaded, so nothing past the dword holding the buffer's last byte is touched.
-__device__ __forceinline__ uint64_t load_window(const uint8_t* base, size_t s, int nb) {
-    const uint32_t* d = reinterpret_cast<const uint32_t*>(base + (s & ~(size_t)3));
-    const int sh = (int)(s & 3), ndw = (sh + nb + 3) >> 2;
-    const uint32_t w0 = d[0];
-    const uint32_t w1 = ndw > 1 ? d[1] : 0u;
-    const uint32_t w2 = ndw > 2 ? d[2] : 0u;
-    const uint64_t lo = ((uint64_t)w1 << 32) | w0;
-    return sh ? (lo >> (8 * sh)) | ((uint64_t)w2 << (64 - 8 * sh)) : lo;
 }
 
 // Samples x0 .. x0 + n - 1 (n = 2 or 4, x0 % 4 == 0) of a mosaic row into v[0..3] (v[2], v[3] = 0 when n == 2).  A wave covers
@@ -65,21 +49,10 @@ __device__ __forceinline__ void load_quad(const uint8_t* row, size_t row_off, in
         const TI* p = reinterpret_cast<const TI*>(row + row_off) + x0;
         v[0] = to_f32(p[0]); v[1] = to_f32(p[1]);
         v[2] = n == 4 ? to_f32(p[2]) : 0.f; v[3] = n == 4 ? to_f32(p[3]) : 0.f;
-    } else if constexpr (ST == kMipi10) {                       // 2w % 4 == 0: always a whole 5-byte group
-        const uint64_t g = load_window(row, row_off + (size_t)(x0 >> 2) * 5, 5);
-        const uint32_t lsb = (uint32_t)(g >> 32) & 0xffu;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = (float)((((uint32_t)(g >> (8 * k)) & 0xffu) << 2) | ((lsb >> (2 * k)) & 3u));
-    } else {                                                    // two 3-byte groups, or one at the end of an odd-w row
-        const uint64_t g = load_window(row, row_off + (size_t)(x0 >> 1) * 3, n == 4 ? 6 : 3);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const uint32_t b0 = (uint32_t)(g >> (24 * j)) & 0xffu, b1 = (uint32_t)(g >> (24 * j + 8)) & 0xffu,
-                           b2 = (uint32_t)(g >> (24 * j + 16)) & 0xffu;
-            const bool live = j == 0 || n == 4;
-            v[2 * j] = live ? (float)((b0 << 4) | (b2 & 15u)) : 0.f;
-            v[2 * j + 1] = live ? (float)((b1 << 4) | (b2 >> 4)) : 0.f;
-        }
+    } else {
+        const uint64_t g = window_at(row, row_off + packed_offset<ST, size_t>(x0), packed_bytes<ST>(n));
+        if constexpr (ST == kMipi10) unpack_raw10(g, v);
+        else unpack_raw12(g, n, v);
     }
 }
 
@@ -232,21 +205,9 @@ int rc_raw_ingest_fmt(const void* d_src, const rc_raw_format* fmt, void* d_packe
     RC_REQUIRE(d_src && fmt && d_packed && d_cond, "rc_raw_ingest_fmt: null pointer");
     RC_REQUIRE(batch >= 1 && h >= 1 && w >= 1 && hp >= h && wp >= w && cond_h >= 1 && cond_w >= 1, "rc_raw_ingest_fmt: bad shape");
     RC_REQUIRE(out_dtype == RC_F32 || out_dtype == RC_BF16 || out_dtype == RC_F16, "rc_raw_ingest_fmt: bad dtype");
-    const int st = fmt->storage;
-    RC_REQUIRE(st >= RC_RAW_F32 && st <= RC_RAW_MIPI12, "rc_raw_ingest_fmt: unknown storage");
-    RC_REQUIRE(fmt->cfa >= RC_CFA_RGGB && fmt->cfa <= RC_CFA_GBRG, "rc_raw_ingest_fmt: unknown cfa");
-    RC_REQUIRE(fmt->reserved[0] == 0 && fmt->reserved[1] == 0 && fmt->reserved[2] == 0 && fmt->reserved[3] == 0,
-               "rc_raw_ingest_fmt: reserved fields must be zero");
-    RC_REQUIRE(fmt->width == 0 || fmt->width == 2 * w, "rc_raw_ingest_fmt: width must be 0 or the mosaic width 2w");
+    RawSource rs;
+    if (const int e = raw_source("rc_raw_ingest_fmt", d_src, fmt, w, &rs)) return e;
     for (int k = 0; k < 4; ++k) RC_REQUIRE(fmt->white > fmt->black[k], "rc_raw_ingest_fmt: white must exceed every black level");
-    const bool mipi = st == RC_RAW_MIPI10 || st == RC_RAW_MIPI12;
-    RC_REQUIRE(st != RC_RAW_MIPI10 || (2 * w) % 4 == 0, "rc_raw_ingest_fmt: RAW10 needs a mosaic width 2w divisible by 4");
-    const int esize = st == RC_RAW_F32 ? 4 : st == RC_RAW_U8 ? 1 : 2;
-    const long long need = st == RC_RAW_MIPI10 ? 2LL * w * 10 / 8 : st == RC_RAW_MIPI12 ? 2LL * w * 12 / 8 : 2LL * w * esize;
-    const long long lb = fmt->line_bytes ? fmt->line_bytes : need;
-    RC_REQUIRE(lb >= need, "rc_raw_ingest_fmt: line_bytes shorter than one mosaic row");
-    RC_REQUIRE(mipi || lb % esize == 0, "rc_raw_ingest_fmt: line_bytes must be a multiple of the sample size");
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % (mipi ? 4 : esize) == 0, "rc_raw_ingest_fmt: source misaligned (MIPI: 4 bytes, else one sample)");
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_packed) % 16 == 0, "rc_raw_ingest_fmt: packed must be 16-byte aligned");
 
     // packed slot k (0 R, 1 G of the R row, 2 G of the B row, 3 B) <- cell position of that colour in the 2x2 cell
@@ -254,7 +215,7 @@ int rc_raw_ingest_fmt(const void* d_src, const rc_raw_format* fmt, void* d_packe
     IngestArgs a;
     a.src = static_cast<const uint8_t*>(d_src);
     a.batch = batch; a.h = h; a.w = w; a.hp = hp; a.wp = wp; a.ch = cond_h; a.cw = cond_w;
-    a.line_bytes = (int)lb;
+    a.line_bytes = (int)rs.line_bytes;
     a.pos = 0;
     for (int k = 0; k < 4; ++k) {
         const int pos = kSlotPos[fmt->cfa][k];
@@ -273,7 +234,7 @@ int rc_raw_ingest_fmt(const void* d_src, const rc_raw_format* fmt, void* d_packe
         else if (out_dtype == RC_BF16) LAUNCH(ST, TI, bf16_t);                      \
         else LAUNCH(ST, TI, f16_t);                                                 \
     } while (0)
-    switch (st) {
+    switch (fmt->storage) {
         case RC_RAW_F32: BY_OUT(kElem, float); break;
         case RC_RAW_BF16: BY_OUT(kElem, bf16_t); break;
         case RC_RAW_F16: BY_OUT(kElem, f16_t); break;

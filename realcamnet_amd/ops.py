@@ -470,35 +470,43 @@ _RAW_TENSOR_DTYPE = {"u16": torch.uint16, "u8": torch.uint8, "mipi10": torch.uin
 _RAW_STORAGE = {"u16": _lib.RC_RAW_U16, "u8": _lib.RC_RAW_U8, "mipi10": _lib.RC_RAW_MIPI10, "mipi12": _lib.RC_RAW_MIPI12}
 
 
-def _raw_ingest_fmt(mosaic, dtype, pad_to, black_level, white_level, cond_hw, fmt):
-    from .raw_format import CFAS, RawFormat
-    if not isinstance(fmt, RawFormat):
-        raise TypeError(f"raw_format must be a RawFormat, got {type(fmt).__name__}")
-    if black_level != 0.0 or white_level != 1.0:
-        raise ValueError("raw_format carries the black / white levels: leave black_level / white_level at their defaults")
+def _raw_source(mosaic, raw_format, who):
+    """The sensor frame the mosaic front-end ops read (raw_ingest(raw_format=), raw_defects, raw_calibrate): checks `mosaic` against `raw_format`
+    (a RawFormat) and returns the frame as a contiguous (B, 2h, X) tensor on the device, its rc_raw_storage and (2h, 2w).  `who` opens the
+    message that names the op."""
+    from .raw_format import RawFormat
+    if not isinstance(raw_format, RawFormat):
+        raise TypeError(f"{who}raw_format must be a RawFormat, got {type(raw_format).__name__}")
     if not isinstance(mosaic, torch.Tensor):
         raise TypeError("mosaic: expected a tensor")
-    _, w2 = fmt.validate(mosaic.shape)
+    hw = raw_format.validate(mosaic.shape)
+    want = _RAW_TENSOR_DTYPE.get(raw_format.storage)
+    if want is None:
+        _dt(mosaic)
+        storage = _DT[mosaic.dtype]                         # RC_RAW_F32 / BF16 / F16 are the rc_dtype values
+    else:
+        if mosaic.dtype != want:
+            raise TypeError(f"raw_format storage {raw_format.storage!r} takes a {want} tensor, got {mosaic.dtype}")
+        storage = _RAW_STORAGE[raw_format.storage]
+    mosaic = _req(mosaic, "mosaic")
+    return (mosaic[:, 0] if mosaic.dim() == 4 else mosaic), storage, hw
+
+
+def _raw_ingest_fmt(mosaic, dtype, pad_to, black_level, white_level, cond_hw, fmt):
+    from .raw_format import CFAS
+    mosaic, storage, (_, w2) = _raw_source(mosaic, fmt, "")
+    if black_level != 0.0 or white_level != 1.0:
+        raise ValueError("raw_format carries the black / white levels: leave black_level / white_level at their defaults")
     if fmt.defects is not None:
         raise ValueError("raw_ingest does not correct defects: run ops.raw_defects first and ingest its result (forward_mosaic does both)")
     if fmt.calibration is not None:
         raise ValueError("raw_ingest does not calibrate: run ops.raw_calibrate first and ingest its float result with levels 0 / 1 "
                          "(forward_mosaic does both)")
-    want = _RAW_TENSOR_DTYPE.get(fmt.storage)
-    if want is None:
-        _dt(mosaic)
-        storage = _DT[mosaic.dtype]                         # RC_RAW_F32 / BF16 / F16 are the rc_dtype values
-        dtype = dtype or mosaic.dtype
-    else:
-        if mosaic.dtype != want:
-            raise TypeError(f"raw_format storage {fmt.storage!r} takes a {want} tensor, got {mosaic.dtype}")
-        if dtype is None:
+    if dtype is None:
+        if fmt.storage in _RAW_STORAGE:
             raise ValueError(f"raw_ingest: give the activation dtype for a {fmt.storage} mosaic")
-        storage = _RAW_STORAGE[fmt.storage]
+        dtype = mosaic.dtype
     _DT[dtype]
-    mosaic = _req(mosaic, "mosaic")
-    if mosaic.dim() == 4:
-        mosaic = mosaic[:, 0]
     return _R.raw_ingest_fmt(mosaic, dtype, int(pad_to), storage, CFAS[fmt.cfa], int(w2), list(fmt.blacks()), float(fmt.white_level),
                              int(cond_hw[0]), int(cond_hw[1]))
 
@@ -511,27 +519,12 @@ def raw_defects(mosaic: torch.Tensor, raw_format, defects=None):
     device: replaced from the map, as hot, as cold.  One launch; the map's bitmap is kept on the device per (map, device); nothing is
     synchronised.  Frames holding NaN / Inf are outside the contract."""
     from .defects import Defects
-    from .raw_format import CFAS, RawFormat
-    if not isinstance(raw_format, RawFormat):
-        raise TypeError(f"raw_defects: raw_format must be a RawFormat, got {type(raw_format).__name__}")
+    from .raw_format import CFAS
+    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format, "raw_defects: ")
     defects = raw_format.defects if defects is None else defects
     if not isinstance(defects, Defects):
         raise TypeError(f"raw_defects: defects must be a Defects (or raw_format.defects set), got {type(defects).__name__}")
-    if not isinstance(mosaic, torch.Tensor):
-        raise TypeError("mosaic: expected a tensor")
-    h2, w2 = raw_format.validate(mosaic.shape)
     defects.check(h2, w2)
-    want = _RAW_TENSOR_DTYPE.get(raw_format.storage)
-    if want is None:
-        _dt(mosaic)
-        storage = _DT[mosaic.dtype]                         # RC_RAW_F32 / BF16 / F16 are the rc_dtype values
-    else:
-        if mosaic.dtype != want:
-            raise TypeError(f"raw_format storage {raw_format.storage!r} takes a {want} tensor, got {mosaic.dtype}")
-        storage = _RAW_STORAGE[raw_format.storage]
-    mosaic = _req(mosaic, "mosaic")
-    if mosaic.dim() == 4:
-        mosaic = mosaic[:, 0]
     words = None
     if defects.map is not None:
         if isinstance(mosaic, FakeTensor):                     # a trace: shapes only, nothing is built, copied or kept
@@ -553,31 +546,16 @@ def raw_calibrate(mosaic: torch.Tensor, raw_format, calibration=None, dtype: tor
     gains tensor is read in place by the kernel; nothing is synchronised.  raw_format.defects must be None: run ops.raw_defects first.
     Frames holding NaN / Inf are outside the contract."""
     from .calibration import Calibration
-    from .raw_format import CFAS, RawFormat
-    if not isinstance(raw_format, RawFormat):
-        raise TypeError(f"raw_calibrate: raw_format must be a RawFormat, got {type(raw_format).__name__}")
+    from .raw_format import CFAS
+    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format, "raw_calibrate: ")
     calibration = raw_format.calibration if calibration is None else calibration
     if not isinstance(calibration, Calibration):
         raise TypeError(f"raw_calibrate: calibration must be a Calibration (or raw_format.calibration set), got {type(calibration).__name__}")
     if raw_format.defects is not None:
         raise ValueError("raw_calibrate does not correct defects: run ops.raw_defects first and calibrate its result (forward_mosaic does both)")
-    if not isinstance(mosaic, torch.Tensor):
-        raise TypeError("mosaic: expected a tensor")
-    h2, w2 = raw_format.validate(mosaic.shape)
     calibration.check(h2, w2, mosaic.shape[0])
     if dtype not in _DT:
         raise TypeError(f"raw_calibrate: dtype must be fp32 / bf16 / fp16, got {dtype}")
-    want = _RAW_TENSOR_DTYPE.get(raw_format.storage)
-    if want is None:
-        _dt(mosaic)
-        storage = _DT[mosaic.dtype]                         # RC_RAW_F32 / BF16 / F16 are the rc_dtype values
-    else:
-        if mosaic.dtype != want:
-            raise TypeError(f"raw_format storage {raw_format.storage!r} takes a {want} tensor, got {mosaic.dtype}")
-        storage = _RAW_STORAGE[raw_format.storage]
-    mosaic = _req(mosaic, "mosaic")
-    if mosaic.dim() == 4:
-        mosaic = mosaic[:, 0]
     gain_map, cell = None, 0
     if calibration.shading is not None:
         cell = calibration.shading.cell

@@ -123,14 +123,19 @@ def _fmt_alloc(src, dtype, pad_to, storage, cfa, width, black, white, cond_h, co
             src.new_empty((b, 4, cond_h, cond_w), dtype=dtype))
 
 
+def _raw_source(src, storage, cfa, width, black, white):
+    """The rc_raw_format of the frame src (B, 2h, X) and the tensor to pass for it: src itself, or a copy when a MIPI frame starts mid-dword
+    (a view may; packed lines are read as whole dwords from a 4-byte aligned base, element storages need their own alignment only)."""
+    if storage in (_lib.RC_RAW_MIPI10, _lib.RC_RAW_MIPI12) and src.data_ptr() % 4:
+        src = src.clone()
+    return src, _lib.RawFormatDesc(storage=storage, cfa=cfa, line_bytes=src.shape[2] * src.element_size(), width=width,
+                                   black=(C.c_float * 4)(*(float(v) for v in black)), white=float(white))
+
+
 def _fmt_launch(outs, src, dtype, pad_to, storage, cfa, width, black, white, cond_h, cond_w):
     packed, cond = outs
-    b, h2, x = src.shape
-    if src.data_ptr() % 4:
-        src = src.clone()                       # MIPI lines are read as whole dwords from a 4-byte aligned base (a view may start mid-dword)
-    d = _lib.RawFormatDesc(storage=storage, cfa=cfa, line_bytes=x * src.element_size(), width=width, white=float(white))
-    for k in range(4):
-        d.black[k] = float(black[k])
+    b, h2, _ = src.shape
+    src, d = _raw_source(src, storage, cfa, width, black, white)
     check(lib().rc_raw_ingest_fmt(src.data_ptr(), C.byref(d), packed.data_ptr(), cond.data_ptr(), _DT[dtype], b, h2 // 2, width // 2,
                                   packed.shape[1], packed.shape[2], cond_h, cond_w, _stream()), "rc_raw_ingest_fmt")
 
@@ -237,14 +242,10 @@ def _defects_alloc(src, map_words, storage, cfa, width, black, flags, thr, want_
 
 def _defects_launch(outs, src, map_words, storage, cfa, width, black, flags, thr, want_counts):
     out, counts = outs
-    b, h2, x = src.shape
+    b, h2, _ = src.shape
     if len(black) != 4 or len(thr) != 4:
         raise ValueError(f"realcam::raw_defects: black and thr hold four floats each, got {black!r} and {thr!r}")
-    if src.data_ptr() % 4:
-        src = src.clone()                       # MIPI lines are read as whole dwords from a 4-byte aligned base (a view may start mid-dword)
-    f = _lib.RawFormatDesc(storage=storage, cfa=cfa, line_bytes=x * src.element_size(), width=width, white=0.0)
-    for k in range(4):
-        f.black[k] = float(black[k])
+    src, f = _raw_source(src, storage, cfa, width, black, 0.0)
     d = _lib.DefectDesc(flags=flags, hot_abs=thr[0], hot_rel=thr[1], cold_abs=thr[2], cold_rel=thr[3])
     check(lib().rc_raw_defects(src.data_ptr(), C.byref(f), C.byref(d), _p(map_words), 0 if map_words is None else 4 * map_words.shape[1],
                                out.data_ptr(), 0, counts.data_ptr() if want_counts else None, b, h2 // 2, width // 2, _stream()), "rc_raw_defects")
@@ -259,15 +260,11 @@ define("raw_defects(Tensor src, Tensor? map_words, int storage, int cfa, int wid
 
 
 def _calib_launch(out, src, gain_map, frame_gains, storage, cfa, width, black, white, curve_x, curve_y, cell, gains, clip, dtype):
-    b, h2, x = src.shape
+    b, h2, _ = src.shape
     if len(black) != 4 or len(gains) not in (0, 4) or len(clip) not in (0, 2) or len(curve_x) != len(curve_y) or len(curve_x) > _lib.RC_CALIB_MAX_KNOTS:
         raise ValueError(f"realcam::raw_calibrate: black holds four floats, gains none or four, clip none or two, the curve at most "
                          f"{_lib.RC_CALIB_MAX_KNOTS} knots; got {black!r}, {gains!r}, {clip!r}, {curve_x!r}, {curve_y!r}")
-    if storage in (_lib.RC_RAW_MIPI10, _lib.RC_RAW_MIPI12) and src.data_ptr() % 4:
-        src = src.clone()                       # MIPI lines are read as whole dwords from a 4-byte aligned base (a view may start mid-dword)
-    f = _lib.RawFormatDesc(storage=storage, cfa=cfa, line_bytes=x * src.element_size(), width=width, white=float(white))
-    for k in range(4):
-        f.black[k] = float(black[k])
+    src, f = _raw_source(src, storage, cfa, width, black, white)
     d = _lib.CalibDesc(flags=(_lib.RC_CALIB_GAINS if gains else 0) | (_lib.RC_CALIB_CLIP if clip else 0), knots=len(curve_x), cell=cell)
     for k, (cx, cy) in enumerate(zip(curve_x, curve_y)):
         d.curve_x[k], d.curve_y[k] = float(cx), float(cy)

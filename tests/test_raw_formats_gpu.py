@@ -145,6 +145,29 @@ def test_mipi_line_stride_view_and_padding_bytes_are_ignored(hip):
 
 
 @pytest.mark.gpu
+def test_frames_that_start_mid_dword_equal_their_copies(hip):
+    """Only a MIPI frame whose base is not 4-byte aligned is copied before the launch; element storages are read where they lie (they need
+    their own alignment only).  A uint16 view one sample into its buffer, a uint8 view one byte in and a RAW12 view two bytes in give,
+    through the ingest, the defect correction and the calibration, bit for bit what their clones give."""
+    c = counts((1, 6, 12), 10, 7)
+    frames = (("u16", c, 1, dict(black_level=(64.0, 66.0, 60.0, 63.5), white_level=1023.0)),
+              ("u8", (c.to(torch.int32) >> 2).to(torch.uint8), 1, dict(black_level=(16.0, 17.0, 15.0, 16.0), white_level=255.0)),
+              ("mipi12", lines_of(c.to(torch.int32) * 4 + 3, 12), 2, dict(width=12, black_level=(256.0, 250.0, 261.0, 256.0), white_level=4095.0)))
+    spec = M.Defects(hot=(8.0, 0.1), cold=(8.0, 0.1), counts=True)
+    cal = M.Calibration(gains=(1.5, 1.0, 1.0, 2.0), clip=(0.0, 1.0))
+    for storage, frame, skip, kw in frames:
+        fmt = M.RawFormat(storage=storage, cfa="GRBG", **kw)
+        buf = torch.zeros(skip + frame.numel(), dtype=frame.dtype)
+        buf[skip:] = frame.flatten()
+        view = buf.to(DEV)[skip:].view(frame.shape)
+        assert view.data_ptr() % 4 == skip * frame.element_size()
+        for op in (lambda t: ops.raw_ingest(t, dtype=torch.float32, raw_format=fmt, cond_hw=(3, 5)), lambda t: ops.raw_defects(t, fmt, spec),
+                   lambda t: (ops.raw_calibrate(t, fmt, cal),)):
+            got, want = op(view), op(view.clone())
+            assert len(got) == len(want) and all(same(g, w) for g, w in zip(got, want)), storage
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("dt", DTS)
 def test_u8_equals_u16(hip, dt):
     c = counts((2, 1, 30, 46), 8, 3)

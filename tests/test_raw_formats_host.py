@@ -108,6 +108,7 @@ def _ingest(fmt, src=FAKE, packed=FAKE, cond=FAKE, out_dtype=RC_F32, b=1, h=8, w
     ("width mismatch", dict(fmt=_fmt(width=12)), b"width"),
     ("packed misaligned", dict(packed=FAKE + 8), b"16-byte"),
     ("MIPI source misaligned", dict(fmt=_fmt(storage=_lib.RC_RAW_MIPI12, width=16), src=FAKE + 2), b"misaligned"),
+    ("line past 2 GiB", dict(fmt=_fmt(storage=_lib.RC_RAW_F32), w=1 << 28, wp=1 << 28), b"line_bytes"),       # 2w x 4 bytes = 2^31: no int
 ])
 def test_raw_ingest_fmt_bad_arguments_are_reported(case, kwargs, msg):
     kwargs = dict(kwargs)
