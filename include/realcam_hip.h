@@ -410,6 +410,55 @@ size_t rc_calib_desc_size(void);
 int rc_raw_calibrate(const void* d_src, const rc_raw_format* fmt, const rc_calib_desc* desc, const float* d_gain_map, const float* d_frame_gains,
                      int frame_gains_batch, void* d_dst, int dst_dtype, int dst_pitch_bytes, int batch, int h, int w, void* stream);
 
+/* ---- multi-exposure HDR merge (ABI 15, additive): E = 2 .. 4 exposures of one scene -> one linear mosaic, between the defects stage (run per
+ * exposure) and the calibration.
+ * Replaces: a float copy of every exposure (the packed lines unpacked first), and a dozen elementwise passes over the E frames -- weights,
+ * masks, the sums and the quotient.  Here one launch over the bytes as delivered. */
+#define RC_HDR_MOTION 1           /* rc_hdr_desc.flags: motion_abs / motion_rel cut a longer exposure that disagrees with the shortest */
+typedef struct rc_hdr_desc {
+    int exposures;                 /* E, 2 .. 4 */
+    int flags;                     /* RC_HDR_MOTION, or 0 */
+    float times[4];                /* t_0 < t_1 < ..: exposure times or ratios (only their quotients matter), finite and positive; not looked
+                                      at when d_times is given */
+    float knee_lo, knee_hi;        /* finite, lo < hi, in the storage's own units (codes) */
+    float motion_abs, motion_rel;  /* finite and >= 0 (RC_HDR_MOTION) */
+    long long exposure_stride_bytes;   /* bytes from row r of exposure e to row r of exposure e + 1; 0: 2h line_bytes (whole frames, dense) */
+    long long frame_stride_bytes;      /* bytes from one frame of the batch (all its exposures) to the next; 0: E 2h line_bytes */
+    int reserved[4];               /* zero */
+} rc_hdr_desc;
+size_t rc_hdr_desc_size(void);
+
+/* src: B frames of E exposures of a mosaic (2h, 2w) as rc_raw_calibrate reads one (fmt: storage, cfa, line_bytes, width, black; white is not
+ * looked at).  Row r of exposure e of frame f starts at d_src + f frame_stride_bytes + e exposure_stride_bytes + r line_bytes, where
+ * fmt->line_bytes (0: one dense row) is the stride between rows of ONE exposure: whole frames (B, E, 2h, X) are the defaults above;
+ * line-interleaved readout (B, E 2h, X), row r of exposure e at tensor row r E + e, is line_bytes = E X, exposure_stride_bytes = X.
+ * Exposure 0 is the shortest.  d_times: NULL (desc->times), or (times_batch, E) fp32 on the device, times_batch = 1 (one row for every frame)
+ * or batch, read by the kernel when it runs: a loop that rewrites them needs no host sync, and a captured graph sees the new values on
+ * replay; device values are not checked (a value <= 0 or rows out of order: any result, no fault).  d_dst (B, 2h, 2w) fp32, rows
+ * dst_pitch_bytes apart (0: dense), frames 2h rows apart.
+ *
+ * c_e is the decoded sample of exposure e as fp32 (counts are exact), at (y, x); pos = 2 (y & 1) + (x & 1); b = black[pos].  Every product,
+ * every sum and every quotient is rounded to fp32 on its own (no fused multiply-add; both divisions correctly rounded).
+ *   1. linear   d_e = c_e - b;  l_e = d_e q_e,  q_e = t_0 / t_e (one fp32 division: on the host for desc->times, in the kernel per frame for
+ *               d_times -- the same bits).  l_e is in exposure 0's units.
+ *   2. knee     u_0 = 1.  e >= 1: u_e = 1 if c_e <= knee_lo, 0 if c_e >= knee_hi, otherwise (knee_hi - c_e) ik,
+ *               ik = (float)(1.0 / ((double)knee_hi - (double)knee_lo)) on the host.
+ *   3. motion   (RC_HDR_MOTION) e >= 1: u_e = 0 where |l_e - l_0| > motion_abs + motion_rel |l_0|.
+ *   4. sums     w_e = u_e t_e;  num = w_0 l_0, den = w_0;  then for e = 1 .. E - 1 in this order: num = num + w_e l_e, den = den + w_e.
+ *   5. result   m = b + num / den  (den >= t_0 > 0).
+ * m is in exposure 0's code units: fmt->black / white mean for it what they meant for exposure 0, and the range the longer exposures add
+ * shows as fractional codes.  Non-finite samples of a float storage are outside this contract (no fault, any value).  One launch, capturable;
+ * the library keeps no device buffer.
+ * Null d_src / fmt / desc / d_dst, an unknown storage or cfa, line_bytes shorter than a row or no multiple of the sample size, fmt->width
+ * other than 0 or 2w, a RAW10 width not divisible by 4, a source misaligned for its sample (MIPI: 4 bytes), a black level that is not finite,
+ * E outside 2 .. 4, unknown flags, non-zero reserved (fmt's too), times_batch other than 1 or batch (0 without d_times), d_times not 4-byte
+ * aligned, host times that are not finite, positive and strictly increasing, knee_lo >= knee_hi or not finite, a motion threshold that is
+ * negative or not finite, a stride that is negative or no multiple of 4 bytes (MIPI) / of the sample size, a dst pitch shorter than a row or
+ * no multiple of 4, dst misaligned, a frame whose extent over all its exposures (or whose destination) reaches 2 GiB, more than 65535
+ * frames: RC_ERR_INVALID before anything is enqueued. */
+int rc_raw_hdr_merge(const void* d_src, const rc_raw_format* fmt, const rc_hdr_desc* desc, const float* d_times, int times_batch,
+                     void* d_dst, int dst_pitch_bytes, int batch, int h, int w, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

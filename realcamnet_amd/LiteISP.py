@@ -257,6 +257,27 @@ class Color_Condition_GFM_LFM(nn.Module):
         return vec.to(global_raw.dtype).view(vec.shape[0], vec.shape[1], 1, 1), ops.to_nchw(lfm)
 
 
+def _merge_exposures(net, mosaic, raw_format):
+    """raw_format.exposures (an Exposures): the tensor holds E exposures of each frame.  The defects stage, when asked for, runs on every
+    exposure (layout "frames": (B,E,...) viewed as (B E,...); net.defect_counts is then (B,E,3)); ops.raw_hdr_merge (one launch) fuses them
+    into one linear fp32 mosaic in the shortest exposure's code units.  Returns that mosaic and the format that describes it: storage
+    "float", the same CFA and levels, the calibration kept for the next stage."""
+    import dataclasses
+    h2, w2 = raw_format.validate(mosaic.shape)                # also: "lines" with defects, a curve with exposures
+    ex = raw_format.exposures
+    if raw_format.defects is not None:
+        b, e = mosaic.shape[0], ex.count
+        one = dataclasses.replace(raw_format, exposures=None, calibration=None)
+        fixed = ops.raw_defects(mosaic.reshape((b * e,) + tuple(mosaic.shape[2:])), one)
+        if raw_format.defects.counts:
+            fixed, counts = fixed
+            net.__dict__["defect_counts"] = counts.view(b, e, 3)
+        mosaic = fixed.view(b, e, h2, w2)
+        raw_format = dataclasses.replace(raw_format, storage="float" if raw_format.storage == "float" else "u16", width=None, defects=None)
+    merged = ops.raw_hdr_merge(mosaic, raw_format)
+    return merged, dataclasses.replace(raw_format, storage="float", width=None, exposures=None, defects=None)
+
+
 def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, raw_format=None):
     """Front end shared by every forward_mosaic: packed NHWC RAW (+ the cond image when the caller did not bring one).
     raw_format (a RawFormat): the sensor's CFA phase / storage / levels, decoded by the one-launch rc_raw_ingest_fmt.
@@ -266,8 +287,12 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
     delivered) are then linearised, normalised with the format's levels, flat-fielded, white-balanced and clipped by ops.raw_calibrate (one
     launch) into an fp32 mosaic, and the ingest reads that with storage "float" and levels 0 / 1: the packed RAW and the cond image are
     rounded to the network's type once, by the ingest, as without a calibration.
+    raw_format.exposures (an Exposures): the tensor holds E exposures of each frame; they are repaired one by one and merged first
+    (_merge_exposures), and the calibration and the ingest then read the merged fp32 mosaic with the same levels.
     A cond the caller supplies is used as it is: it is NOT corrected and NOT calibrated."""
     need_cond = hasattr(net, "classifier") and cond is None and not getattr(net, "cond_from_raw", False)
+    if raw_format is not None and raw_format.exposures is not None:
+        mosaic, raw_format = _merge_exposures(net, mosaic, raw_format)
     if raw_format is not None and raw_format.defects is not None:
         import dataclasses
         fixed = ops.raw_defects(mosaic, raw_format)
@@ -290,7 +315,8 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
 
 
 def _mosaic_hw(mosaic, raw_format):
-    """(2h, 2w) of the frame: the tensor's last two dimensions, or for MIPI-packed lines the height and raw_format.width."""
+    """(2h, 2w) of the frame: the tensor's last two dimensions, or for MIPI-packed lines the height and raw_format.width; with
+    raw_format.exposures, one exposure's."""
     if raw_format is None:
         return mosaic.shape[-2], mosaic.shape[-1]
     return raw_format.validate(mosaic.shape)

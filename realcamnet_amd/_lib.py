@@ -33,6 +33,7 @@ RC_WARP_MIN_CELL_LOG2, RC_WARP_MAX_CELL_LOG2, RC_WARP_MAX_DIM = 3, 6, 1 << 23
 RC_STATS_MAX_GRID, RC_STATS_SLOTS = 64, 8
 RC_DEFECT_HOT, RC_DEFECT_COLD = 1, 2
 RC_CALIB_GAINS, RC_CALIB_CLIP, RC_CALIB_MAX_KNOTS = 1, 2, 16
+RC_HDR_MOTION = 1
 
 
 class ConvDesc(C.Structure):
@@ -110,6 +111,15 @@ class CalibDesc(C.Structure):
     ]
 
 
+class HdrDesc(C.Structure):
+    """Mirror of `struct rc_hdr_desc`."""
+    _fields_ = [
+        ("exposures", C.c_int32), ("flags", C.c_int32), ("times", C.c_float * 4), ("knee_lo", C.c_float), ("knee_hi", C.c_float),
+        ("motion_abs", C.c_float), ("motion_rel", C.c_float), ("exposure_stride_bytes", C.c_longlong), ("frame_stride_bytes", C.c_longlong),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 def declared_symbols() -> list[str]:
     """Every function the public header declares (used by the CPU-side ABI test)."""
     text = HEADER.read_text()
@@ -141,6 +151,8 @@ _SIGS = {
     "rc_raw_defects": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(DefectDesc), _P, _I, _P, _I, _P, _I, _I, _I, _P]),
     "rc_calib_desc_size": (_SZ, []),
     "rc_raw_calibrate": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(CalibDesc), _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "rc_hdr_desc_size": (_SZ, []),
+    "rc_raw_hdr_merge": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(HdrDesc), _P, _I, _P, _I, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

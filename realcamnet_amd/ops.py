@@ -471,9 +471,10 @@ _RAW_STORAGE = {"u16": _lib.RC_RAW_U16, "u8": _lib.RC_RAW_U8, "mipi10": _lib.RC_
 
 
 def _raw_source(mosaic, raw_format, who):
-    """The sensor frame the mosaic front-end ops read (raw_ingest(raw_format=), raw_defects, raw_calibrate): checks `mosaic` against `raw_format`
-    (a RawFormat) and returns the frame as a contiguous (B, 2h, X) tensor on the device, its rc_raw_storage and (2h, 2w).  `who` opens the
-    message that names the op."""
+    """The sensor frame the mosaic front-end ops read (raw_ingest(raw_format=), raw_defects, raw_calibrate, raw_hdr_merge): checks `mosaic` against
+    `raw_format` (a RawFormat) and returns the frame as a contiguous (B, 2h, X) tensor on the device -- with raw_format.exposures set,
+    (B, E, 2h, X) or (B, E 2h, X) as its layout says -- its rc_raw_storage and (2h, 2w) of one exposure.  `who` opens the message that names
+    the op."""
     from .raw_format import RawFormat
     if not isinstance(raw_format, RawFormat):
         raise TypeError(f"{who}raw_format must be a RawFormat, got {type(raw_format).__name__}")
@@ -489,11 +490,21 @@ def _raw_source(mosaic, raw_format, who):
             raise TypeError(f"raw_format storage {raw_format.storage!r} takes a {want} tensor, got {mosaic.dtype}")
         storage = _RAW_STORAGE[raw_format.storage]
     mosaic = _req(mosaic, "mosaic")
+    if raw_format.exposures is not None:                        # raw_hdr_merge: (B, E, 2h, X) whole frames or (B, E 2h, X) interleaved lines
+        return (mosaic[:, 0] if mosaic.dim() == 4 and raw_format.exposures.layout == "lines" else mosaic), storage, hw
     return (mosaic[:, 0] if mosaic.dim() == 4 else mosaic), storage, hw
+
+
+def _one_exposure(raw_format, op):
+    """The single-exposure front-end ops refuse a format whose exposures are set, rather than read E frames as one."""
+    if getattr(raw_format, "exposures", None) is not None:
+        raise ValueError(f"{op} reads one exposure: merge first.  The order is ops.raw_defects (per exposure), ops.raw_hdr_merge, "
+                         "ops.raw_calibrate, ops.raw_ingest (forward_mosaic runs all four)")
 
 
 def _raw_ingest_fmt(mosaic, dtype, pad_to, black_level, white_level, cond_hw, fmt):
     from .raw_format import CFAS
+    _one_exposure(fmt, "raw_ingest")
     mosaic, storage, (_, w2) = _raw_source(mosaic, fmt, "")
     if black_level != 0.0 or white_level != 1.0:
         raise ValueError("raw_format carries the black / white levels: leave black_level / white_level at their defaults")
@@ -520,6 +531,7 @@ def raw_defects(mosaic: torch.Tensor, raw_format, defects=None):
     synchronised.  Frames holding NaN / Inf are outside the contract."""
     from .defects import Defects
     from .raw_format import CFAS
+    _one_exposure(raw_format, "raw_defects")
     mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format, "raw_defects: ")
     defects = raw_format.defects if defects is None else defects
     if not isinstance(defects, Defects):
@@ -547,6 +559,7 @@ def raw_calibrate(mosaic: torch.Tensor, raw_format, calibration=None, dtype: tor
     Frames holding NaN / Inf are outside the contract."""
     from .calibration import Calibration
     from .raw_format import CFAS
+    _one_exposure(raw_format, "raw_calibrate")
     mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format, "raw_calibrate: ")
     calibration = raw_format.calibration if calibration is None else calibration
     if not isinstance(calibration, Calibration):
@@ -577,6 +590,42 @@ def raw_calibrate(mosaic: torch.Tensor, raw_format, calibration=None, dtype: tor
     return _R.raw_calibrate(mosaic, gain_map, frame_gains, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), float(raw_format.white_level),
                             [] if curve is None else list(curve.x), [] if curve is None else list(curve.y), cell, host_gains,
                             [] if calibration.clip is None else list(calibration.clip), dtype)
+
+
+def raw_hdr_merge(mosaic: torch.Tensor, raw_format, exposures=None) -> torch.Tensor:
+    """Multi-exposure HDR merge on the mosaic itself, between the defects stage and the calibration (rc_raw_hdr_merge; the arithmetic is fixed
+    in include/realcam_hip.h): the E = 2 .. 4 exposures of each frame as `raw_format` (a RawFormat) describes them -- (B,E,2h,X) for
+    Exposures(layout="frames"), (B,[1,]E 2h,X) line-interleaved for "lines" -> one linear mosaic (B,2h,2w) fp32 in the shortest exposure's
+    code units, unpacked and dense.  `exposures` (an Exposures; default: raw_format.exposures) names the times, the knee and the motion cut.
+    One launch; a times tensor is read in place by the kernel; nothing is synchronised.  MIPI lines whose stride is no multiple of 4 bytes
+    are copied to such a stride first.  raw_format.defects must be None: run ops.raw_defects on each exposure first.  A Calibration.curve is
+    refused (the merge needs linear samples).  Non-finite samples are outside the contract."""
+    import dataclasses
+    from .exposures import Exposures
+    from .raw_format import CFAS, RawFormat
+    if not isinstance(raw_format, RawFormat):
+        raise TypeError(f"raw_hdr_merge: raw_format must be a RawFormat, got {type(raw_format).__name__}")
+    exposures = raw_format.exposures if exposures is None else exposures
+    if not isinstance(exposures, Exposures):
+        raise TypeError(f"raw_hdr_merge: exposures must be an Exposures (or raw_format.exposures set), got {type(exposures).__name__}")
+    if raw_format.defects is not None:
+        raise ValueError("raw_hdr_merge does not correct defects: run ops.raw_defects on each exposure first and merge its result "
+                         "(forward_mosaic does both)")
+    if raw_format.exposures is not exposures:
+        raw_format = dataclasses.replace(raw_format, exposures=exposures)
+    mosaic, storage, (_, w2) = _raw_source(mosaic, raw_format, "raw_hdr_merge: ")
+    times, host_times = None, []
+    if exposures.device_times:
+        times = exposures.times
+        if not times.is_cuda or times.device != mosaic.device:
+            raise RuntimeError(f"raw_hdr_merge: the times tensor is on {times.device}, the mosaic on {mosaic.device}; give host numbers or a "
+                               "tensor on the mosaic's device")
+        if not times.is_contiguous():
+            raise ValueError("raw_hdr_merge: the times tensor must be contiguous (it is read in place, not copied)")
+    else:
+        host_times = list(exposures.times)
+    return _R.raw_hdr_merge(mosaic, times, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), exposures.count,
+                            exposures.layout == "lines", host_times, list(exposures.knee), [] if exposures.motion is None else list(exposures.motion))
 
 
 def rgb_encode(y: torch.Tensor, bits: int, crop_hw: Optional[Tuple[int, int]] = None) -> torch.Tensor:

@@ -28,6 +28,11 @@ class RawFormat:
     width        mosaic width 2w in samples; required for the MIPI storages (the tensor's last dimension is the line stride).
     black_level  one float, or four in CFA-position order (DNG BlackLevel order).
     white_level  must exceed every black level.
+    exposures    None, or an Exposures: the tensor holds E = 2 .. 4 exposures of each frame, (B,E,2h,X) for its layout "frames" or
+                 (B,[1,]E 2h,X) line-interleaved for "lines", and forward_mosaic merges them (ops.raw_hdr_merge) into one linear fp32
+                 mosaic in the shortest exposure's code units -- after the defects stage, which then runs per exposure, and in front of
+                 the calibration.  The levels are the shortest exposure's; a calibration must not carry a curve (the merge needs linear
+                 samples), and layout "lines" takes no defects (de-interleave first).
     defects      None, or a Defects: forward_mosaic repairs the mosaic (ops.raw_defects: a static map and / or hot / cold thresholds, in
                  this storage's own units) before it ingests it.  A map must have the mosaic's size.
     calibration  None, or a Calibration: forward_mosaic then runs ops.raw_calibrate (a linearisation curve, these levels, a flat-field gain
@@ -40,6 +45,7 @@ class RawFormat:
     width: Optional[int] = None
     black_level: Union[float, Tuple[float, float, float, float]] = 0.0
     white_level: float = 1.0
+    exposures: Optional[object] = None
     defects: Optional[object] = None
     calibration: Optional[object] = None
 
@@ -57,9 +63,39 @@ class RawFormat:
         """Bytes of one MIPI-packed line of `width` samples."""
         return math.ceil(width * PACKED_BITS[self.storage] / 8)
 
+    def _one_exposure(self, shape: Tuple[int, ...]) -> Tuple[int, ...]:
+        """With exposures set: check the tensor's shape against the layout and return the shape (B, 2h, X) of ONE exposure; also the
+        refusals that depend on the other fields."""
+        from .exposures import Exposures
+        ex = self.exposures
+        if not isinstance(ex, Exposures):
+            raise TypeError(f"RawFormat.exposures must be None or an Exposures, got {type(ex).__name__}")
+        e = ex.count
+        if ex.layout == "frames":
+            if len(shape) != 4 or min(shape) < 1:
+                raise ValueError(f"mosaic must be (B,E,2h,X) for Exposures(layout='frames'), got {shape}")
+            if shape[1] != e:
+                raise ValueError(f"mosaic holds {shape[1]} exposures (B,E,2h,X), Exposures.times has {e}")
+            one = (shape[0],) + shape[2:]
+        else:
+            if len(shape) == 4 and shape[1] == 1:
+                shape = (shape[0],) + shape[2:]
+            if len(shape) != 3 or min(shape) < 1:
+                raise ValueError(f"mosaic must be (B,[1,]E 2h,X) for Exposures(layout='lines'), got {shape}")
+            if shape[1] % (2 * e):
+                raise ValueError(f"line-interleaved mosaic of {e} exposures needs a multiple of {2 * e} rows (E 2h), got {shape[1]}")
+            one = (shape[0], shape[1] // e, shape[2])
+            if self.defects is not None:
+                raise ValueError("Exposures(layout='lines') takes no defects: the defects stage reads whole frames -- de-interleave the lines "
+                                 "into (B,E,2h,X) first")
+        if self.calibration is not None and getattr(self.calibration, "curve", None) is not None:
+            raise ValueError("a Calibration.curve cannot follow exposures: the merge needs linear samples -- linearise each exposure first")
+        return one
+
     def validate(self, mosaic_shape: Sequence[int]) -> Tuple[int, int]:
         """Check this format against a mosaic tensor's shape (B,[1,]2h,X); returns the mosaic size (2h, 2w).  X is 2w for the sample
-        storages and the line stride in bytes for the MIPI ones.  Raises ValueError."""
+        storages and the line stride in bytes for the MIPI ones.  With exposures set the tensor is (B,E,2h,X) or (B,[1,]E 2h,X) (its layout)
+        and the size returned is that of one exposure.  Raises ValueError."""
         if self.cfa not in CFAS:
             raise ValueError(f"RawFormat.cfa must be one of {sorted(CFAS)}, got {self.cfa!r}")
         if self.storage not in STORAGES:
@@ -71,6 +107,8 @@ class RawFormat:
         if not isinstance(self.white_level, (int, float)) or not all(float(self.white_level) > v for v in self.blacks()):
             raise ValueError(f"RawFormat.white_level ({self.white_level!r}) must exceed every black level {self.blacks()}")
         shape = tuple(int(s) for s in mosaic_shape)
+        if self.exposures is not None:
+            shape = self._one_exposure(shape)
         if len(shape) == 4 and shape[1] == 1:
             shape = (shape[0],) + shape[2:]
         if len(shape) != 3 or min(shape) < 1:
@@ -92,6 +130,8 @@ class RawFormat:
             raise ValueError(f"RAW10 packs 4 samples in 5 bytes: the mosaic width must be a multiple of 4, got {w2}")
         if self.packed and x < self.min_line_bytes(w2):
             raise ValueError(f"{self.storage} line of {w2} samples needs {self.min_line_bytes(w2)} bytes, the tensor's lines have {x}")
+        if self.exposures is not None:
+            self.exposures.check(h2, w2, shape[0])
         if self.defects is not None:
             from .defects import Defects
             if not isinstance(self.defects, Defects):

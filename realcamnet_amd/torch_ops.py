@@ -284,6 +284,41 @@ define("raw_calibrate(Tensor src, Tensor? gain_map, Tensor? frame_gains, int sto
        lambda src, gain_map, frame_gains, storage, cfa, width, black, white, curve_x, curve_y, cell, gains, clip, dtype:
        src.new_empty((src.shape[0], src.shape[1], width), dtype=dtype), _calib_launch)
 
+def _hdr_alloc(src, times, storage, cfa, width, black, exposures, lines, host_times, knee, motion):
+    return src.new_empty((src.shape[0], src.shape[1] // exposures if lines else src.shape[2], width), dtype=torch.float32)
+
+
+def _hdr_launch(out, src, times, storage, cfa, width, black, exposures, lines, host_times, knee, motion):
+    if len(black) != 4 or len(knee) != 2 or len(motion) not in (0, 2) or len(host_times) not in (0, exposures) or (times is None) == (not host_times):
+        raise ValueError(f"realcam::raw_hdr_merge: black holds four floats, knee two, motion none or two, the times E host numbers or a tensor; "
+                         f"got {black!r}, {knee!r}, {motion!r}, {host_times!r}")
+    if src.dim() != (3 if lines else 4) or (not lines and src.shape[1] != exposures) or (times is not None and times.shape[1] != exposures):
+        raise ValueError(f"realcam::raw_hdr_merge: src must be (B, E, 2h, X), or (B, E 2h, X) for interleaved lines, and times (1 or B, E); got "
+                         f"{tuple(src.shape)} for E = {exposures}")
+    if storage in (_lib.RC_RAW_MIPI10, _lib.RC_RAW_MIPI12) and src.shape[-1] % 4:
+        wide = src.new_zeros(tuple(src.shape[:-1]) + (src.shape[-1] + -src.shape[-1] % 4,))      # packed lines: every row of every exposure then starts on a dword
+        wide[..., :src.shape[-1]] = src
+        src = wide
+    b, h2 = src.shape[0], out.shape[1]
+    xb = src.shape[-1] * src.element_size()
+    src, f = _raw_source(src, storage, cfa, width, black, 0.0)
+    f.line_bytes = exposures * xb if lines else xb
+    d = _lib.HdrDesc(exposures=exposures, flags=_lib.RC_HDR_MOTION if motion else 0, knee_lo=float(knee[0]), knee_hi=float(knee[1]),
+                     exposure_stride_bytes=xb if lines else h2 * xb, frame_stride_bytes=exposures * h2 * xb)
+    for k, t in enumerate(host_times):
+        d.times[k] = float(t)
+    if motion:
+        d.motion_abs, d.motion_rel = float(motion[0]), float(motion[1])
+    check(lib().rc_raw_hdr_merge(src.data_ptr(), C.byref(f), C.byref(d), _p(times), 0 if times is None else times.shape[0], out.data_ptr(), 0,
+                                 b, h2 // 2, width // 2, _stream()), "rc_raw_hdr_merge")
+
+
+# src (B, E, 2h, X) whole frames, or (B, E 2h, X) line-interleaved (row r of exposure e at row r E + e) when `lines`; X as raw_ingest_fmt takes it;
+# times (1 or B, E) fp32 on the device or None (then host_times holds the E times); knee: (lo, hi); motion: (t_abs, t_rel) or empty -> the
+# merged mosaic (B, 2h, 2w) fp32
+define("raw_hdr_merge(Tensor src, Tensor? times, int storage, int cfa, int width, float[] black, int exposures, bool lines, float[] host_times, "
+       "float[] knee, float[] motion) -> Tensor", _hdr_alloc, _hdr_launch)
+
 define("nchw_to_nhwc(Tensor x, ScalarType dtype, int hp, int wp) -> Tensor",
        lambda x, dtype, hp, wp: x.new_empty((x.shape[0], hp, wp, x.shape[1]), dtype=dtype),
        lambda out, x, dtype, hp, wp: check(lib().rc_nchw_to_nhwc(x.data_ptr(), _dt(x), out.data_ptr(), _DT[dtype], x.shape[0], x.shape[1],
