@@ -459,6 +459,56 @@ size_t rc_hdr_desc_size(void);
 int rc_raw_hdr_merge(const void* d_src, const rc_raw_format* fmt, const rc_hdr_desc* desc, const float* d_times, int times_batch,
                      void* d_dst, int dst_pitch_bytes, int batch, int h, int w, void* stream);
 
+/* ---- temporal noise reduction (ABI 15, additive): a motion-adaptive recursive filter on the mosaic, between the repair / merge and the
+ * calibration, where the samples are linear sensor codes and the noise depends on the level alone.
+ * Replaces: fp32 copies of the frame and the state (the packed lines unpacked first), padded shifts for the nine taps, and a dozen
+ * elementwise passes -- difference, activity, noise level, ratio, weight, blend.  Here one launch over the bytes as delivered. */
+#define RC_TNR_RESET 1            /* rc_temporal_desc.flags: no state yet (or a scene cut): the result is the decoded frame */
+#define RC_TNR_GAIN 2             /* rc_temporal_desc.flags: desc->gain scales the state about the black level */
+typedef struct rc_temporal_desc {
+    int flags;                     /* RC_TNR_RESET | RC_TNR_GAIN, or 0 */
+    float noise_abs, noise_rel;    /* the noise level of a sample is noise_abs + noise_rel max(p - black, 0), in the storage's own units
+                                      (codes): noise_abs finite and > 0, noise_rel finite and >= 0 */
+    float alpha;                   /* in (0, 1]: the weight of the new frame where nothing moves */
+    float ramp;                    /* finite and > 1: at an activity of ramp noise levels the new frame passes unchanged */
+    float gain;                    /* RC_TNR_GAIN: this frame's exposure over the state's, finite and > 0 */
+    int reserved[4];               /* zero */
+} rc_temporal_desc;
+size_t rc_temporal_desc_size(void);
+
+/* src: B frames of a mosaic (2h, 2w) as rc_raw_calibrate reads them (fmt: storage, cfa, line_bytes, width, black; white is not looked at).
+ * d_prev: the state, the last result (B, 2h, 2w) fp32, rows prev_pitch_bytes apart (0: dense), frames 2h rows apart; NULL with RC_TNR_RESET
+ * (then it is not read).  d_gain: NULL, or (gain_batch) fp32 on the device, gain_batch = 1 (one value for every frame) or batch, read by the
+ * kernel when it runs: an AE loop that rewrites it needs no host sync, and a captured graph sees the new value on replay; device values are
+ * not checked (a value <= 0 or not finite: any result, no fault).  d_dst (B, 2h, 2w) fp32, rows dst_pitch_bytes apart (0: dense), frames 2h
+ * rows apart; it must not overlap d_prev.  The B frames are B independent streams.
+ *
+ * c is the decoded sample as fp32 (counts are exact) and s the state's sample, at (y, x); pos = 2 (y & 1) + (x & 1); b = black[pos].  Every
+ * product, every sum and every quotient is rounded to fp32 on its own (no fused multiply-add; the division correctly rounded).
+ *   0. reset     (RC_TNR_RESET) out = c.  Nothing else is read.
+ *   1. previous  p = s; with a gain g (desc->gain, or d_gain[gain_batch == 1 ? 0 : frame]): p = b + (s - b) g.
+ *   2. diff      d = c - p, e = |d|, at every sample of the frame.
+ *   3. activity  the taps (dy, dx) in the order (-2,-2), (-2,0), (-2,2), (0,-2), (0,0), (0,2), (2,-2), (2,0), (2,2): the same-colour 3x3
+ *                neighbourhood.  A tap whose row y + dy is outside [0, 2h) takes row y; one whose column x + dx is outside [0, 2w) takes
+ *                column x; each axis on its own.  A = the first tap's e, the others added one by one in this order; a = A (float)(1.0 / 9.0).
+ *   4. noise     t = noise_abs + noise_rel max(p - b, 0)  (> 0).
+ *   5. ratio     u = a / t.
+ *   6. weight    u <= 1: k = alpha.  u >= ramp: out = c exactly, step 7 is skipped.  Otherwise k = alpha + (u - 1) slope,
+ *                slope = (float)((1.0 - (double)alpha) / ((double)ramp - 1.0)) on the host.
+ *   7. result    out = p + k d.
+ * Hence, exactly: a reset returns c; a frame equal to its state (no gain) returns c; a frame that differs from its state by more than
+ * ramp t everywhere returns c.  Non-finite samples or state are outside this contract (no fault, any value); no index is formed from a
+ * value.  One launch, capturable; the library keeps no device buffer: the caller owns the state and swaps it with the result.
+ * Null d_src / fmt / desc / d_dst, an unknown storage or cfa, line_bytes shorter than a row or no multiple of the sample size, fmt->width
+ * other than 0 or 2w, a RAW10 width not divisible by 4, a source misaligned for its sample (MIPI: 4 bytes), a black level that is not finite,
+ * a null d_prev without RC_TNR_RESET, d_dst overlapping d_prev, a prev or dst pitch shorter than a row or no multiple of 4, prev / dst /
+ * d_gain not 4-byte aligned, a frame of 2 GiB or more (rows x pitch: source, state or destination), gain_batch other than 1 or batch (0
+ * without d_gain), a gain given both ways (RC_TNR_GAIN and d_gain), noise_abs <= 0, noise_rel < 0, alpha outside (0, 1], ramp <= 1, a host
+ * gain <= 0, any of them not finite, unknown flags, non-zero reserved (fmt's too), more than 65535 frames: RC_ERR_INVALID before anything is
+ * enqueued. */
+int rc_raw_temporal(const void* d_src, const rc_raw_format* fmt, const rc_temporal_desc* desc, const float* d_prev, int prev_pitch_bytes,
+                    const float* d_gain, int gain_batch, void* d_dst, int dst_pitch_bytes, int batch, int h, int w, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

@@ -267,15 +267,47 @@ def _merge_exposures(net, mosaic, raw_format):
     ex = raw_format.exposures
     if raw_format.defects is not None:
         b, e = mosaic.shape[0], ex.count
-        one = dataclasses.replace(raw_format, exposures=None, calibration=None)
+        one = dataclasses.replace(raw_format, exposures=None, calibration=None, temporal=None)
         fixed = ops.raw_defects(mosaic.reshape((b * e,) + tuple(mosaic.shape[2:])), one)
         if raw_format.defects.counts:
             fixed, counts = fixed
             net.__dict__["defect_counts"] = counts.view(b, e, 3)
         mosaic = fixed.view(b, e, h2, w2)
         raw_format = dataclasses.replace(raw_format, storage="float" if raw_format.storage == "float" else "u16", width=None, defects=None)
-    merged = ops.raw_hdr_merge(mosaic, raw_format)
+    merged = ops.raw_hdr_merge(mosaic, dataclasses.replace(raw_format, temporal=None))
     return merged, dataclasses.replace(raw_format, storage="float", width=None, exposures=None, defects=None)
+
+
+def _temporal(mosaic, raw_format):
+    """raw_format.temporal (a Temporal): ops.raw_temporal (one launch) filters the frame -- repaired and merged by now -- against the last
+    filtered mosaic its TemporalState holds, and the result becomes the state: two buffers that swap from call to call.  An empty state, or
+    one of another shape or device, starts over (the result is the decoded frame).  Returns the filtered fp32 mosaic and the format that
+    describes it: storage "float", the same CFA and levels, the calibration kept for the next stage."""
+    import dataclasses
+    h2, w2 = raw_format.validate(mosaic.shape)
+    st = raw_format.temporal.state
+    shape = (mosaic.shape[0], h2, w2)
+    prev = st.frame if st.matches(shape, mosaic.device) else None
+    out = st._spare
+    if out is None or out is prev or tuple(out.shape) != shape or out.device != mosaic.device:
+        out = None
+    st.frame, st._spare = ops.raw_temporal(mosaic, raw_format, prev=prev, out=out), prev
+    return st.frame, dataclasses.replace(raw_format, storage="float", width=None, defects=None, exposures=None, temporal=None)
+
+
+def _temporal_check(raw_format):
+    """What forward_mosaic asks of a temporal format before any stage runs."""
+    from .temporal import Temporal, TemporalState
+    t = raw_format.temporal
+    if not isinstance(t, Temporal):
+        raise TypeError(f"RawFormat.temporal must be None or a Temporal, got {type(t).__name__}")
+    if not isinstance(t.state, TemporalState):
+        raise ValueError("forward_mosaic: RawFormat.temporal needs a state (Temporal(state=TemporalState())): the filter carries the last "
+                         "filtered frame from one call to the next")
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("forward_mosaic with RawFormat.temporal cannot be captured: it swaps its state buffers between calls and a graph "
+                           "would replay one direction of the swap forever.  Capture ops.raw_temporal(mosaic, raw_format, prev=, out=) on "
+                           "explicit buffers instead")
 
 
 def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, raw_format=None):
@@ -289,17 +321,23 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
     rounded to the network's type once, by the ingest, as without a calibration.
     raw_format.exposures (an Exposures): the tensor holds E exposures of each frame; they are repaired one by one and merged first
     (_merge_exposures), and the calibration and the ingest then read the merged fp32 mosaic with the same levels.
+    raw_format.temporal (a Temporal): the repaired / merged frame is filtered against the last call's result (_temporal) in front of the
+    calibration.  The order is merge (with its per-exposure repair), repair, temporal, calibration, ingest.
     A cond the caller supplies is used as it is: it is NOT corrected and NOT calibrated."""
     need_cond = hasattr(net, "classifier") and cond is None and not getattr(net, "cond_from_raw", False)
+    if raw_format is not None and raw_format.temporal is not None:
+        _temporal_check(raw_format)
     if raw_format is not None and raw_format.exposures is not None:
         mosaic, raw_format = _merge_exposures(net, mosaic, raw_format)
     if raw_format is not None and raw_format.defects is not None:
         import dataclasses
-        fixed = ops.raw_defects(mosaic, raw_format)
+        fixed = ops.raw_defects(mosaic, dataclasses.replace(raw_format, temporal=None))
         if raw_format.defects.counts:
             fixed, net.__dict__["defect_counts"] = fixed
         mosaic = fixed
         raw_format = dataclasses.replace(raw_format, storage="float" if raw_format.storage == "float" else "u16", width=None, defects=None)
+    if raw_format is not None and raw_format.temporal is not None:
+        mosaic, raw_format = _temporal(mosaic, raw_format)
     if raw_format is not None and raw_format.calibration is not None:
         import dataclasses
         mosaic = ops.raw_calibrate(mosaic, raw_format, dtype=torch.float32)

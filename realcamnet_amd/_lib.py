@@ -34,6 +34,7 @@ RC_STATS_MAX_GRID, RC_STATS_SLOTS = 64, 8
 RC_DEFECT_HOT, RC_DEFECT_COLD = 1, 2
 RC_CALIB_GAINS, RC_CALIB_CLIP, RC_CALIB_MAX_KNOTS = 1, 2, 16
 RC_HDR_MOTION = 1
+RC_TNR_RESET, RC_TNR_GAIN = 1, 2
 
 
 class ConvDesc(C.Structure):
@@ -120,6 +121,14 @@ class HdrDesc(C.Structure):
     ]
 
 
+class TemporalDesc(C.Structure):
+    """Mirror of `struct rc_temporal_desc`."""
+    _fields_ = [
+        ("flags", C.c_int32), ("noise_abs", C.c_float), ("noise_rel", C.c_float), ("alpha", C.c_float), ("ramp", C.c_float), ("gain", C.c_float),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 def declared_symbols() -> list[str]:
     """Every function the public header declares (used by the CPU-side ABI test)."""
     text = HEADER.read_text()
@@ -153,6 +162,8 @@ _SIGS = {
     "rc_raw_calibrate": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(CalibDesc), _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     "rc_hdr_desc_size": (_SZ, []),
     "rc_raw_hdr_merge": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(HdrDesc), _P, _I, _P, _I, _I, _I, _I, _P]),
+    "rc_temporal_desc_size": (_SZ, []),
+    "rc_raw_temporal": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(TemporalDesc), _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

@@ -500,6 +500,15 @@ def _one_exposure(raw_format, op):
     if getattr(raw_format, "exposures", None) is not None:
         raise ValueError(f"{op} reads one exposure: merge first.  The order is ops.raw_defects (per exposure), ops.raw_hdr_merge, "
                          "ops.raw_calibrate, ops.raw_ingest (forward_mosaic runs all four)")
+    _no_temporal(raw_format, op)
+
+
+def _no_temporal(raw_format, op):
+    """The other front-end ops refuse a format whose temporal filter is set, rather than skip the stage silently."""
+    if getattr(raw_format, "temporal", None) is not None:
+        raise ValueError(f"{op} does not filter: raw_format.temporal is set.  The order is ops.raw_defects, ops.raw_hdr_merge, "
+                         "ops.raw_temporal, ops.raw_calibrate, ops.raw_ingest, each on a format without the stages already run "
+                         "(forward_mosaic runs all five)")
 
 
 def _raw_ingest_fmt(mosaic, dtype, pad_to, black_level, white_level, cond_hw, fmt):
@@ -611,6 +620,7 @@ def raw_hdr_merge(mosaic: torch.Tensor, raw_format, exposures=None) -> torch.Ten
     if raw_format.defects is not None:
         raise ValueError("raw_hdr_merge does not correct defects: run ops.raw_defects on each exposure first and merge its result "
                          "(forward_mosaic does both)")
+    _no_temporal(raw_format, "raw_hdr_merge")
     if raw_format.exposures is not exposures:
         raw_format = dataclasses.replace(raw_format, exposures=exposures)
     mosaic, storage, (_, w2) = _raw_source(mosaic, raw_format, "raw_hdr_merge: ")
@@ -626,6 +636,65 @@ def raw_hdr_merge(mosaic: torch.Tensor, raw_format, exposures=None) -> torch.Ten
         host_times = list(exposures.times)
     return _R.raw_hdr_merge(mosaic, times, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), exposures.count,
                             exposures.layout == "lines", host_times, list(exposures.knee), [] if exposures.motion is None else list(exposures.motion))
+
+
+def raw_temporal(mosaic: torch.Tensor, raw_format, prev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Temporal noise reduction on the mosaic itself, between the repair / merge and the calibration (rc_raw_temporal; the arithmetic is fixed
+    in include/realcam_hip.h): a sensor frame as `raw_format` (a RawFormat with `temporal` set) describes it, and `prev`, the last filtered
+    mosaic (B,2h,2w) fp32 (None: a reset, the result is the decoded frame) -> the filtered mosaic (B,2h,2w) fp32 in the frame's code units,
+    unpacked.  `out` is an optional fp32 destination (B,2h,2w); it must not alias `prev`.  Rows of `prev` and `out` may be padded (a stride
+    that is a multiple of one sample), frames must be whole rows apart.  One launch; with explicit `prev` and `out` nothing is allocated and
+    the call is capturable; a gain tensor is read in place by the kernel; nothing is synchronised.  The Temporal's state is not looked at:
+    the caller chains prev / out.  raw_format.defects and raw_format.exposures must be None (run those stages first); a Calibration.curve is
+    refused (the noise model needs linear samples).  Non-finite samples or state are outside the contract."""
+    from .raw_format import CFAS, RawFormat
+    from .temporal import Temporal
+    if not isinstance(raw_format, RawFormat):
+        raise TypeError(f"raw_temporal: raw_format must be a RawFormat, got {type(raw_format).__name__}")
+    t = raw_format.temporal
+    if not isinstance(t, Temporal):
+        raise TypeError(f"raw_temporal: raw_format.temporal must be a Temporal, got {type(t).__name__}")
+    if raw_format.exposures is not None:
+        raise ValueError("raw_temporal reads one exposure: merge first.  The order is ops.raw_defects (per exposure), ops.raw_hdr_merge, "
+                         "ops.raw_temporal, ops.raw_calibrate, ops.raw_ingest (forward_mosaic runs all five)")
+    if raw_format.defects is not None:
+        raise ValueError("raw_temporal does not correct defects: run ops.raw_defects first and filter its result (forward_mosaic does both)")
+    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format, "raw_temporal: ")
+    shape = (mosaic.shape[0], h2, w2)
+
+    def state(x, name):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError(f"raw_temporal: {name} must be a tensor, got {type(x).__name__}")
+        if x.dtype != torch.float32 or tuple(x.shape) != shape or x.device != mosaic.device:
+            raise ValueError(f"raw_temporal: {name} must be a {shape} fp32 tensor on {mosaic.device}, got {tuple(x.shape)} {x.dtype} on {x.device}")
+        if x.stride(2) != 1 or x.stride(1) < w2 or (shape[0] > 1 and x.stride(0) != h2 * x.stride(1)):
+            raise ValueError(f"raw_temporal: {name} must have dense samples, rows at least one row apart and frames 2h rows apart, got strides {x.stride()}")
+        return x
+
+    if prev is not None:
+        prev = state(prev, "prev")
+    if out is None:
+        out = mosaic.new_empty(shape, dtype=torch.float32)
+    else:
+        out = state(out, "out")
+        if prev is not None and not isinstance(out, FakeTensor):
+            o0, p0 = out.data_ptr(), prev.data_ptr()
+            o1 = o0 + 4 * ((shape[0] * h2 - 1) * out.stride(1) + w2)
+            p1 = p0 + 4 * ((shape[0] * h2 - 1) * prev.stride(1) + w2)
+            if o0 < p1 and p0 < o1:
+                raise ValueError("raw_temporal: out must not alias prev (a row's neighbours are read after it is written): swap two buffers")
+    gain, host_gain = None, []
+    if t.device_gain:
+        gain = t.gain
+        if not gain.is_cuda or gain.device != mosaic.device:
+            raise RuntimeError(f"raw_temporal: the gain tensor is on {gain.device}, the mosaic on {mosaic.device}; give a host number or a "
+                               "tensor on the mosaic's device")
+        if not gain.is_contiguous():
+            raise ValueError("raw_temporal: the gain tensor must be contiguous (it is read in place, not copied)")
+    elif t.gain is not None:
+        host_gain = [t.gain]
+    _R.raw_temporal(mosaic, prev, gain, out, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), list(t.params()), host_gain)
+    return out
 
 
 def rgb_encode(y: torch.Tensor, bits: int, crop_hw: Optional[Tuple[int, int]] = None) -> torch.Tensor:

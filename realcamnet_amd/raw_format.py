@@ -35,6 +35,11 @@ class RawFormat:
                  samples), and layout "lines" takes no defects (de-interleave first).
     defects      None, or a Defects: forward_mosaic repairs the mosaic (ops.raw_defects: a static map and / or hot / cold thresholds, in
                  this storage's own units) before it ingests it.  A map must have the mosaic's size.
+    temporal     None, or a Temporal: forward_mosaic runs the motion-adaptive recursive temporal filter (ops.raw_temporal, one launch) on
+                 the linear sensor codes -- after the repair / the merge and in front of the calibration -- against the last filtered
+                 frame, which its TemporalState carries from call to call (the B frames of a call are B streams).  The noise model is in
+                 this storage's own code units and uses these black levels; a calibration must not carry a curve (the noise model needs
+                 linear samples).
     calibration  None, or a Calibration: forward_mosaic then runs ops.raw_calibrate (a linearisation curve, these levels, a flat-field gain
                  map, white-balance gains, a clip) after the defects stage and ingests its fp32 result.  With a curve, black_level and
                  white_level are in the curve's linear units.  A gain map must have the node count the mosaic needs.
@@ -45,6 +50,7 @@ class RawFormat:
     width: Optional[int] = None
     black_level: Union[float, Tuple[float, float, float, float]] = 0.0
     white_level: float = 1.0
+    temporal: Optional[object] = None
     exposures: Optional[object] = None
     defects: Optional[object] = None
     calibration: Optional[object] = None
@@ -137,6 +143,13 @@ class RawFormat:
             if not isinstance(self.defects, Defects):
                 raise TypeError(f"RawFormat.defects must be None or a Defects, got {type(self.defects).__name__}")
             self.defects.check(h2, w2)
+        if self.temporal is not None:
+            from .temporal import Temporal
+            if not isinstance(self.temporal, Temporal):
+                raise TypeError(f"RawFormat.temporal must be None or a Temporal, got {type(self.temporal).__name__}")
+            if self.calibration is not None and getattr(self.calibration, "curve", None) is not None:
+                raise ValueError("a Calibration.curve cannot follow temporal: the noise model needs linear samples -- linearise the frame first")
+            self.temporal.check(h2, w2, shape[0])
         if self.calibration is not None:
             from .calibration import Calibration
             if not isinstance(self.calibration, Calibration):

@@ -319,6 +319,29 @@ def _hdr_launch(out, src, times, storage, cfa, width, black, exposures, lines, h
 define("raw_hdr_merge(Tensor src, Tensor? times, int storage, int cfa, int width, float[] black, int exposures, bool lines, float[] host_times, "
        "float[] knee, float[] motion) -> Tensor", _hdr_alloc, _hdr_launch)
 
+def _temporal_launch(ret, src, prev, gain, out, storage, cfa, width, black, params, host_gain):
+    if len(black) != 4 or len(params) != 4 or len(host_gain) not in (0, 1) or (gain is not None and host_gain):
+        raise ValueError(f"realcam::raw_temporal: black holds four floats, params n_abs, n_rel, alpha, ramp, the gain one host number or a tensor; "
+                         f"got {black!r}, {params!r}, {host_gain!r}")
+    b, h2, _ = src.shape
+    if out.dtype != torch.float32 or tuple(out.shape) != (b, h2, width) or (prev is not None and (prev.dtype != torch.float32 or prev.shape != out.shape)):
+        raise ValueError(f"realcam::raw_temporal: prev and out must be ({b}, {h2}, {width}) fp32, got {None if prev is None else tuple(prev.shape)} and {tuple(out.shape)}")
+    src, f = _raw_source(src, storage, cfa, width, black, 0.0)
+    d = _lib.TemporalDesc(flags=(_lib.RC_TNR_RESET if prev is None else 0) | (_lib.RC_TNR_GAIN if host_gain and prev is not None else 0),
+                          noise_abs=float(params[0]), noise_rel=float(params[1]), alpha=float(params[2]), ramp=float(params[3]),
+                          gain=float(host_gain[0]) if host_gain and prev is not None else 0.0)
+    use_gain = gain is not None and prev is not None           # a reset reads nothing but the frame
+    check(lib().rc_raw_temporal(src.data_ptr(), C.byref(f), C.byref(d), _p(prev), 0 if prev is None else 4 * prev.stride(1),
+                                gain.data_ptr() if use_gain else None, gain.shape[0] if use_gain else 0, out.data_ptr(), 4 * out.stride(1),
+                                b, h2 // 2, width // 2, _stream()), "rc_raw_temporal")
+
+
+# src (B, 2h, X) as raw_ingest_fmt takes it; prev (B, 2h, 2w) fp32, the last result, or None (a reset: out = the decoded frame); gain (1 or B, 1)
+# fp32 on the device or None (then host_gain holds one number or nothing); params: n_abs, n_rel, alpha, ramp; out (B, 2h, 2w) fp32 is written
+# (rows of prev and out may be padded: their stride(1) is the pitch) -> nothing (an empty tensor)
+define("raw_temporal(Tensor src, Tensor? prev, Tensor? gain, Tensor(a!) out, int storage, int cfa, int width, float[] black, float[] params, "
+       "float[] host_gain) -> Tensor", lambda src, prev, gain, out, storage, cfa, width, black, params, host_gain: out.new_empty((0,)), _temporal_launch)
+
 define("nchw_to_nhwc(Tensor x, ScalarType dtype, int hp, int wp) -> Tensor",
        lambda x, dtype, hp, wp: x.new_empty((x.shape[0], hp, wp, x.shape[1]), dtype=dtype),
        lambda out, x, dtype, hp, wp: check(lib().rc_nchw_to_nhwc(x.data_ptr(), _dt(x), out.data_ptr(), _DT[dtype], x.shape[0], x.shape[1],
