@@ -231,6 +231,40 @@ int rc_resize(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, int 
  * read outside the table.  One launch.  n outside 2 .. 65, a bad dtype, h > H or w > W: RC_ERR_INVALID before any launch. */
 int rc_lut3d(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, const float* d_lut, int n, int batch, int H, int W, int h, int w, void* stream);
 
+/* ---- output sharpening (ABI 15, additive): the same planar result with its luma detail amplified, between the look and the encoders --------
+ * Replaces: F.conv2d on a luma plane, F.max_pool2d twice for the local range and half a dozen elementwise passes after the network.
+ * An unsharp mask on the luma: a 3x3 (radius 1) or 5x5 (radius 2) binomial blur, the difference cored (detail below `core` is left
+ * alone, so noise is not sharpened), scaled by `amount`, limited so that the sharpened luma leaves the range of its 3x3 neighbourhood by
+ * at most `overshoot`, and added to R, G and B alike.  matrix: RC_MATRIX_* (the luma coefficients of RC_YUV_KR_KB). */
+typedef struct rc_sharpen_desc {
+    int radius;                 /* 1 or 2 */
+    int matrix;                 /* RC_MATRIX_BT601 / BT709 / BT2020 */
+    float amount;               /* [0, 8] */
+    float core;                 /* [0, 1], in output units */
+    float overshoot;            /* [0, 1], in output units */
+} rc_sharpen_desc;
+size_t rc_sharpen_desc_size(void);
+
+/* src (B,3,H,W) RC_F32 / RC_BF16 / RC_F16 planar R,G,B, cropped to (h,w); dst (B,3,h,w) planar, RC_F32 or src_dtype; dst must not overlap src.
+ * The taps of pixel (y, x) of the crop are taken at clamp(y + dy, 0, h-1) and clamp(x + dx, 0, w-1), each axis on its own: nothing outside
+ * the crop is ever read (the source's rows and columns beyond (h, w) may hold anything).  X[dy][dx] below is X at such a tap.
+ * fp32, every product, sum and difference rounded on its own (no fused multiply-add):
+ *   1. r,g,b = float(src), NaN -> 0, clamped to [0,1]                                          (step 1 of rc_yuv_encode)
+ *   2. L = ((Kr r) + (Kg g)) + (Kb b)         RC_YUV_KR_KB, Kg = 1 - Kr - Kb in double, each rounded to fp32 once   (rc_yuv_encode's Y)
+ *   3. a separable binomial, along the row on L and then down the column on the row sums, in this order of additions:
+ *        radius 1:  S = (L[-1] + L[+1]) + (2 L[0]);                                       T = (S[-1] + S[+1]) + (2 S[0]);    blur = T 2^-4
+ *        radius 2:  S = (((L[-2] + L[+2]) + (2 L[0])) + (4 L[0])) + (4 (L[-1] + L[+1]));   T the same way on the rows of S;  blur = T 2^-8
+ *      (on a constant neighbourhood every partial sum is a power of two times the value: blur == L exactly)
+ *   4. d = L - blur;  a = |d|;  c = max(a - core, 0);  d1 = copysign(c, d);  e = amount d1
+ *   5. lo, hi = the minimum and maximum of L over the 3x3 taps;
+ *      t = L + e;  t = min(t, hi + overshoot);  t = max(t, lo - overshoot);  e2 = t - L
+ *   6. per channel c of step 1:  o = min(max(c + e2, 0), 1), stored as fp32, or rounded to nearest even once into src_dtype
+ * So a frame whose three planes are each constant, amount = 0 and core = 1 all return step 1's values, and every output is finite and lies
+ * in [0,1] whatever the source holds.  One launch, no device state.  Null pointers, a bad dtype, radius or matrix, a non-finite or
+ * out-of-range amount / core / overshoot, an empty frame, h > H or w > W, three planes of 2 GiB or more (the offsets inside a frame are
+ * 32-bit), dst overlapping src: RC_ERR_INVALID before any launch. */
+int rc_sharpen(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, const rc_sharpen_desc* desc, int batch, int H, int W, int h, int w, void* stream);
+
 /* ---- geometric correction (ABI 15, additive): the same planar result resampled through a coarse mesh, in front of the scaler --------------
  * Replaces: F.grid_sample(result.float(), dense (B, oh, ow, 2) grid, align_corners=True) after the network -- lens distortion correction,
  * a 90 degree orientation, a flip, per-frame stabilisation -- and with it the dense grid in HBM and the fp32 copy of the frame.

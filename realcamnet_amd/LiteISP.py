@@ -404,8 +404,8 @@ def _plan_outputs(outputs, out_format, hw):
 
 def _emit(y, bits, outs):
     """The single result of the out_format route, or the list of renditions of `outs` in the order given: each an optional ops.warp (fp32)
-    of the one float result, then an optional ops.resize (fp32), then an optional colour look (ops.lut3d, fp32), then the encoders of
-    _encode."""
+    of the one float result, then an optional ops.resize (fp32), then an optional colour look (ops.lut3d, fp32), then an optional
+    sharpening (ops.sharpen, fp32), then the encoders of _encode."""
     if outs is None:
         return _encode(y, bits)
     res = []
@@ -414,6 +414,8 @@ def _emit(y, bits, outs):
         t = t if o.resize is None else ops.resize(t, o.resize)
         if o.look is not None:
             t = ops.lut3d(t, o.look)
+        if o.sharpen is not None:
+            t = ops.sharpen(t, o.sharpen)
         res.append(_encode(t, _out_bits(o.format)))
     return res
 

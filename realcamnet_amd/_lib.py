@@ -121,6 +121,11 @@ class HdrDesc(C.Structure):
     ]
 
 
+class SharpenDesc(C.Structure):
+    """Mirror of `struct rc_sharpen_desc`."""
+    _fields_ = [("radius", C.c_int32), ("matrix", C.c_int32), ("amount", C.c_float), ("core", C.c_float), ("overshoot", C.c_float)]
+
+
 class TemporalDesc(C.Structure):
     """Mirror of `struct rc_temporal_desc`."""
     _fields_ = [
@@ -153,6 +158,8 @@ _SIGS = {
     "rc_resize_taps": (C.c_int, [_I, _I, _I, _I, _P, _P, C.POINTER(C.c_int)]),
     "rc_resize": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "rc_lut3d": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "rc_sharpen_desc_size": (_SZ, []),
+    "rc_sharpen": (C.c_int, [_P, _I, _P, _I, C.POINTER(SharpenDesc), _I, _I, _I, _I, _I, _P]),
     "rc_warp": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_stats_desc_size": (_SZ, []),
     "rc_frame_stats": (C.c_int, [_P, _I, C.POINTER(StatsDesc), _P, _P, _I, _I, _I, _I, _I, _P]),

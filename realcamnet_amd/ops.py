@@ -811,6 +811,25 @@ def lut3d(y: torch.Tensor, lut, crop_hw: Optional[Tuple[int, int]] = None, out_d
     return _R.lut3d(y, table, lut.size, h, w, out_dtype)
 
 
+def sharpen(y: torch.Tensor, sharpen, crop_hw: Optional[Tuple[int, int]] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Planar result (B,3,H,W), cropped to crop_hw, -> (B,3,h,w) with its luma detail amplified as the Sharpen `sharpen` asks: an unsharp
+    mask on the luma, cored and limited to the local range (rc_sharpen; the arithmetic is fixed in include/realcam_hip.h).  out_dtype:
+    torch.float32, or y's dtype (rounded to nearest even once).  One launch, no device state."""
+    from .sharpen import Sharpen
+    if not isinstance(sharpen, Sharpen):
+        raise TypeError(f"sharpen: sharpen must be a Sharpen, got {type(sharpen).__name__}")
+    y = _req(y, "sharpen input")
+    if y.dim() != 4 or y.shape[1] != 3:
+        raise ValueError(f"sharpen: expected (B,3,H,W), got {tuple(y.shape)}")
+    _dt(y)
+    if out_dtype not in (torch.float32, y.dtype):
+        raise ValueError(f"sharpen: out_dtype must be torch.float32 or the source's {y.dtype}, got {out_dtype}")
+    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
+    if y.shape[0] < 1 or h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]:
+        raise ValueError(f"sharpen: crop {(h, w)} of the source {tuple(y.shape)} is empty or exceeds it")
+    return _R.sharpen(y, sharpen.radius, sharpen.matrix_code, sharpen.amount, sharpen.core, sharpen.overshoot, h, w, out_dtype)
+
+
 _WARP_MESHES = {}        # (Warp, device) -> the device mesh of rc_warp
 
 

@@ -12,6 +12,7 @@ from typing import Optional, Tuple
 from . import _lib
 from .look import Lut3D
 from .out_format import OutFormat
+from .sharpen import Sharpen
 from .stats import Stats
 from .warp import Warp
 
@@ -96,20 +97,23 @@ class Resize:
 
 @dataclass(frozen=True)
 class Output:
-    """One entry of forward_mosaic(outputs=[...]): an optional Warp of the float result, an optional Resize, an optional colour look, then
-    its format.
+    """One entry of forward_mosaic(outputs=[...]): an optional Warp of the float result, an optional Resize, an optional colour look, an
+    optional Sharpen, then its format.
 
     format  None (the planar float tensor), "rgb8" / "rgb16" (interleaved uint8 / uint16), an OutFormat (a YuvFrames) or a Stats (a
             FrameStats: the statistics of the frame after this output's own warp / resize / look, in place of a picture).
     resize  None (the result's own size) or a Resize.
     look    None or a Lut3D, applied after the resize and before the encoder (ops.lut3d; with format None the looked tensor is fp32).
     warp    None or a Warp, applied first (ops.warp, fp32): the resize's window and the format then see a frame of warp.size.
+    sharpen None or a Sharpen, applied last among the float stages (ops.sharpen, fp32): its thresholds are meant in the values the encoder
+            and the viewer see, and nothing resamples or remaps the picture after it.
     """
 
     format: object = None
     resize: Optional[Resize] = None
     look: Optional[Lut3D] = None
     warp: Optional[Warp] = None
+    sharpen: Optional[Sharpen] = None
 
     def __post_init__(self):
         f = self.format
@@ -123,6 +127,8 @@ class Output:
             raise TypeError(f"Output.look must be None or a Lut3D, got {type(self.look).__name__}")
         if self.warp is not None and not isinstance(self.warp, Warp):
             raise TypeError(f"Output.warp must be None or a Warp, got {type(self.warp).__name__}")
+        if self.sharpen is not None and not isinstance(self.sharpen, Sharpen):
+            raise TypeError(f"Output.sharpen must be None or a Sharpen, got {type(self.sharpen).__name__}")
         if isinstance(f, OutFormat) and self.resize is not None and (self.resize.size[0] % 2 or self.resize.size[1] % 2):
             raise ValueError(f"Output: 4:2:0 ({f.layout}) needs an even height and width, Resize.size is {self.resize.size}")
         if isinstance(f, OutFormat) and self.resize is None and self.warp is not None and (self.warp.size[0] % 2 or self.warp.size[1] % 2):

@@ -196,6 +196,17 @@ def _lut3d_launch(out, y, table, n, h, w, dtype):
 define("lut3d(Tensor y, Tensor table, int n, int h, int w, ScalarType dtype) -> Tensor",
        lambda y, table, n, h, w, dtype: y.new_empty((y.shape[0], 3, h, w), dtype=dtype), _lut3d_launch)
 
+
+def _sharpen_launch(out, y, radius, matrix, amount, core, overshoot, h, w, dtype):
+    d = _lib.SharpenDesc(radius=radius, matrix=matrix, amount=amount, core=core, overshoot=overshoot)
+    check(lib().rc_sharpen(y.data_ptr(), _dt(y), out.data_ptr(), _DT[dtype], C.byref(d), y.shape[0], y.shape[2], y.shape[3], h, w, _stream()),
+          "rc_sharpen")
+
+
+# y (B,3,H,W) planar, cropped to (h,w), -> (B,3,h,w) of `dtype` (fp32 or y's); the fields of rc_sharpen_desc
+define("sharpen(Tensor y, int radius, int matrix, float amount, float core, float overshoot, int h, int w, ScalarType dtype) -> Tensor",
+       lambda y, radius, matrix, amount, core, overshoot, h, w, dtype: y.new_empty((y.shape[0], 3, h, w), dtype=dtype), _sharpen_launch)
+
 def _warp_launch(out, y, mesh, cell, interp, border, fill, h, w, oh, ow, dtype):
     gh, gw = -(-oh // cell) + 1, -(-ow // cell) + 1
     if (mesh.dtype != torch.float32 or mesh.device != y.device or not mesh.is_contiguous() or mesh.dim() != 4 or tuple(mesh.shape[1:]) != (gh, gw, 2)
