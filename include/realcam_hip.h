@@ -265,6 +265,72 @@ size_t rc_sharpen_desc_size(void);
  * 32-bit), dst overlapping src: RC_ERR_INVALID before any launch. */
 int rc_sharpen(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, const rc_sharpen_desc* desc, int batch, int H, int W, int h, int w, void* stream);
 
+/* ---- local tone mapping (ABI 15, additive): the same planar result with a scene-adaptive gain, between the scaler and the look -------------
+ * Replaces: an fp32 copy of the frame, torch.bincount per tile, cumulative sums, eight gathers per pixel and the interpolation passes.
+ * Contrast-limited adaptive histogram equalisation (CLAHE) on the 8-bit luma code, applied as ONE gain to R, G and B, so the hue is
+ * kept.  A grid of gy x gx tiles; each tile owns a table of 256 gains, and a pixel interpolates bilinearly between the tables of the
+ * four nearest tile centres.  Three launches, none keeps device state: rc_tone_hist (the tiles' histograms), rc_tone_gains (histograms
+ * -> gain tables; a video caller may smooth the tables over time before the next step) and rc_tone_apply.
+ *
+ * Tiles follow rc_frame_stats' zones: tile column i is the columns a_i .. a_{i+1} - 1 with a_i = ceil(i w / gx), rows the same way with h
+ * and gy.  The grid is 1 .. RC_TONE_MAX_GRID per axis and at most the side, so no tile is empty.
+ * fp32 throughout, every product, sum, difference and quotient rounded on its own (no fused multiply-add; divisions correctly rounded):
+ *  hist    1. r,g,b = float(src), NaN -> 0, clamped to [0,1]                                          (step 1 of rc_yuv_encode)
+ *          2. Y = ((Kr r) + (Kg g)) + (Kb b)     RC_YUV_KR_KB, Kg = 1 - Kr - Kb in double, each rounded to fp32 once  (rc_sharpen's L)
+ *          3. q = clamp(rint(Y 255), 0, 255), round half to even
+ *          4. hist[tile][q] += 1            (integers: independent of the order of the adds, the same from run to run)
+ *  gains   per tile, in 64-bit integers; n = max(sum of h[k], 1): the tile's pixels; clip_q8 = rint(clip 256) in 256 .. 65536
+ *          1. limit = max(1, (n clip_q8) >> 16)
+ *          2. c[k] = min(h[k], limit)
+ *          3. E = n - sum c
+ *          4. c[k] += (E >> 8) + ((((k + 1) (E & 255)) >> 8) - ((k (E & 255)) >> 8))       (the excess spread evenly, sum c = n again; one pass)
+ *          5. C[k] = sum of c[j] over j <= k
+ *          6. T_k = float(C[k]) / float(n), the conversions rounded to nearest even
+ *          7. for k >= 1:  y_k = float(k) / 255;  m_k = y_k + strength (T_k - y_k);  G[k] = min(m_k / y_k, max_gain)
+ *          8. G[0] = G[1]
+ *  axis    rc_tone_axis, per column x (per row y the same way):  s_i = a_i + a_{i+1} (twice the centre of tile i), q = 2 x + 1;
+ *          q <= s_0: idx = 0, wt = 0;  q >= s_{g-1}: idx = g - 1, wt = 0;  otherwise idx = the largest i with s_i <= q and
+ *          wt = (float)((double)(q - s_i) / (double)(s_{i+1} - s_i))
+ *  apply   steps 1 and 2 of hist, then  p = Y 255;  i = min(int(floor(p)), 254);  f = min(p - float(i), 1)
+ *          jy = iy[y], v = uy[y], jx = ix[x], u = ux[x];  jy' = min(jy + 1, gy - 1), jx' = min(jx + 1, gx - 1)
+ *          for each of the four tiles t = (jy | jy', jx | jx'):  g_t = G_t[i] + f (G_t[i + 1] - G_t[i])
+ *          top = g00 + u (g01 - g00);  bot = g10 + u (g11 - g10);  g = top + v (bot - top)
+ *          per channel c of step 1:  o = min(c g, 1), stored as fp32, or rounded to nearest even once into src_dtype
+ * The form a + t (b - a) interpolates equal nodes exactly.  So strength = 0 (every gain 1) returns step 1's values, and a frame that
+ * repeats one tile maps as that tile alone.  No index is formed from a gain; the gains on the device are not checked, and non-finite
+ * gains are outside the contract.  The kernel clamps the indices it reads from iy / ix to the grid, so no table can make it read outside
+ * the gains. */
+#define RC_TONE_MAX_GRID 16       /* tiles per axis */
+#define RC_TONE_BINS 256
+typedef struct rc_tone_desc {
+    int grid[2];                /* gy, gx: 1 .. RC_TONE_MAX_GRID and at most the frame's side */
+    int matrix;                 /* RC_MATRIX_BT601 / BT709 / BT2020 */
+    int clip_q8;                /* 256 .. 65536: the clip limit in 1/256 of a bin's mean count; 65536 = plain equalisation */
+    float strength;             /* [0, 1] */
+    float max_gain;             /* [1, 64] */
+    int reserved[4];            /* zero */
+} rc_tone_desc;
+size_t rc_tone_desc_size(void);
+
+/* Host function, no GPU: idx[n] and wt[n] of an axis of n positions and g tiles (the `axis` rules above).  n < 1, g outside
+ * 1 .. min(RC_TONE_MAX_GRID, n), a null pointer: RC_ERR_INVALID. */
+int rc_tone_axis(int n, int g, int* idx, float* wt);
+
+/* src (B,3,H,W) RC_F32 / RC_BF16 / RC_F16 planar R,G,B, cropped to (h,w) -> d_hist (B,gy,gx,256) int32, zeroed on `stream` by the call
+ * itself.  Null pointers, a bad dtype, matrix or grid, clip_q8 / strength / max_gain out of range or not finite, non-zero reserved, an
+ * empty frame, h > H or w > W, a source plane of 2^29 samples or more (offsets inside a frame are 32-bit), more than 65535 frames, a
+ * misaligned pointer: RC_ERR_INVALID before anything is enqueued.  The same holds for the two entries below. */
+int rc_tone_hist(const void* d_src, int src_dtype, const rc_tone_desc* desc, int* d_hist, int batch, int H, int W, int h, int w, void* stream);
+
+/* d_hist (tiles,256) int32 -> d_gains (tiles,256) fp32, tiles = batch gy gx.  One block per tile. */
+int rc_tone_gains(const int* d_hist, const rc_tone_desc* desc, float* d_gains, int batch, void* stream);
+
+/* src as rc_tone_hist takes it; d_gains (gains_batch,gy,gx,256) fp32, 16-byte aligned, gains_batch 1 (one set for every frame) or batch;
+ * d_iy / d_uy (h) and d_ix / d_ux (w): the device copies of rc_tone_axis(h, gy) and rc_tone_axis(w, gx), 4-byte aligned; dst (B,3,h,w)
+ * planar, RC_F32 or src_dtype, must not overlap src. */
+int rc_tone_apply(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, const rc_tone_desc* desc, const float* d_gains, int gains_batch,
+                  const int* d_iy, const float* d_uy, const int* d_ix, const float* d_ux, int batch, int H, int W, int h, int w, void* stream);
+
 /* ---- geometric correction (ABI 15, additive): the same planar result resampled through a coarse mesh, in front of the scaler --------------
  * Replaces: F.grid_sample(result.float(), dense (B, oh, ow, 2) grid, align_corners=True) after the network -- lens distortion correction,
  * a 90 degree orientation, a flip, per-frame stabilisation -- and with it the dense grid in HBM and the fp32 copy of the frame.

@@ -404,14 +404,16 @@ def _plan_outputs(outputs, out_format, hw):
 
 def _emit(y, bits, outs):
     """The single result of the out_format route, or the list of renditions of `outs` in the order given: each an optional ops.warp (fp32)
-    of the one float result, then an optional ops.resize (fp32), then an optional colour look (ops.lut3d, fp32), then an optional
-    sharpening (ops.sharpen, fp32), then the encoders of _encode."""
+    of the one float result, then an optional ops.resize (fp32), then an optional local tone mapping (ops.tone_map, fp32: three launches),
+    then an optional colour look (ops.lut3d, fp32), then an optional sharpening (ops.sharpen, fp32), then the encoders of _encode."""
     if outs is None:
         return _encode(y, bits)
     res = []
     for o in outs:
         t = y if o.warp is None else ops.warp(y, o.warp)
         t = t if o.resize is None else ops.resize(t, o.resize)
+        if o.tone is not None:
+            t = ops.tone_map(t, o.tone)
         if o.look is not None:
             t = ops.lut3d(t, o.look)
         if o.sharpen is not None:

@@ -31,6 +31,7 @@ RC_WARP_BILINEAR, RC_WARP_BICUBIC = 0, 1
 RC_WARP_CLAMP, RC_WARP_CONSTANT = 0, 1
 RC_WARP_MIN_CELL_LOG2, RC_WARP_MAX_CELL_LOG2, RC_WARP_MAX_DIM = 3, 6, 1 << 23
 RC_STATS_MAX_GRID, RC_STATS_SLOTS = 64, 8
+RC_TONE_MAX_GRID, RC_TONE_BINS = 16, 256
 RC_DEFECT_HOT, RC_DEFECT_COLD = 1, 2
 RC_CALIB_GAINS, RC_CALIB_CLIP, RC_CALIB_MAX_KNOTS = 1, 2, 16
 RC_HDR_MOTION = 1
@@ -126,6 +127,12 @@ class SharpenDesc(C.Structure):
     _fields_ = [("radius", C.c_int32), ("matrix", C.c_int32), ("amount", C.c_float), ("core", C.c_float), ("overshoot", C.c_float)]
 
 
+class ToneDesc(C.Structure):
+    """Mirror of `struct rc_tone_desc`."""
+    _fields_ = [("grid", C.c_int32 * 2), ("matrix", C.c_int32), ("clip_q8", C.c_int32), ("strength", C.c_float), ("max_gain", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
 class TemporalDesc(C.Structure):
     """Mirror of `struct rc_temporal_desc`."""
     _fields_ = [
@@ -160,6 +167,11 @@ _SIGS = {
     "rc_lut3d": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "rc_sharpen_desc_size": (_SZ, []),
     "rc_sharpen": (C.c_int, [_P, _I, _P, _I, C.POINTER(SharpenDesc), _I, _I, _I, _I, _I, _P]),
+    "rc_tone_desc_size": (_SZ, []),
+    "rc_tone_axis": (C.c_int, [_I, _I, _P, _P]),
+    "rc_tone_hist": (C.c_int, [_P, _I, C.POINTER(ToneDesc), _P, _I, _I, _I, _I, _I, _P]),
+    "rc_tone_gains": (C.c_int, [_P, C.POINTER(ToneDesc), _P, _I, _P]),
+    "rc_tone_apply": (C.c_int, [_P, _I, _P, _I, C.POINTER(ToneDesc), _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rc_warp": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_stats_desc_size": (_SZ, []),
     "rc_frame_stats": (C.c_int, [_P, _I, C.POINTER(StatsDesc), _P, _P, _I, _I, _I, _I, _I, _P]),

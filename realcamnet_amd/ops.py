@@ -830,6 +830,95 @@ def sharpen(y: torch.Tensor, sharpen, crop_hw: Optional[Tuple[int, int]] = None,
     return _R.sharpen(y, sharpen.radius, sharpen.matrix_code, sharpen.amount, sharpen.core, sharpen.overshoot, h, w, out_dtype)
 
 
+class _ToneTables:
+    """The owner of the tone axis tables' entries in the derived-value cache (`derived` keeps its values on an object)."""
+
+
+_TONE_TABLES = _ToneTables()
+
+
+def tone_axis_tables(n: int, g: int, device):
+    """idx (n,) int32 and wt (n,) fp32 on `device`: rc_tone_axis(n, g), built on the host and copied once per (n, g, device), then kept
+    through `derived` -- a warmed-up ops.tone_apply makes no host-to-device copy."""
+    from .tone import axis
+    device = torch.device(device)
+    key = (int(n), int(g), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    return derived(_TONE_TABLES, ("tone_axis",) + key, (), lambda: tuple(torch.from_numpy(a).to(device) for a in axis(int(n), int(g))))
+
+
+def _tone_source(y, tm, crop_hw, what):
+    """The checks the tone ops share: (y contiguous on the GPU, h, w)."""
+    from .tone import ToneMap
+    if not isinstance(tm, ToneMap):
+        raise TypeError(f"{what}: tm must be a ToneMap, got {type(tm).__name__}")
+    y = _req(y, f"{what} input")
+    if y.dim() != 4 or y.shape[1] != 3:
+        raise ValueError(f"{what}: expected (B,3,H,W), got {tuple(y.shape)}")
+    _dt(y)
+    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
+    if y.shape[0] < 1 or h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]:
+        raise ValueError(f"{what}: crop {(h, w)} of the source {tuple(y.shape)} is empty or exceeds it")
+    if y.shape[2] * y.shape[3] >= 1 << 29:
+        raise ValueError(f"{what}: a source plane of {tuple(y.shape[2:])} has 2^29 samples or more")
+    tm.check(h, w)
+    return y, h, w
+
+
+def _tone_desc(tm):
+    return [tm.grid[0], tm.grid[1], tm.matrix_code, tm.clip_q8], [tm.strength, tm.max_gain]
+
+
+def tone_hist(y: torch.Tensor, tm, crop_hw: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """Planar result (B,3,H,W), cropped to crop_hw, -> (B,gy,gx,256) int32: per tile of the ToneMap `tm` the histogram of the 8-bit luma
+    code (rc_tone_hist; the arithmetic is fixed in include/realcam_hip.h).  One launch and a memset, no device state."""
+    y, h, w = _tone_source(y, tm, crop_hw, "tone_hist")
+    ints, floats = _tone_desc(tm)
+    return _R.tone_hist(y, ints, floats, h, w)
+
+
+def tone_gains(hist: torch.Tensor, tm) -> torch.Tensor:
+    """Tile histograms (B,gy,gx,256) int32 -> (B,gy,gx,256) fp32: per tile the clipped, redistributed and accumulated histogram as a table
+    of gains (rc_tone_gains).  One launch.  A video caller smooths the tables over time between this and tone_apply, e.g.
+    `state.lerp_(gains, 0.1)`, without a host sync."""
+    from .tone import BINS, ToneMap
+    if not isinstance(tm, ToneMap):
+        raise TypeError(f"tone_gains: tm must be a ToneMap, got {type(tm).__name__}")
+    hist = _req(hist, "tone_gains input")
+    if hist.dtype != torch.int32 or hist.dim() != 4 or hist.shape[0] < 1 or tuple(hist.shape[1:]) != (*tm.grid, BINS):
+        raise ValueError(f"tone_gains: expected an int32 tensor (B, {tm.grid[0]}, {tm.grid[1]}, {BINS}), got {tuple(hist.shape)} {hist.dtype}")
+    ints, floats = _tone_desc(tm)
+    return _R.tone_gains(hist, ints, floats)
+
+
+def tone_apply(y: torch.Tensor, gains: torch.Tensor, tm, crop_hw: Optional[Tuple[int, int]] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Planar result (B,3,H,W), cropped to crop_hw, and gain tables (1 or B, gy, gx, 256) fp32 -> (B,3,h,w): every pixel's R, G and B times
+    the gain that its luma finds in the tables of the four nearest tile centres, bilinearly interpolated (rc_tone_apply).  out_dtype:
+    torch.float32, or y's dtype (rounded to nearest even once).  One launch; the gains are read when the kernel runs."""
+    from .tone import BINS
+    y, h, w = _tone_source(y, tm, crop_hw, "tone_apply")
+    if out_dtype not in (torch.float32, y.dtype):
+        raise ValueError(f"tone_apply: out_dtype must be torch.float32 or the source's {y.dtype}, got {out_dtype}")
+    if (not isinstance(gains, torch.Tensor) or gains.dtype != torch.float32 or gains.device != y.device or gains.dim() != 4
+            or gains.shape[0] not in (1, y.shape[0]) or tuple(gains.shape[1:]) != (*tm.grid, BINS)):
+        raise ValueError(f"tone_apply: the gains must be a float32 tensor (1 or {y.shape[0]}, {tm.grid[0]}, {tm.grid[1]}, {BINS}) on {y.device}")
+    gains = gains.contiguous()
+    if isinstance(y, FakeTensor):                              # a trace: shapes only, nothing is built, copied or kept
+        iy, uy = y.new_empty((h,), dtype=torch.int32), y.new_empty((h,), dtype=torch.float32)
+        ix, ux = y.new_empty((w,), dtype=torch.int32), y.new_empty((w,), dtype=torch.float32)
+    else:
+        if gains.data_ptr() % 16:
+            gains = gains.clone()                              # the kernel stages whole tables with 16-byte loads
+        (iy, uy), (ix, ux) = tone_axis_tables(h, tm.grid[0], y.device), tone_axis_tables(w, tm.grid[1], y.device)
+    ints, floats = _tone_desc(tm)
+    return _R.tone_apply(y, gains, iy, uy, ix, ux, ints, floats, h, w, out_dtype)
+
+
+def tone_map(y: torch.Tensor, tm, crop_hw: Optional[Tuple[int, int]] = None, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Local tone mapping of the planar result (B,3,H,W), cropped to crop_hw, as the ToneMap `tm` asks: tone_hist, tone_gains and
+    tone_apply in a row -- three launches, no device state, no host sync, so the call replays under a captured graph."""
+    return tone_apply(y, tone_gains(tone_hist(y, tm, crop_hw), tm), tm, crop_hw, out_dtype)
+
+
 _WARP_MESHES = {}        # (Warp, device) -> the device mesh of rc_warp
 
 

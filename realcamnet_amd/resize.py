@@ -6,7 +6,7 @@ function rc_resize_taps, which holds the one copy of the filter arithmetic.
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 from typing import Optional, Tuple
 
 from . import _lib
@@ -14,6 +14,7 @@ from .look import Lut3D
 from .out_format import OutFormat
 from .sharpen import Sharpen
 from .stats import Stats
+from .tone import ToneMap
 from .warp import Warp
 
 FILTERS = {"area": _lib.RC_FILTER_AREA, "bilinear": _lib.RC_FILTER_BILINEAR}
@@ -97,8 +98,8 @@ class Resize:
 
 @dataclass(frozen=True)
 class Output:
-    """One entry of forward_mosaic(outputs=[...]): an optional Warp of the float result, an optional Resize, an optional colour look, an
-    optional Sharpen, then its format.
+    """One entry of forward_mosaic(outputs=[...]): an optional Warp of the float result, an optional Resize, an optional ToneMap, an
+    optional colour look, an optional Sharpen, then its format.
 
     format  None (the planar float tensor), "rgb8" / "rgb16" (interleaved uint8 / uint16), an OutFormat (a YuvFrames) or a Stats (a
             FrameStats: the statistics of the frame after this output's own warp / resize / look, in place of a picture).
@@ -107,6 +108,11 @@ class Output:
     warp    None or a Warp, applied first (ops.warp, fp32): the resize's window and the format then see a frame of warp.size.
     sharpen None or a Sharpen, applied last among the float stages (ops.sharpen, fp32): its thresholds are meant in the values the encoder
             and the viewer see, and nothing resamples or remaps the picture after it.
+    tone    None or a ToneMap, applied after the resize and before the look (ops.tone_map, fp32): a show LUT is designed against a normally
+            exposed picture, so the scene-adaptive lift comes first.
+    The first five are dataclass fields.  `tone` is an init-only parameter kept as an attribute: dataclasses.fields(Output) stays the five
+    names callers know, while the constructor (sixth position or keyword), equality, hash, repr and dataclasses.replace all take
+    `tone` in.
     """
 
     format: object = None
@@ -114,8 +120,9 @@ class Output:
     look: Optional[Lut3D] = None
     warp: Optional[Warp] = None
     sharpen: Optional[Sharpen] = None
+    tone: InitVar[Optional[ToneMap]] = None
 
-    def __post_init__(self):
+    def __post_init__(self, tone=None):
         f = self.format
         if f is not None and not isinstance(f, (str, OutFormat, Stats)):
             raise TypeError(f"Output.format must be None, 'rgb8', 'rgb16', an OutFormat or a Stats, got {type(f).__name__}")
@@ -129,10 +136,25 @@ class Output:
             raise TypeError(f"Output.warp must be None or a Warp, got {type(self.warp).__name__}")
         if self.sharpen is not None and not isinstance(self.sharpen, Sharpen):
             raise TypeError(f"Output.sharpen must be None or a Sharpen, got {type(self.sharpen).__name__}")
+        if tone is not None and not isinstance(tone, ToneMap):
+            raise TypeError(f"Output.tone must be None or a ToneMap, got {type(tone).__name__}")
+        object.__setattr__(self, "tone", tone)
         if isinstance(f, OutFormat) and self.resize is not None and (self.resize.size[0] % 2 or self.resize.size[1] % 2):
             raise ValueError(f"Output: 4:2:0 ({f.layout}) needs an even height and width, Resize.size is {self.resize.size}")
         if isinstance(f, OutFormat) and self.resize is None and self.warp is not None and (self.warp.size[0] % 2 or self.warp.size[1] % 2):
             raise ValueError(f"Output: 4:2:0 ({f.layout}) needs an even height and width, Warp.size is {self.warp.size} and no Resize follows it")
+
+    def _key(self):
+        return (self.format, self.resize, self.look, self.warp, self.sharpen, self.tone)
+
+    def __eq__(self, other):
+        return self._key() == other._key() if other.__class__ is self.__class__ else NotImplemented
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "Output(" + ", ".join(f"{n}={v!r}" for n, v in zip(("format", "resize", "look", "warp", "sharpen", "tone"), self._key())) + ")"
 
     def plan(self, h: int, w: int) -> Tuple[int, int]:
         """The (h, w) this output has for an (h, w) result; every refusal that depends on the frame is raised here, before any launch."""
@@ -142,6 +164,8 @@ class Output:
         if self.resize is not None:
             self.resize.window(h, w)
             h, w = self.resize.size
+        if self.tone is not None:
+            self.tone.check(h, w)
         if isinstance(self.format, OutFormat):
             self.format.plane_layout(h, w)
         if isinstance(self.format, Stats):

@@ -207,6 +207,53 @@ def _sharpen_launch(out, y, radius, matrix, amount, core, overshoot, h, w, dtype
 define("sharpen(Tensor y, int radius, int matrix, float amount, float core, float overshoot, int h, int w, ScalarType dtype) -> Tensor",
        lambda y, radius, matrix, amount, core, overshoot, h, w, dtype: y.new_empty((y.shape[0], 3, h, w), dtype=dtype), _sharpen_launch)
 
+
+def _tone_desc(ints, floats):
+    if len(ints) != 4 or len(floats) != 2:
+        raise ValueError(f"realcam::tone_*: ints holds gy, gx, matrix, clip_q8 and floats strength, max_gain; got {ints!r}, {floats!r}")
+    return _lib.ToneDesc(grid=(C.c_int32 * 2)(ints[0], ints[1]), matrix=ints[2], clip_q8=ints[3], strength=floats[0], max_gain=floats[1])
+
+
+def _tone_hist_launch(hist, y, ints, floats, h, w):
+    d = _tone_desc(ints, floats)
+    check(lib().rc_tone_hist(y.data_ptr(), _dt(y), C.byref(d), hist.data_ptr(), y.shape[0], y.shape[2], y.shape[3], h, w, _stream()), "rc_tone_hist")
+
+
+# y (B,3,H,W) planar, cropped to (h,w) -> (B,gy,gx,256) int32: the tiles' luma-code histograms; ints: gy, gx, matrix, clip_q8; floats: strength,
+# max_gain (the fields of rc_tone_desc).  The output is not zeroed here: the entry point does that on the stream
+define("tone_hist(Tensor y, int[] ints, float[] floats, int h, int w) -> Tensor",
+       lambda y, ints, floats, h, w: y.new_empty((y.shape[0], ints[0], ints[1], _lib.RC_TONE_BINS), dtype=torch.int32), _tone_hist_launch)
+
+
+def _tone_gains_launch(gains, hist, ints, floats):
+    d = _tone_desc(ints, floats)
+    if hist.dtype != torch.int32 or not hist.is_contiguous() or tuple(hist.shape[1:]) != (ints[0], ints[1], _lib.RC_TONE_BINS):
+        raise ValueError(f"realcam::tone_gains: hist must be a contiguous int32 tensor (B, {ints[0]}, {ints[1]}, {_lib.RC_TONE_BINS}), got {tuple(hist.shape)} {hist.dtype}")
+    check(lib().rc_tone_gains(hist.data_ptr(), C.byref(d), gains.data_ptr(), hist.shape[0], _stream()), "rc_tone_gains")
+
+
+# hist (B,gy,gx,256) int32 -> (B,gy,gx,256) fp32: the tiles' gain tables
+define("tone_gains(Tensor hist, int[] ints, float[] floats) -> Tensor",
+       lambda hist, ints, floats: hist.new_empty(tuple(hist.shape), dtype=torch.float32), _tone_gains_launch)
+
+
+def _tone_apply_launch(out, y, gains, iy, uy, ix, ux, ints, floats, h, w, dtype):
+    d = _tone_desc(ints, floats)
+    for name, t, dt, n in (("iy", iy, torch.int32, h), ("uy", uy, torch.float32, h), ("ix", ix, torch.int32, w), ("ux", ux, torch.float32, w)):
+        if t.dtype != dt or t.device != y.device or not t.is_contiguous() or tuple(t.shape) != (n,):
+            raise ValueError(f"realcam::tone_apply: table {name} must be a contiguous {dt} tensor of {n} entries on {y.device}")
+    if (gains.dtype != torch.float32 or gains.device != y.device or not gains.is_contiguous() or gains.dim() != 4 or gains.shape[0] not in (1, y.shape[0])
+            or tuple(gains.shape[1:]) != (ints[0], ints[1], _lib.RC_TONE_BINS)):
+        raise ValueError(f"realcam::tone_apply: the gains must be a contiguous float32 tensor (1 or {y.shape[0]}, {ints[0]}, {ints[1]}, {_lib.RC_TONE_BINS}) on {y.device}")
+    check(lib().rc_tone_apply(y.data_ptr(), _dt(y), out.data_ptr(), _DT[dtype], C.byref(d), gains.data_ptr(), gains.shape[0], iy.data_ptr(), uy.data_ptr(),
+                              ix.data_ptr(), ux.data_ptr(), y.shape[0], y.shape[2], y.shape[3], h, w, _stream()), "rc_tone_apply")
+
+
+# y (B,3,H,W) planar, cropped to (h,w), -> (B,3,h,w) of `dtype` (fp32 or y's); gains (1 or B,gy,gx,256) fp32; the device tables of rc_tone_axis:
+# iy (h,) int32, uy (h,) fp32, ix (w,), ux (w,)
+define("tone_apply(Tensor y, Tensor gains, Tensor iy, Tensor uy, Tensor ix, Tensor ux, int[] ints, float[] floats, int h, int w, ScalarType dtype) -> Tensor",
+       lambda y, gains, iy, uy, ix, ux, ints, floats, h, w, dtype: y.new_empty((y.shape[0], 3, h, w), dtype=dtype), _tone_apply_launch)
+
 def _warp_launch(out, y, mesh, cell, interp, border, fill, h, w, oh, ow, dtype):
     gh, gw = -(-oh // cell) + 1, -(-ow // cell) + 1
     if (mesh.dtype != torch.float32 or mesh.device != y.device or not mesh.is_contiguous() or mesh.dim() != 4 or tuple(mesh.shape[1:]) != (gh, gw, 2)
