@@ -19,11 +19,11 @@
 //             block, non-zero bins only, with 64-bit global atomics.
 // Widths (the bound of every partial is written where it is declared): everything after the codes is integer, so the order of the adds
 // does not matter and the result is bit-exact and the same from run to run.
-#include "common.hpp"
+#include "rgb_strip.hpp"
 
 namespace rc {
 
-constexpr int kStatsPx = 4, kStatsWaves = 4, kStatsRows = 16, kStatsThreads = 64 * kStatsWaves;
+constexpr int kStatsPx = kRgbPx, kStatsWaves = 4, kStatsRows = 16, kStatsThreads = 64 * kStatsWaves;
 constexpr int kStatsTileW = 64 * kStatsPx, kStatsTileH = kStatsWaves * kStatsRows;
 constexpr int kStatsMaxBins = 1024, kStatsSlots = RC_STATS_SLOTS, kStatsGrid = RC_STATS_MAX_GRID;
 
@@ -32,7 +32,8 @@ struct StatsArgs {
     int org, rh, rw;           // the ROI inside it: its first sample y0 W + x0 and its size
     int gy, gx;
     int nbins, dark, clip;
-    float fS, kr, kg, kb;      // float(S) and the luma coefficients
+    float fS;                  // float(S)
+    Luma k;
     int ntx, ntiles, nblk;     // tiles per ROI row of tiles, tiles per frame, blocks per frame
     int vec;                   // every lane's 4 samples start on a 4-sample boundary of the source
 };
@@ -43,34 +44,16 @@ struct StatsRow {
     int yr;                    // qY of the pixel right of the lane's last one (meaningful where that pixel is inside the ROI)
 };
 
-__device__ __forceinline__ float stats_unit(float v) { return v > 0.f ? (v < 1.f ? v : 1.f) : 0.f; }    // NaN compares false: 0
-
 __device__ __forceinline__ int stats_code(float v, float fS) {
     const float q = rintf(__fmul_rn(v, fS));                    // round half to even; v is in [0, 1 + a few ulp] and never NaN here
     return (int)__builtin_amdgcn_fmed3f(q, 0.f, fS);            // the clamp as one median: 16 codes' compare pairs would crowd the scalar registers
 }
 
 // float(S) and the luma coefficients
-struct StatsCoef { float fS, kr, kg, kb; };
+struct StatsCoef { float fS; Luma k; };
 
 __device__ __forceinline__ int stats_luma(const StatsCoef& a, float r, float g, float b) {
-    return stats_code(__fadd_rn(__fadd_rn(__fmul_rn(a.kr, r), __fmul_rn(a.kg, g)), __fmul_rn(a.kb, b)), a.fS);
-}
-
-template <typename TI> __device__ __forceinline__ void stats_load4(const TI* p, float* f);
-template <> __device__ __forceinline__ void stats_load4<float>(const float* p, float* f) {
-    const float4 v = *reinterpret_cast<const float4*>(p);
-    f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-}
-template <> __device__ __forceinline__ void stats_load4<bf16_t>(const bf16_t* p, float* f) {
-    const uint2 v = *reinterpret_cast<const uint2*>(p);
-    f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-    f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-}
-template <> __device__ __forceinline__ void stats_load4<f16_t>(const f16_t* p, float* f) {
-    const uint2 v = *reinterpret_cast<const uint2*>(p);
-    f[0] = Vec16<f16_t>::lo(v.x); f[1] = Vec16<f16_t>::hi(v.x);
-    f[2] = Vec16<f16_t>::lo(v.y); f[3] = Vec16<f16_t>::hi(v.y);
+    return stats_code(rgb_luma(a.k, r, g, b), a.fS);
 }
 
 // The codes of ROI row y for the lane's pixels px0 .. px0 + 3 (cnt = rw - px0 of them are inside the ROI; <= 0: none, and nothing is read).
@@ -79,9 +62,12 @@ template <typename TI>
 __device__ __forceinline__ void stats_row(const StatsArgs& a, const StatsCoef& cf, const TI* __restrict__ frame, int y, int px0, int cnt, int cnt63, StatsRow& o) {
     const uint32_t plane = (uint32_t)a.plane, at = (uint32_t)a.org + (uint32_t)y * (uint32_t)a.W + (uint32_t)px0;
     float px[3][kStatsPx];
+    // One branch for the three planes, and the element path written out with its index formed in 32 bits: through rgb_load the offsets
+    // k fold into the loads' immediates, the whole kernel is scheduled differently (95 / 96 VGPRs, 77 instructions fewer) and runs 14 to
+    // 19 % slower on 4K frames (profiles/output_strip_refactor.md).
     if (cnt >= kStatsPx && a.vec) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) stats_load4<TI>(frame + c * plane + at, px[c]);
+        for (int c = 0; c < 3; ++c) rgb_load<TI>(frame + c * plane + at, true, kStatsPx, px[c]);
     } else {
 #pragma unroll
         for (int c = 0; c < 3; ++c)
@@ -90,13 +76,13 @@ __device__ __forceinline__ void stats_row(const StatsArgs& a, const StatsCoef& c
     }
 #pragma unroll
     for (int k = 0; k < kStatsPx; ++k) {
-        const float r = stats_unit(px[0][k]), g = stats_unit(px[1][k]), b = stats_unit(px[2][k]);
+        const float r = rgb_unit(px[0][k]), g = rgb_unit(px[1][k]), b = rgb_unit(px[2][k]);
         o.rgb[k] = (uint32_t)stats_code(r, cf.fS) | ((uint32_t)stats_code(g, cf.fS) << 10) | ((uint32_t)stats_code(b, cf.fS) << 20);
         o.y[k] = stats_luma(cf, r, g, b);
     }
     int yr = __shfl_down(o.y[0], 1);                            // the next lane's first pixel: px0 + 4
     if (cnt63 > kStatsPx)                                       // ... which for the last lane (cnt63 = cnt there, 0 elsewhere) belongs to the tile to the right
-        yr = stats_luma(cf, stats_unit(to_f32(frame[at + kStatsPx])), stats_unit(to_f32(frame[plane + at + kStatsPx])), stats_unit(to_f32(frame[2 * plane + at + kStatsPx])));
+        yr = stats_luma(cf, rgb_unit(to_f32(frame[at + kStatsPx])), rgb_unit(to_f32(frame[plane + at + kStatsPx])), rgb_unit(to_f32(frame[2 * plane + at + kStatsPx])));
     o.yr = yr;
 }
 
@@ -163,7 +149,7 @@ __global__ void __launch_bounds__(kStatsThreads) frame_stats_kernel(StatsArgs a,
     int last[4] = {0, 0, 0, 0};                                                   // per channel: the code of the current run ...
     uint32_t run[4] = {0u, 0u, 0u, 0u};                                           // ... and its length, at most the lane's pixels < 2^29
 
-    StatsCoef cf = {a.fS, a.kr, a.kg, a.kb};
+    StatsCoef cf = {a.fS, a.k};
     int dark = a.dark, clip = a.clip;
     int ty = 0, tx = blockIdx.x;                                                  // tile t = ty ntx + tx, walked without a division
     for (int t = blockIdx.x; t < a.ntiles; t += a.nblk, tx += a.nblk) {
@@ -240,8 +226,6 @@ __global__ void __launch_bounds__(kStatsThreads) frame_stats_kernel(StatsArgs a,
     }
 }
 
-static const double kStatsKrKb[3][2] = RC_YUV_KR_KB;
-
 }  // namespace rc
 
 using namespace rc;
@@ -253,8 +237,9 @@ size_t rc_stats_desc_size(void) { return sizeof(rc_stats_desc); }
 int rc_frame_stats(const void* d_src, int src_dtype, const rc_stats_desc* desc, long long* d_hist, long long* d_zones,
                    int batch, int H, int W, int h, int w, void* stream) {
     RC_REQUIRE(d_src && desc && d_hist && d_zones, "rc_frame_stats: null pointer");
-    RC_REQUIRE(src_dtype == RC_F32 || src_dtype == RC_BF16 || src_dtype == RC_F16, "rc_frame_stats: bad dtype");
-    RC_REQUIRE(batch >= 1 && batch <= 65535 && h >= 1 && w >= 1 && h <= H && w <= W, "rc_frame_stats: bad shape (empty, more than 65535 frames, or the crop exceeds the source)");
+    RgbSide src;
+    if (int e = rgb_source("rc_frame_stats", d_src, src_dtype, batch, H, W, h, w, &src)) return e;
+    RC_REQUIRE(batch <= 65535, "rc_frame_stats: bad shape (more than 65535 frames)");
     RC_REQUIRE((long long)H * W < (1LL << 29), "rc_frame_stats: bad shape (a source plane of 2^29 samples or more)");
     RC_REQUIRE(desc->bits == 8 || desc->bits == 10, "rc_frame_stats: bits must be 8 or 10");
     RC_REQUIRE(desc->matrix >= RC_MATRIX_BT601 && desc->matrix <= RC_MATRIX_BT2020, "rc_frame_stats: unknown matrix");
@@ -270,19 +255,15 @@ int rc_frame_stats(const void* d_src, int src_dtype, const rc_stats_desc* desc, 
     RC_REQUIRE(desc->clip >= 1 && desc->clip <= nbins, "rc_frame_stats: clip must lie in 1 .. 2^bits");
     RC_REQUIRE(desc->dark >= -1 && desc->dark <= nbins - 1, "rc_frame_stats: dark must lie in -1 .. 2^bits - 1");
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_hist) % 8 == 0 && reinterpret_cast<uintptr_t>(d_zones) % 8 == 0, "rc_frame_stats: the outputs must be 8-byte aligned");
-    const size_t es = dtype_size(src_dtype);
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % es == 0, "rc_frame_stats: src misaligned");
 
     StatsArgs a;
     a.W = W; a.plane = H * W; a.org = y0 * W + x0; a.rh = rh; a.rw = rw; a.gy = gy; a.gx = gx;
     a.nbins = nbins; a.dark = desc->dark; a.clip = desc->clip;
     a.fS = (float)(nbins - 1);
-    const double kr = kStatsKrKb[desc->matrix][0], kb = kStatsKrKb[desc->matrix][1];      // as rc_yuv_encode forms them
-    a.kr = (float)kr; a.kb = (float)kb; a.kg = (float)(1.0 - kr - kb);
+    a.k = rgb_coef(desc->matrix).k;
     a.ntx = ceil_div(rw, kStatsTileW);
     a.ntiles = a.ntx * ceil_div(rh, kStatsTileH);                                         // < 2^29 / 256 + 2^29 / 64
-    // then every plane, row and lane starts on a 4-sample boundary
-    a.vec = reinterpret_cast<uintptr_t>(d_src) % (kStatsPx * es) == 0 && W % kStatsPx == 0 && x0 % kStatsPx == 0;
+    a.vec = src.vec && x0 % kStatsPx == 0;                                                // then every lane, too, starts on a 4-sample boundary
     // persistent blocks: 4 per CU fit (33 KB of LDS, <= 128 VGPRs) shared among the frames, and no more than a third of the tiles, so
     // that a block's one histogram flush is paid by at least three tiles
     const int cap = std::max(1, 4 * device_cu_count() / batch);
@@ -293,9 +274,10 @@ int rc_frame_stats(const void* d_src, int src_dtype, const rc_stats_desc* desc, 
     const dim3 grid((unsigned)nblk, (unsigned)batch), block(kStatsThreads);
     unsigned long long* hist = reinterpret_cast<unsigned long long*>(d_hist);
     unsigned long long* zones = reinterpret_cast<unsigned long long*>(d_zones);
-    if (src_dtype == RC_F32) hipLaunchKernelGGL(frame_stats_kernel<float>, grid, block, 0, st, a, static_cast<const float*>(d_src), hist, zones);
-    else if (src_dtype == RC_BF16) hipLaunchKernelGGL(frame_stats_kernel<bf16_t>, grid, block, 0, st, a, static_cast<const bf16_t*>(d_src), hist, zones);
-    else hipLaunchKernelGGL(frame_stats_kernel<f16_t>, grid, block, 0, st, a, static_cast<const f16_t*>(d_src), hist, zones);
+    by_source(src_dtype, [&](auto ti) {
+        typedef typename decltype(ti)::type TI;
+        hipLaunchKernelGGL(frame_stats_kernel<TI>, grid, block, 0, st, a, static_cast<const TI*>(d_src), hist, zones);
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

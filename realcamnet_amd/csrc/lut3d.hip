@@ -15,11 +15,11 @@
 // Arithmetic: fp32, every product and every sum rounded on its own (__fmul_rn / __fadd_rn / __fsub_rn: no contraction whatever the
 // compile flags say), so the vector path, the element path and a plain elementwise restatement give the same bits.  The node indices
 // are clamped to [0, n - 2] after the NaN rule: no input makes the kernel read outside the table.
-#include "common.hpp"
+#include "rgb_strip.hpp"
 
 namespace rc {
 
-constexpr int kLutPx = 4, kLutStrips = 64, kLutRows = 4, kLutThreads = kLutStrips * kLutRows;
+constexpr int kLutPx = kRgbPx, kLutStrips = 64, kLutRows = 4, kLutThreads = kLutStrips * kLutRows;
 constexpr int kLutLdsMax = 17, kLutLdsStrips = 256, kLutLdsThreads = kLutLdsStrips * kLutRows;     // the LDS form: tables up to 17^3 x 16 bytes, blocks of 16 waves
 
 struct Lut3dArgs {
@@ -29,44 +29,25 @@ struct Lut3dArgs {
     int vec_src, vec_dst;      // every source row segment / every destination strip starts on a vector boundary
 };
 
-__device__ __forceinline__ float lut_unit(float v) { return v > 0.f ? (v < 1.f ? v : 1.f) : 0.f; }    // NaN compares false: 0
-
 // One channel's node index and fraction: p = c (n - 1), i = min(int(floor(p)), n - 2), f = p - i (exact).
 __device__ __forceinline__ void lut_cell(float c, const Lut3dArgs& a, int& i, float& f) {
-    const float p = __fmul_rn(lut_unit(c), a.scale);
+    const float p = __fmul_rn(rgb_unit(c), a.scale);
     i = min((int)p, a.n - 2);                                                      // p >= 0: truncation is floor
     f = __fsub_rn(p, (float)i);
 }
 
-// kLutPx values of T at p: one vector load when `vec`, else the first `cnt` as elements (the rest 0).
-template <typename T>
-__device__ __forceinline__ void lut_load(const T* p, bool vec, int cnt, float* f) {
-    if (vec) {
-        if constexpr (sizeof(T) == 4) {
-            Vec16<float>::unpack(*reinterpret_cast<const uint4*>(p), f);
-        } else {
-            const uint2 raw = *reinterpret_cast<const uint2*>(p);
-            f[0] = lo16<T>(raw.x); f[1] = hi16<T>(raw.x); f[2] = lo16<T>(raw.y); f[3] = hi16<T>(raw.y);
+// rgb_strip.hpp's load, except that an fp32 vector is read in place: copied into words first (rgb_load), the two fp32 kernels wait twice
+// more for memory and run 9 % slower on 1080p and 720p fp32 frames (profiles/output_strip_refactor.md).
+template <typename TI>
+__device__ __forceinline__ void lut_load(const TI* p, bool vec, int cnt, float* f) {
+    if constexpr (sizeof(TI) == 4) {
+        if (vec) {
+            const float4& v = *reinterpret_cast<const float4*>(p);
+            f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
+            return;
         }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kLutPx; ++k) f[k] = k < cnt ? to_f32(p[k]) : 0.f;
     }
-}
-
-template <typename T>
-__device__ __forceinline__ void lut_store(T* p, bool vec, int cnt, const float* f) {
-    if (vec) {
-        if constexpr (sizeof(T) == 4) {
-            *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-        } else {
-            *reinterpret_cast<uint2*>(p) = make_uint2(Vec16<T>::rne(f[0]) | (Vec16<T>::rne(f[1]) << 16), Vec16<T>::rne(f[2]) | (Vec16<T>::rne(f[3]) << 16));
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kLutPx; ++k)
-            if (k < cnt) p[k] = from_f32<T>(f[k]);
-    }
+    rgb_load<TI>(p, vec, cnt, f);
 }
 
 template <typename TI, typename TO>
@@ -123,7 +104,7 @@ __device__ __forceinline__ void lut3d_strip(const Lut3dArgs& a, const TI* __rest
 #undef RC_LUT_MIX
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) lut_store<TO>(d + c * dplane, a.vec_dst && cnt == kLutPx, cnt, o[c]);
+    for (int c = 0; c < 3; ++c) rgb_store<TO>(d + c * dplane, a.vec_dst && cnt == kLutPx, cnt, o[c]);
 }
 
 template <typename TI, typename TO>
@@ -156,40 +137,32 @@ extern "C" {
 
 int rc_lut3d(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, const float* d_lut, int n, int batch, int H, int W, int h, int w, void* stream) {
     RC_REQUIRE(n >= RC_LUT3D_MIN_SIZE && n <= RC_LUT3D_MAX_SIZE, "rc_lut3d: table size outside 2 .. 65");
-    RC_REQUIRE(src_dtype == RC_F32 || src_dtype == RC_BF16 || src_dtype == RC_F16, "rc_lut3d: bad source dtype");
-    RC_REQUIRE(dst_dtype == RC_F32 || dst_dtype == src_dtype, "rc_lut3d: bad output dtype (fp32 or the source's)");
     RC_REQUIRE(d_src && d_dst && d_lut, "rc_lut3d: null pointer");
-    RC_REQUIRE(batch >= 1 && h >= 1 && w >= 1 && h <= H && w <= W, "rc_lut3d: bad shape (the crop exceeds the source)");
+    RgbSide src, dst;
+    if (int e = rgb_source("rc_lut3d", d_src, src_dtype, batch, H, W, h, w, &src)) return e;
+    if (int e = rgb_dest("rc_lut3d", d_dst, dst_dtype, src_dtype, w, &dst)) return e;
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_lut) % 16 == 0, "rc_lut3d: the table must be 16-byte aligned");
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % dtype_size(src_dtype) == 0 && reinterpret_cast<uintptr_t>(d_dst) % dtype_size(dst_dtype) == 0,
-               "rc_lut3d: misaligned pointer");
     Lut3dArgs a;
     a.H = H; a.W = W; a.h = h; a.w = w; a.n = n; a.scale = (float)(n - 1);
-    const size_t sv = kLutPx * dtype_size(src_dtype), dv = kLutPx * dtype_size(dst_dtype);
-    a.vec_src = reinterpret_cast<uintptr_t>(d_src) % sv == 0 && W % kLutPx == 0;          // then every plane and every row starts on a vector
-    a.vec_dst = reinterpret_cast<uintptr_t>(d_dst) % dv == 0 && w % kLutPx == 0;
+    a.vec_src = src.vec; a.vec_dst = dst.vec;
     const dim3 grid(ceil_div(w, kLutStrips * kLutPx), ceil_div(h, kLutRows), (unsigned)batch);
     RC_REQUIRE(grid.y <= 65535u && grid.z <= 65535u, "rc_lut3d: more than 65535 frames or 262140 rows");
     const float4* lut = reinterpret_cast<const float4*>(d_lut);
     const long long ctiles = ceil_div(w, kLutLdsStrips * kLutPx), per_frame = ctiles * grid.y, total = per_frame * batch;
-    if (n <= kLutLdsMax && total <= 0x7fffffffLL) {
-        const dim3 lgrid((unsigned)(total < device_cu_count() ? total : device_cu_count())), lblock(kLutLdsStrips, kLutRows);
-        const int lds = n * n * n * (int)sizeof(float4);
-#define LAUNCH(TI, TO) \
-    return launch_lds<&lut3d_lds_kernel<TI, TO>>(lgrid, lblock, lds, as_stream(stream), a, (int)ctiles, (int)per_frame, (int)total, static_cast<const TI*>(d_src), static_cast<TO*>(d_dst), lut)
-        if (src_dtype == RC_F32) LAUNCH(float, float);
-        else if (src_dtype == RC_BF16) { if (dst_dtype == RC_F32) LAUNCH(bf16_t, float); else LAUNCH(bf16_t, bf16_t); }
-        else { if (dst_dtype == RC_F32) LAUNCH(f16_t, float); else LAUNCH(f16_t, f16_t); }
-#undef LAUNCH
-    }
-#define LAUNCH(TI, TO) \
-    hipLaunchKernelGGL((lut3d_kernel<TI, TO>), grid, dim3(kLutStrips, kLutRows), 0, as_stream(stream), a, static_cast<const TI*>(d_src), static_cast<TO*>(d_dst), lut)
-    if (src_dtype == RC_F32) LAUNCH(float, float);
-    else if (src_dtype == RC_BF16) { if (dst_dtype == RC_F32) LAUNCH(bf16_t, float); else LAUNCH(bf16_t, bf16_t); }
-    else { if (dst_dtype == RC_F32) LAUNCH(f16_t, float); else LAUNCH(f16_t, f16_t); }
-#undef LAUNCH
-    RC_HIP_CHECK(hipGetLastError());
-    return RC_OK;
+    const bool in_lds = n <= kLutLdsMax && total <= 0x7fffffffLL;
+    return by_source_dest(src_dtype, dst_dtype, [&](auto ti, auto to) {
+        typedef typename decltype(ti)::type TI;
+        typedef typename decltype(to)::type TO;
+        const TI* s = static_cast<const TI*>(d_src);
+        TO* d = static_cast<TO*>(d_dst);
+        if (in_lds) {
+            const dim3 lgrid((unsigned)(total < device_cu_count() ? total : device_cu_count())), lblock(kLutLdsStrips, kLutRows);
+            return launch_lds<&lut3d_lds_kernel<TI, TO>>(lgrid, lblock, n * n * n * (int)sizeof(float4), as_stream(stream), a, (int)ctiles, (int)per_frame, (int)total, s, d, lut);
+        }
+        hipLaunchKernelGGL((lut3d_kernel<TI, TO>), grid, dim3(kLutStrips, kLutRows), 0, as_stream(stream), a, s, d, lut);
+        RC_HIP_CHECK(hipGetLastError());
+        return (int)RC_OK;
+    });
 }
 
 }  // extern "C"

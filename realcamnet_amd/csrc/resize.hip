@@ -13,7 +13,7 @@
 #include <cmath>
 #include <vector>
 
-#include "common.hpp"
+#include "rgb_strip.hpp"
 
 namespace rc {
 
@@ -159,23 +159,21 @@ int rc_resize_taps(int filter, int n, int off, int m, int* first, float* weights
 int rc_resize(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, int batch, int H, int W, int h, int w, const int* d_first_y, const float* d_wy,
               int taps_y, const int* d_first_x, const float* d_wx, int taps_x, void* stream) {
     RC_REQUIRE(d_src && d_dst && d_first_y && d_wy && d_first_x && d_wx, "rc_resize: null pointer");
-    RC_REQUIRE(src_dtype == RC_F32 || src_dtype == RC_BF16 || src_dtype == RC_F16, "rc_resize: bad source dtype");
-    RC_REQUIRE(dst_dtype == RC_F32 || dst_dtype == src_dtype, "rc_resize: bad output dtype (fp32 or the source's)");
-    RC_REQUIRE(batch >= 1 && h >= 1 && w >= 1 && h <= H && w <= W, "rc_resize: bad shape (the stage downscales or keeps the size)");
+    RgbSide src, dst;                                                             // the stage downscales or keeps the size: its output is a crop's size
+    if (int e = rgb_source("rc_resize", d_src, src_dtype, batch, H, W, h, w, &src)) return e;
+    if (int e = rgb_dest("rc_resize", d_dst, dst_dtype, src_dtype, w, &dst)) return e;
     RC_REQUIRE(taps_y >= 1 && taps_x >= 1 && taps_y <= RC_RESIZE_MAX_TAPS && taps_x <= RC_RESIZE_MAX_TAPS, "rc_resize: tap length outside 1 .. 20");
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % dtype_size(src_dtype) == 0 && reinterpret_cast<uintptr_t>(d_dst) % dtype_size(dst_dtype) == 0 &&
-               reinterpret_cast<uintptr_t>(d_first_y) % 4 == 0 && reinterpret_cast<uintptr_t>(d_wy) % 4 == 0 &&
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_first_y) % 4 == 0 && reinterpret_cast<uintptr_t>(d_wy) % 4 == 0 &&
                reinterpret_cast<uintptr_t>(d_first_x) % 4 == 0 && reinterpret_cast<uintptr_t>(d_wx) % 4 == 0, "rc_resize: misaligned pointer");
     const dim3 grid(ceil_div(w, kRsCols), ceil_div(h, kRsRows), (unsigned)batch * 3u);
     RC_REQUIRE(grid.y <= 65535u && batch <= 21845, "rc_resize: more than 21845 frames or 524280 output rows");
     ResizeArgs a;
     a.H = H; a.W = W; a.h = h; a.w = w; a.ty = taps_y; a.tx = taps_x;
-#define LAUNCH(TI, TO) \
-    hipLaunchKernelGGL((resize_kernel<TI, TO>), grid, dim3(kRsCols, kRsWaves), 0, as_stream(stream), a, static_cast<const TI*>(d_src), static_cast<TO*>(d_dst), d_first_y, d_wy, d_first_x, d_wx)
-    if (src_dtype == RC_F32) LAUNCH(float, float);
-    else if (src_dtype == RC_BF16) { if (dst_dtype == RC_F32) LAUNCH(bf16_t, float); else LAUNCH(bf16_t, bf16_t); }
-    else { if (dst_dtype == RC_F32) LAUNCH(f16_t, float); else LAUNCH(f16_t, f16_t); }
-#undef LAUNCH
+    by_source_dest(src_dtype, dst_dtype, [&](auto ti, auto to) {
+        typedef typename decltype(ti)::type TI;
+        typedef typename decltype(to)::type TO;
+        hipLaunchKernelGGL((resize_kernel<TI, TO>), grid, dim3(kRsCols, kRsWaves), 0, as_stream(stream), a, static_cast<const TI*>(d_src), static_cast<TO*>(d_dst), d_first_y, d_wy, d_first_x, d_wx);
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

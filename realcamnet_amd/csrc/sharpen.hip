@@ -23,13 +23,14 @@
 // sum and difference rounded on its own (__fmul_rn / __fadd_rn / __fsub_rn: no contraction whatever the compile flags say), so the vector
 // path, the element path and a plain elementwise restatement give the same bits.  Every tap is clamped to the crop: nothing outside
 // (h, w) is ever read.
-#include "common.hpp"
+#include "rgb_strip.hpp"
 
 #include <cmath>
 
 namespace rc {
 
 constexpr int kShPx = 4, kShWaves = 4, kShThreads = 64 * kShWaves;
+static_assert(kShPx == kRgbPx, "a lane holds one rgb_strip.hpp strip");
 constexpr int kShSpan = 64 * kShPx;               // columns a wave loads
 constexpr int kShOut = kShSpan - 2 * kShPx;       // columns it produces inside a row: strips start this far apart
 constexpr int kShRows = 32;                       // rows per band
@@ -37,66 +38,25 @@ constexpr int kShRows = 32;                       // rows per band
 struct SharpenArgs {
     int H, W, h, w;            // source plane, cropped / output plane
     int vec_src, vec_dst;      // every source row segment / every destination quad starts on a vector boundary
-    float kr, kg, kb;
+    Luma k;
     float amount, core, over;
 };
 
-__device__ __forceinline__ float sh_unit(float v) { return v > 0.f ? (v < 1.f ? v : 1.f) : 0.f; }    // NaN compares false: 0
+// The source words of a lane's 4 pixels of the three planes, as loaded (rgb_strip.hpp) ...
+template <typename TI> struct ShPx { RgbRaw<TI> c[3]; };
 
-// The source words of a lane's 4 pixels of the three planes, as loaded.
-template <typename TI> struct ShRaw { uint32_t w[3][sizeof(TI) == 4 ? 4 : 2]; };
-
+// ... and step 1 of them: float(src), NaN -> 0, clamped to [0, 1].
 template <typename TI>
-__device__ __forceinline__ void sh_load(const TI* p, bool vec, int cnt, uint32_t* w) {
-    if constexpr (sizeof(TI) == 4) {
-        if (vec) {
-            const uint4 v = *reinterpret_cast<const uint4*>(p);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        } else {
+__device__ __forceinline__ void sh_decode(const ShPx<TI>& px, float (*f)[kShPx]) {
 #pragma unroll
-            for (int k = 0; k < kShPx; ++k) w[k] = k < cnt ? __float_as_uint(p[k]) : 0u;
-        }
-    } else {
-        if (vec) {
-            const uint2 v = *reinterpret_cast<const uint2*>(p);
-            w[0] = v.x; w[1] = v.y;
-        } else {
-            const uint16_t* q = reinterpret_cast<const uint16_t*>(p);
-            uint32_t e[kShPx];
+    for (int p = 0; p < 3; ++p) {
 #pragma unroll
-            for (int k = 0; k < kShPx; ++k) e[k] = k < cnt ? (uint32_t)q[k] : 0u;
-            w[0] = e[0] | (e[1] << 16); w[1] = e[2] | (e[3] << 16);
-        }
-    }
-}
-
-template <typename TI>
-__device__ __forceinline__ void sh_decode(const uint32_t* w, float* f) {     // step 1: float(src), NaN -> 0, clamped to [0, 1]
-    if constexpr (sizeof(TI) == 4) {
-#pragma unroll
-        for (int k = 0; k < kShPx; ++k) f[k] = sh_unit(__uint_as_float(w[k]));
-    } else {
-        f[0] = sh_unit(lo16<TI>(w[0])); f[1] = sh_unit(hi16<TI>(w[0])); f[2] = sh_unit(lo16<TI>(w[1])); f[3] = sh_unit(hi16<TI>(w[1]));
-    }
-}
-
-template <typename TO>
-__device__ __forceinline__ void sh_store(TO* p, bool vec, int cnt, const float* f) {
-    if (vec) {
-        if constexpr (sizeof(TO) == 4) {
-            *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-        } else {
-            *reinterpret_cast<uint2*>(p) = make_uint2(Vec16<TO>::rne(f[0]) | (Vec16<TO>::rne(f[1]) << 16), Vec16<TO>::rne(f[2]) | (Vec16<TO>::rne(f[3]) << 16));
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kShPx; ++k)
-            if (k < cnt) p[k] = from_f32<TO>(f[k]);
+        for (int k = 0; k < kShPx; ++k) f[p][k] = rgb_unit(rgb_pixel<TI>(px.c[p], k));
     }
 }
 
 // A row as a wave holds it.  Which fields of which window row are live is in the header comment; the rest is dead and costs no register.
-template <typename TI> struct ShRow { float S[kShPx], L[kShPx], mn[kShPx], mx[kShPx]; ShRaw<TI> px; };
+template <typename TI> struct ShRow { float S[kShPx], L[kShPx], mn[kShPx], mx[kShPx]; ShPx<TI> px; };
 
 // The binomial of five (radius 2) or three (radius 1) values in the header's order of additions; m is the centre.
 template <int R>
@@ -127,11 +87,11 @@ __global__ void __launch_bounds__(kShThreads) sharpen_kernel(SharpenArgs a, cons
     TO* d = dst + (size_t)frame * 3 * (size_t)dplane;
 
     auto load = [&](int y) {
-        ShRaw<TI> r = {};
+        ShPx<TI> r = {};
         if (act) {
             const uint32_t o = (uint32_t)y * (uint32_t)a.W + (uint32_t)x0;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) sh_load<TI>(s + (c * splane + o), vin, n, r.w[c]);
+            for (int c = 0; c < 3; ++c) r.c[c] = rgb_words<TI>(s + (c * splane + o), vin, n);
         }
         return r;
     };
@@ -139,17 +99,16 @@ __global__ void __launch_bounds__(kShThreads) sharpen_kernel(SharpenArgs a, cons
     // the rows this wave reads: r0 - R .. r1 - 1 + R, clamped to the crop
     const int y_end = min(r1 - 1 + R, a.h - 1);
     int yr = max(r0 - R, 0);                                                       // the row whose words are in flight
-    ShRaw<TI> ahead = load(yr);
+    ShPx<TI> ahead = load(yr);
 
     auto next_row = [&](ShRow<TI>& o) {                                            // every lane of the wave runs this: the shifts need them all
         o.px = ahead;
         ++yr;
         if (yr <= y_end) ahead = load(yr);                                         // in flight while this row is worked on
         float c[3][kShPx];
+        sh_decode<TI>(o.px, c);
 #pragma unroll
-        for (int p = 0; p < 3; ++p) sh_decode<TI>(o.px.w[p], c[p]);
-#pragma unroll
-        for (int k = 0; k < kShPx; ++k) o.L[k] = __fadd_rn(__fadd_rn(__fmul_rn(a.kr, c[0][k]), __fmul_rn(a.kg, c[1][k])), __fmul_rn(a.kb, c[2][k]));
+        for (int k = 0; k < kShPx; ++k) o.L[k] = rgb_luma(a.k, c[0][k], c[1][k], c[2][k]);
 #pragma unroll
         for (int k = 1; k < kShPx; ++k) o.L[k] = k < n ? o.L[k] : o.L[k - 1];     // past the crop's last column: that column
         const float l2 = __shfl_up(o.L[2], 1), l3 = __shfl_up(o.L[3], 1), q0 = __shfl_down(o.L[0], 1), q1 = __shfl_down(o.L[1], 1);
@@ -170,8 +129,7 @@ __global__ void __launch_bounds__(kShThreads) sharpen_kernel(SharpenArgs a, cons
     auto emit = [&](int y, const ShRow<TI>* w) {
         const ShRow<TI>& m = w[R];
         float c[3][kShPx], o[3][kShPx];
-#pragma unroll
-        for (int p = 0; p < 3; ++p) sh_decode<TI>(m.px.w[p], c[p]);
+        sh_decode<TI>(m.px, c);
 #pragma unroll
         for (int k = 0; k < kShPx; ++k) {
             const float T = sh_binomial<R>(w[0].S[k], w[R - 1].S[k], m.S[k], w[R + 1].S[k], w[kWin - 1].S[k]);
@@ -192,7 +150,7 @@ __global__ void __launch_bounds__(kShThreads) sharpen_kernel(SharpenArgs a, cons
         if (owns) {
             const uint32_t off = (uint32_t)y * (uint32_t)a.w + (uint32_t)x0;
 #pragma unroll
-            for (int p = 0; p < 3; ++p) sh_store<TO>(d + (p * dplane + off), vout, n, o[p]);
+            for (int p = 0; p < 3; ++p) rgb_store<TO>(d + (p * dplane + off), vout, n, o[p]);
         }
     };
 
@@ -218,25 +176,21 @@ __global__ void __launch_bounds__(kShThreads) sharpen_kernel(SharpenArgs a, cons
 
 using namespace rc;
 
-static const double kShKrKb[3][2] = RC_YUV_KR_KB;
-
 extern "C" {
 
 size_t rc_sharpen_desc_size(void) { return sizeof(rc_sharpen_desc); }
 
 int rc_sharpen(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, const rc_sharpen_desc* desc, int batch, int H, int W, int h, int w, void* stream) {
     RC_REQUIRE(d_src && d_dst && desc, "rc_sharpen: null pointer");
-    RC_REQUIRE(src_dtype == RC_F32 || src_dtype == RC_BF16 || src_dtype == RC_F16, "rc_sharpen: bad source dtype");
-    RC_REQUIRE(dst_dtype == RC_F32 || dst_dtype == src_dtype, "rc_sharpen: bad output dtype (fp32 or the source's)");
+    RgbSide src, dst;
+    if (int e = rgb_source("rc_sharpen", d_src, src_dtype, batch, H, W, h, w, &src)) return e;
+    if (int e = rgb_dest("rc_sharpen", d_dst, dst_dtype, src_dtype, w, &dst)) return e;
     RC_REQUIRE(desc->radius == 1 || desc->radius == 2, "rc_sharpen: radius must be 1 or 2");
     RC_REQUIRE(desc->matrix >= 0 && desc->matrix <= 2, "rc_sharpen: bad matrix");
     RC_REQUIRE(std::isfinite(desc->amount) && desc->amount >= 0.f && desc->amount <= 8.f, "rc_sharpen: amount must be finite and lie in [0, 8]");
     RC_REQUIRE(std::isfinite(desc->core) && desc->core >= 0.f && desc->core <= 1.f, "rc_sharpen: core must be finite and lie in [0, 1]");
     RC_REQUIRE(std::isfinite(desc->overshoot) && desc->overshoot >= 0.f && desc->overshoot <= 1.f, "rc_sharpen: overshoot must be finite and lie in [0, 1]");
-    RC_REQUIRE(batch >= 1 && h >= 1 && w >= 1, "rc_sharpen: bad shape (an empty frame)");
-    RC_REQUIRE(h <= H && w <= W, "rc_sharpen: bad shape (the crop exceeds the source)");
-    const long long ss = (long long)dtype_size(src_dtype), ds = (long long)dtype_size(dst_dtype);
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % ss == 0 && reinterpret_cast<uintptr_t>(d_dst) % ds == 0, "rc_sharpen: misaligned pointer");
+    const long long ss = (long long)src.esize, ds = (long long)dst.esize;
     // a frame's element offsets are formed in 32 bits
     RC_REQUIRE(3LL * H * W * ss <= 0x7fffffffLL && 3LL * h * w * ds <= 0x7fffffffLL, "rc_sharpen: a frame's three planes (source, destination) must stay below 2 GiB");
     const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), s1 = s0 + (uintptr_t)(3LL * H * W * ss * batch);
@@ -245,25 +199,19 @@ int rc_sharpen(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, con
 
     SharpenArgs a;
     a.H = H; a.W = W; a.h = h; a.w = w;
-    a.vec_src = s0 % (uintptr_t)(kShPx * ss) == 0 && W % kShPx == 0;               // then every plane and every row starts on a vector
-    a.vec_dst = o0 % (uintptr_t)(kShPx * ds) == 0 && w % kShPx == 0;
-    // Kr, Kb -> Kg in double, each rounded to fp32 once: rc_yuv_encode's Y
-    const double kr = kShKrKb[desc->matrix][0], kb = kShKrKb[desc->matrix][1];
-    a.kr = (float)kr; a.kb = (float)kb; a.kg = (float)(1.0 - kr - kb);
+    a.vec_src = src.vec; a.vec_dst = dst.vec;
+    a.k = rgb_coef(desc->matrix).k;
     a.amount = desc->amount; a.core = desc->core; a.over = desc->overshoot;
     const int strips = 1 + (w > kShSpan ? ceil_div(w - kShSpan, kShOut) : 0);
     const dim3 grid((unsigned)ceil_div(strips, kShWaves), (unsigned)ceil_div(h, kShRows), (unsigned)batch), block(kShThreads);
     RC_REQUIRE(grid.y <= 65535u && grid.z <= 65535u, "rc_sharpen: more than 65535 frames or 2097120 rows");
     const hipStream_t st = as_stream(stream);
-#define LAUNCH(TI, TO)                                                                                                                           \
-    do {                                                                                                                                         \
-        if (desc->radius == 1) hipLaunchKernelGGL((sharpen_kernel<TI, TO, 1>), grid, block, 0, st, a, static_cast<const TI*>(d_src), static_cast<TO*>(d_dst)); \
-        else hipLaunchKernelGGL((sharpen_kernel<TI, TO, 2>), grid, block, 0, st, a, static_cast<const TI*>(d_src), static_cast<TO*>(d_dst));                   \
-    } while (0)
-    if (src_dtype == RC_F32) LAUNCH(float, float);
-    else if (src_dtype == RC_BF16) { if (dst_dtype == RC_F32) LAUNCH(bf16_t, float); else LAUNCH(bf16_t, bf16_t); }
-    else { if (dst_dtype == RC_F32) LAUNCH(f16_t, float); else LAUNCH(f16_t, f16_t); }
-#undef LAUNCH
+    by_source_dest(src_dtype, dst_dtype, [&](auto ti, auto to) {
+        typedef typename decltype(ti)::type TI;
+        typedef typename decltype(to)::type TO;
+        if (desc->radius == 1) hipLaunchKernelGGL((sharpen_kernel<TI, TO, 1>), grid, block, 0, st, a, static_cast<const TI*>(d_src), static_cast<TO*>(d_dst));
+        else hipLaunchKernelGGL((sharpen_kernel<TI, TO, 2>), grid, block, 0, st, a, static_cast<const TI*>(d_src), static_cast<TO*>(d_dst));
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

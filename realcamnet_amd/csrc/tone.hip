@@ -13,7 +13,7 @@
 // tone_gains_kernel: one block of 256 threads per tile, thread k owns bin k; the sums and the prefix sum are a Hillis-Steele scan in LDS,
 //   in 64-bit integers.  Off the hot path.
 // tone_apply_kernel: grid (strips of 256 columns, bands of 64 rows, frames), four waves per block, dynamic LDS.
-//   lane map   lane l holds the 4 pixels xs + 4 l .. + 3 of a row of each plane (sharpen.hip's loads and stores); ix / ux of these columns
+//   lane map   lane l holds the 4 pixels xs + 4 l .. + 3 of a row of each plane (rgb_strip.hpp's loads and stores); ix / ux of these columns
 //              are the lane's constants for the whole band.  Wave v takes rows v, v + 4, ... of a segment.
 //   segments   the band is cut where iy changes: inside a segment jy and jy' are fixed, so the block stages the gain tables of tile rows
 //              jy and jy', tile columns jx_lo .. jx_hi (what the strip can touch: at most ceil(256 / min tile width) + 3 of them, 1 KiB
@@ -23,54 +23,21 @@
 // 32-bit element offsets below a 64-bit frame base (the entry points check).  The arithmetic is step for step the header's: every product,
 // sum, difference and quotient rounded on its own (__fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn), so the vector path, the element path
 // and a plain elementwise restatement give the same bits.  Nothing outside the crop is ever read.
-#include "common.hpp"
+#include "rgb_strip.hpp"
 
 #include <cmath>
 
 namespace rc {
 
 constexpr int kTonePx = 4, kToneWaves = 4, kToneThreads = 64 * kToneWaves;
+static_assert(kTonePx == kRgbPx, "a lane holds one rgb_strip.hpp strip");
 constexpr int kToneSpan = 64 * kTonePx;           // columns of a piece (hist) and of a strip (apply)
 constexpr int kToneHistRows = 32;                 // rows of a hist slab
 constexpr int kToneBand = 64;                     // rows of an apply band
 constexpr int kToneBins = RC_TONE_BINS, kToneGrid = RC_TONE_MAX_GRID;
 
-__device__ __forceinline__ float tone_unit(float v) { return v > 0.f ? (v < 1.f ? v : 1.f) : 0.f; }    // NaN compares false: 0
-
 // a_i = ceil(i side / g) for i <= g <= 16 and side < 2^29: i side < 2^33, so 64 bits
 __host__ __device__ inline int tone_bound(int i, int side, int g) { return (int)(((long long)i * side + g - 1) / g); }
-
-// The source words of a lane's 4 pixels of one plane.
-template <typename TI>
-__device__ __forceinline__ void tone_load(const TI* p, bool vec, int cnt, float* f) {
-    if (vec) {
-        if constexpr (sizeof(TI) == 4) {
-            const float4 v = *reinterpret_cast<const float4*>(p);
-            f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
-        } else {
-            const uint2 v = *reinterpret_cast<const uint2*>(p);
-            f[0] = lo16<TI>(v.x); f[1] = hi16<TI>(v.x); f[2] = lo16<TI>(v.y); f[3] = hi16<TI>(v.y);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kTonePx; ++k) f[k] = k < cnt ? to_f32(p[k]) : 0.f;
-    }
-}
-
-template <typename TO>
-__device__ __forceinline__ void tone_store(TO* p, bool vec, int cnt, const float* f) {
-    if (vec) {
-        if constexpr (sizeof(TO) == 4) {
-            *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-        } else {
-            *reinterpret_cast<uint2*>(p) = make_uint2(Vec16<TO>::rne(f[0]) | (Vec16<TO>::rne(f[1]) << 16), Vec16<TO>::rne(f[2]) | (Vec16<TO>::rne(f[3]) << 16));
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kTonePx; ++k)
-            if (k < cnt) p[k] = from_f32<TO>(f[k]);
-    }
-}
 
 // The histograms start from zero: a launch on the stream, so that a captured graph replays it with the rest.
 __global__ void __launch_bounds__(kToneThreads) tone_zero_kernel(unsigned int* __restrict__ p, size_t n) {
@@ -82,7 +49,7 @@ struct ToneHistArgs {
     int H, W, h, w;            // source plane, crop
     int gy, gx;
     int vec;                   // every 4-sample group of every row starts on a vector boundary
-    float kr, kg, kb;
+    Luma k;
 };
 
 template <typename TI>
@@ -109,11 +76,11 @@ __global__ void __launch_bounds__(kToneThreads) tone_hist_kernel(ToneHistArgs a,
             const bool vec = a.vec && cnt == kTonePx;
             float c[3][kTonePx];
 #pragma unroll
-            for (int p = 0; p < 3; ++p) tone_load<TI>(s + (p * plane + o), vec, cnt, c[p]);
+            for (int p = 0; p < 3; ++p) rgb_load<TI>(s + (p * plane + o), vec, cnt, c[p]);
 #pragma unroll
             for (int k = 0; k < kTonePx; ++k) {
                 if (x0 + k >= xa && x0 + k < xb) {
-                    const float Y = __fadd_rn(__fadd_rn(__fmul_rn(a.kr, tone_unit(c[0][k])), __fmul_rn(a.kg, tone_unit(c[1][k]))), __fmul_rn(a.kb, tone_unit(c[2][k])));
+                    const float Y = rgb_luma(a.k, rgb_unit(c[0][k]), rgb_unit(c[1][k]), rgb_unit(c[2][k]));
                     const int q = (int)__builtin_amdgcn_fmed3f(rintf(__fmul_rn(Y, 255.f)), 0.f, 255.f);
                     if (q == last) {
                         ++run;
@@ -189,7 +156,7 @@ struct ToneApplyArgs {
     int shared_gains;          // one set of tables for every frame
     int ncmax;                 // tile columns the LDS holds per tile row
     int vec_src, vec_dst;
-    float kr, kg, kb;
+    Luma k;
 };
 
 template <typename TI, typename TO>
@@ -253,11 +220,11 @@ __global__ void __launch_bounds__(kToneThreads) tone_apply_kernel(ToneApplyArgs 
                 const uint32_t o = (uint32_t)y * (uint32_t)a.W + (uint32_t)x0;
                 float c[3][kTonePx], out[3][kTonePx];
 #pragma unroll
-                for (int p = 0; p < 3; ++p) tone_load<TI>(s + (p * splane + o), vin, n, c[p]);
+                for (int p = 0; p < 3; ++p) rgb_load<TI>(s + (p * splane + o), vin, n, c[p]);
 #pragma unroll
                 for (int k = 0; k < kTonePx; ++k) {
-                    const float r = tone_unit(c[0][k]), g = tone_unit(c[1][k]), b = tone_unit(c[2][k]);
-                    const float Y = __fadd_rn(__fadd_rn(__fmul_rn(a.kr, r), __fmul_rn(a.kg, g)), __fmul_rn(a.kb, b));
+                    const float r = rgb_unit(c[0][k]), g = rgb_unit(c[1][k]), b = rgb_unit(c[2][k]);
+                    const float Y = rgb_luma(a.k, r, g, b);
                     const float p = __fmul_rn(Y, 255.f);                           // in [0, 255 + a few ulp], never NaN
                     const int i = min((int)floorf(p), kToneBins - 2);
                     const float f = fminf(__fsub_rn(p, (float)i), 1.f);
@@ -278,15 +245,13 @@ __global__ void __launch_bounds__(kToneThreads) tone_apply_kernel(ToneApplyArgs 
                 }
                 const uint32_t off = (uint32_t)y * (uint32_t)a.w + (uint32_t)x0;
 #pragma unroll
-                for (int p = 0; p < 3; ++p) tone_store<TO>(d + (p * dplane + off), vout, n, out[p]);
+                for (int p = 0; p < 3; ++p) rgb_store<TO>(d + (p * dplane + off), vout, n, out[p]);
             }
         }
         __syncthreads();                                                           // every wave is done with the tables before the next segment's replace them
         ys = ye;
     }
 }
-
-static const double kToneKrKb[3][2] = RC_YUV_KR_KB;
 
 // The refusals the three entries share; the message names the entry.
 static int tone_check_desc(const rc_tone_desc* d, const char* who) {
@@ -301,10 +266,10 @@ static int tone_check_desc(const rc_tone_desc* d, const char* who) {
     return RC_OK;
 }
 
-static int tone_check_frame(const rc_tone_desc* d, int src_dtype, int batch, int H, int W, int h, int w, const char* who) {
+static int tone_check_frame(const rc_tone_desc* d, const void* d_src, int src_dtype, int batch, int H, int W, int h, int w, const char* who, RgbSide* src) {
     const std::string n(who);
-    if (!(src_dtype == RC_F32 || src_dtype == RC_BF16 || src_dtype == RC_F16)) return fail(RC_ERR_INVALID, n + ": bad source dtype");
-    if (!(batch >= 1 && batch <= 65535 && h >= 1 && w >= 1 && h <= H && w <= W)) return fail(RC_ERR_INVALID, n + ": bad shape (empty, more than 65535 frames, or the crop exceeds the source)");
+    if (int e = rgb_source(who, d_src, src_dtype, batch, H, W, h, w, src)) return e;
+    if (!(batch <= 65535)) return fail(RC_ERR_INVALID, n + ": bad shape (more than 65535 frames)");
     if (!((long long)H * W < (1LL << 29))) return fail(RC_ERR_INVALID, n + ": bad shape (a source plane of 2^29 samples or more)");
     if (!(d->grid[0] <= h && d->grid[1] <= w)) return fail(RC_ERR_INVALID, n + ": the grid has more tiles than the frame has rows or columns");
     return RC_OK;
@@ -342,24 +307,24 @@ int rc_tone_axis(int n, int g, int* idx, float* wt) {
 int rc_tone_hist(const void* d_src, int src_dtype, const rc_tone_desc* desc, int* d_hist, int batch, int H, int W, int h, int w, void* stream) {
     RC_REQUIRE(d_src && desc && d_hist, "rc_tone_hist: null pointer");
     if (int e = tone_check_desc(desc, "rc_tone_hist")) return e;
-    if (int e = tone_check_frame(desc, src_dtype, batch, H, W, h, w, "rc_tone_hist")) return e;
-    const size_t es = dtype_size(src_dtype);
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % es == 0 && reinterpret_cast<uintptr_t>(d_hist) % 4 == 0, "rc_tone_hist: misaligned pointer");
+    RgbSide src;
+    if (int e = tone_check_frame(desc, d_src, src_dtype, batch, H, W, h, w, "rc_tone_hist", &src)) return e;
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_hist) % 4 == 0, "rc_tone_hist: misaligned pointer");
 
     ToneHistArgs a;
     a.H = H; a.W = W; a.h = h; a.w = w; a.gy = desc->grid[0]; a.gx = desc->grid[1];
-    a.vec = reinterpret_cast<uintptr_t>(d_src) % (kTonePx * es) == 0 && W % kTonePx == 0;
-    const double kr = kToneKrKb[desc->matrix][0], kb = kToneKrKb[desc->matrix][1];        // as rc_yuv_encode forms them
-    a.kr = (float)kr; a.kb = (float)kb; a.kg = (float)(1.0 - kr - kb);
+    a.vec = src.vec;
+    a.k = rgb_coef(desc->matrix).k;
     const int tiles = a.gy * a.gx, tall = ceil_div(h, a.gy);                              // the tallest tile's rows
     const hipStream_t st = as_stream(stream);
     const size_t words = (size_t)batch * tiles * kToneBins;                               // < 2^32: 65535 frames of 256 tiles
     hipLaunchKernelGGL(tone_zero_kernel, dim3((unsigned)((words + kToneThreads - 1) / kToneThreads)), dim3(kToneThreads), 0, st, reinterpret_cast<unsigned int*>(d_hist), words);
     const dim3 grid((unsigned)ceil_div(tall, kToneHistRows), (unsigned)tiles, (unsigned)batch), block(kToneThreads);
     unsigned int* hist = reinterpret_cast<unsigned int*>(d_hist);
-    if (src_dtype == RC_F32) hipLaunchKernelGGL(tone_hist_kernel<float>, grid, block, 0, st, a, static_cast<const float*>(d_src), hist);
-    else if (src_dtype == RC_BF16) hipLaunchKernelGGL(tone_hist_kernel<bf16_t>, grid, block, 0, st, a, static_cast<const bf16_t*>(d_src), hist);
-    else hipLaunchKernelGGL(tone_hist_kernel<f16_t>, grid, block, 0, st, a, static_cast<const f16_t*>(d_src), hist);
+    by_source(src_dtype, [&](auto ti) {
+        typedef typename decltype(ti)::type TI;
+        hipLaunchKernelGGL(tone_hist_kernel<TI>, grid, block, 0, st, a, static_cast<const TI*>(d_src), hist);
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }
@@ -381,11 +346,11 @@ int rc_tone_apply(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, 
                   const int* d_iy, const float* d_uy, const int* d_ix, const float* d_ux, int batch, int H, int W, int h, int w, void* stream) {
     RC_REQUIRE(d_src && d_dst && desc && d_gains && d_iy && d_uy && d_ix && d_ux, "rc_tone_apply: null pointer");
     if (int e = tone_check_desc(desc, "rc_tone_apply")) return e;
-    if (int e = tone_check_frame(desc, src_dtype, batch, H, W, h, w, "rc_tone_apply")) return e;
-    RC_REQUIRE(dst_dtype == RC_F32 || dst_dtype == src_dtype, "rc_tone_apply: bad output dtype (fp32 or the source's)");
+    RgbSide src, dst;
+    if (int e = tone_check_frame(desc, d_src, src_dtype, batch, H, W, h, w, "rc_tone_apply", &src)) return e;
+    if (int e = rgb_dest("rc_tone_apply", d_dst, dst_dtype, src_dtype, w, &dst)) return e;
     RC_REQUIRE(gains_batch == 1 || gains_batch == batch, "rc_tone_apply: gains_batch must be 1 or batch");
-    const long long ss = (long long)dtype_size(src_dtype), ds = (long long)dtype_size(dst_dtype);
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % ss == 0 && reinterpret_cast<uintptr_t>(d_dst) % ds == 0, "rc_tone_apply: misaligned pointer");
+    const long long ss = (long long)src.esize, ds = (long long)dst.esize;
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_gains) % 16 == 0, "rc_tone_apply: the gains must be 16-byte aligned");
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_iy) % 4 == 0 && reinterpret_cast<uintptr_t>(d_uy) % 4 == 0 && reinterpret_cast<uintptr_t>(d_ix) % 4 == 0 &&
                reinterpret_cast<uintptr_t>(d_ux) % 4 == 0, "rc_tone_apply: misaligned axis table");
@@ -397,19 +362,17 @@ int rc_tone_apply(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, 
     a.H = H; a.W = W; a.h = h; a.w = w; a.gy = desc->grid[0]; a.gx = desc->grid[1];
     a.shared_gains = gains_batch == 1 && batch > 1;
     a.ncmax = std::min(a.gx, ceil_div(kToneSpan, w / a.gx) + 3);                          // w / gx: the narrowest tile, >= 1
-    a.vec_src = s0 % (uintptr_t)(kTonePx * ss) == 0 && W % kTonePx == 0;                  // then every plane and every row starts on a vector
-    a.vec_dst = o0 % (uintptr_t)(kTonePx * ds) == 0 && w % kTonePx == 0;
-    const double kr = kToneKrKb[desc->matrix][0], kb = kToneKrKb[desc->matrix][1];
-    a.kr = (float)kr; a.kb = (float)kb; a.kg = (float)(1.0 - kr - kb);
+    a.vec_src = src.vec; a.vec_dst = dst.vec;
+    a.k = rgb_coef(desc->matrix).k;
     const dim3 grid((unsigned)ceil_div(w, kToneSpan), (unsigned)ceil_div(h, kToneBand), (unsigned)batch), block(kToneThreads);
     RC_REQUIRE(grid.y <= 65535u, "rc_tone_apply: more than 4194240 rows");
     const size_t lds = (size_t)2 * a.ncmax * kToneBins * sizeof(float);                   // at most 32 KiB: below the default limit
     const hipStream_t st = as_stream(stream);
-#define LAUNCH(TI, TO) hipLaunchKernelGGL((tone_apply_kernel<TI, TO>), grid, block, lds, st, a, static_cast<const TI*>(d_src), static_cast<TO*>(d_dst), d_gains, d_iy, d_uy, d_ix, d_ux)
-    if (src_dtype == RC_F32) LAUNCH(float, float);
-    else if (src_dtype == RC_BF16) { if (dst_dtype == RC_F32) LAUNCH(bf16_t, float); else LAUNCH(bf16_t, bf16_t); }
-    else { if (dst_dtype == RC_F32) LAUNCH(f16_t, float); else LAUNCH(f16_t, f16_t); }
-#undef LAUNCH
+    by_source_dest(src_dtype, dst_dtype, [&](auto ti, auto to) {
+        typedef typename decltype(ti)::type TI;
+        typedef typename decltype(to)::type TO;
+        hipLaunchKernelGGL((tone_apply_kernel<TI, TO>), grid, block, lds, st, a, static_cast<const TI*>(d_src), static_cast<TO*>(d_dst), d_gains, d_iy, d_uy, d_ix, d_ux);
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

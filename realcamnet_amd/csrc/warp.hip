@@ -12,13 +12,13 @@
 // Taps are read through L1 / L2 from global memory: no LDS, no scratch.
 // Arithmetic: fp32, every product, sum and difference rounded on its own (__fmul_rn / __fadd_rn / __fsub_rn: no contraction whatever the
 // compile flags say), so the vector path, the element path and a plain elementwise restatement give the same bits.
-#include "common.hpp"
+#include "rgb_strip.hpp"
 
 #include <cmath>
 
 namespace rc {
 
-constexpr int kWarpPx = 4, kWarpStrips = 64, kWarpRows = 4;
+constexpr int kWarpPx = kRgbPx, kWarpStrips = 64, kWarpRows = 4;
 
 struct WarpArgs {
     int H, W, h, w;            // source plane, the frame inside it
@@ -68,21 +68,6 @@ __device__ __forceinline__ void warp_axis(float s, int n, float* wt, int* idx, u
         const int i = first + k;
         idx[k] = min(max(i, 0), n - 1);
         in |= (unsigned)(i == idx[k]) << k;
-    }
-}
-
-template <typename TO>
-__device__ __forceinline__ void warp_store(TO* p, bool vec, int cnt, const float* f) {
-    if (vec) {
-        if constexpr (sizeof(TO) == 4) {
-            *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-        } else {
-            *reinterpret_cast<uint2*>(p) = make_uint2(Vec16<TO>::rne(f[0]) | (Vec16<TO>::rne(f[1]) << 16), Vec16<TO>::rne(f[2]) | (Vec16<TO>::rne(f[3]) << 16));
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kWarpPx; ++k)
-            if (k < cnt) p[k] = from_f32<TO>(f[k]);
     }
 }
 
@@ -172,7 +157,7 @@ __global__ void __launch_bounds__(kWarpStrips * kWarpRows) warp_kernel(WarpArgs 
         }
     }
 #pragma unroll
-    for (int c = 0; c < 3; ++c) warp_store<TO>(d + c * dplane, a.vec_dst && cnt == kWarpPx, cnt, o[c]);
+    for (int c = 0; c < 3; ++c) rgb_store<TO>(d + c * dplane, a.vec_dst && cnt == kWarpPx, cnt, o[c]);
 }
 
 template <typename TI, typename TO>
@@ -198,20 +183,19 @@ extern "C" {
 
 int rc_warp(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, const float* d_mesh, int mesh_batch, int cell_log2, int interp,
             int border, float fill_r, float fill_g, float fill_b, int batch, int H, int W, int h, int w, int oh, int ow, void* stream) {
-    RC_REQUIRE(src_dtype == RC_F32 || src_dtype == RC_BF16 || src_dtype == RC_F16, "rc_warp: bad source dtype");
-    RC_REQUIRE(dst_dtype == RC_F32 || dst_dtype == src_dtype, "rc_warp: bad output dtype (fp32 or the source's)");
     RC_REQUIRE(interp == RC_WARP_BILINEAR || interp == RC_WARP_BICUBIC, "rc_warp: bad interp (bilinear or bicubic)");
     RC_REQUIRE(border == RC_WARP_CLAMP || border == RC_WARP_CONSTANT, "rc_warp: bad border (clamp or constant)");
     RC_REQUIRE(cell_log2 >= RC_WARP_MIN_CELL_LOG2 && cell_log2 <= RC_WARP_MAX_CELL_LOG2, "rc_warp: bad cell (8, 16, 32 or 64: cell_log2 3 .. 6)");
     RC_REQUIRE(std::isfinite(fill_r) && std::isfinite(fill_g) && std::isfinite(fill_b), "rc_warp: the fill must be finite");
     RC_REQUIRE(d_src && d_dst && d_mesh, "rc_warp: null pointer");
-    RC_REQUIRE(batch >= 1 && h >= 1 && w >= 1 && h <= H && w <= W && oh >= 1 && ow >= 1, "rc_warp: bad shape (empty, or the frame exceeds the source)");
+    RgbSide src, dst;
+    if (int e = rgb_source("rc_warp", d_src, src_dtype, batch, H, W, h, w, &src)) return e;
+    if (int e = rgb_dest("rc_warp", d_dst, dst_dtype, src_dtype, ow, &dst)) return e;
+    RC_REQUIRE(oh >= 1 && ow >= 1, "rc_warp: bad shape (an empty output)");
     RC_REQUIRE(H <= RC_WARP_MAX_DIM && W <= RC_WARP_MAX_DIM && oh <= RC_WARP_MAX_DIM && ow <= RC_WARP_MAX_DIM && (long long)H * W < (1LL << 29),
                "rc_warp: bad shape (a dimension above 2^23 or a source plane of 2^29 samples or more)");
     RC_REQUIRE(mesh_batch == 1 || mesh_batch == batch, "rc_warp: mesh_batch must be 1 or the batch");
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_mesh) % 8 == 0, "rc_warp: the mesh must be 8-byte aligned");
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % dtype_size(src_dtype) == 0 && reinterpret_cast<uintptr_t>(d_dst) % dtype_size(dst_dtype) == 0,
-               "rc_warp: misaligned pointer");
     const int cell = 1 << cell_log2;
     WarpArgs a;
     a.H = H; a.W = W; a.h = h; a.w = w; a.oh = oh; a.ow = ow;
@@ -221,13 +205,13 @@ int rc_warp(const void* d_src, int src_dtype, void* d_dst, int dst_dtype, const 
     a.inv_cell = 1.f / (float)cell;
     a.xmax = (float)(w + 1); a.ymax = (float)(h + 1);
     a.fill[0] = fill_r; a.fill[1] = fill_g; a.fill[2] = fill_b;
-    a.vec_dst = reinterpret_cast<uintptr_t>(d_dst) % (kWarpPx * dtype_size(dst_dtype)) == 0 && ow % kWarpPx == 0;     // then every plane and every row starts on a vector
+    a.vec_dst = dst.vec;
     const dim3 grid(ceil_div(ow, kWarpStrips * kWarpPx), ceil_div(oh, kWarpRows), (unsigned)batch);
     RC_REQUIRE(grid.y <= 65535u && grid.z <= 65535u, "rc_warp: more than 65535 frames or 262140 output rows");
     const hipStream_t st = as_stream(stream);
-    if (src_dtype == RC_F32) warp_launch<float, float>(a, interp, border, grid, st, d_src, d_dst, d_mesh);
-    else if (src_dtype == RC_BF16) { if (dst_dtype == RC_F32) warp_launch<bf16_t, float>(a, interp, border, grid, st, d_src, d_dst, d_mesh); else warp_launch<bf16_t, bf16_t>(a, interp, border, grid, st, d_src, d_dst, d_mesh); }
-    else { if (dst_dtype == RC_F32) warp_launch<f16_t, float>(a, interp, border, grid, st, d_src, d_dst, d_mesh); else warp_launch<f16_t, f16_t>(a, interp, border, grid, st, d_src, d_dst, d_mesh); }
+    by_source_dest(src_dtype, dst_dtype, [&](auto ti, auto to) {
+        warp_launch<typename decltype(ti)::type, typename decltype(to)::type>(a, interp, border, grid, st, d_src, d_dst, d_mesh);
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

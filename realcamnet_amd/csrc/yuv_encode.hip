@@ -7,7 +7,7 @@
 // pitch / height padding write it as zero in the same launch.  Arithmetic: fp32, every product and every sum rounded on its own in
 // the order the header states (__fmul_rn / __fadd_rn: no contraction whatever the compile flags say), so the vector path, the
 // element path and a plain elementwise restatement give the same bits.
-#include "common.hpp"
+#include "rgb_strip.hpp"
 
 namespace rc {
 
@@ -24,11 +24,9 @@ struct YuvArgs {
     int vec_src, vec_dst;      // every source row segment / every destination strip is 16-byte aligned
     long long off_c0, off_c1;  // byte offsets of the CbCr (or Cb) plane and of the Cr plane in a frame
     long long frame;           // bytes from one frame to the next
-    float kr, kg, kb, sb, sr;
+    LumaChroma c;
     float ys, yo, ylo, yhi, cs, co, clo, chi;
 };
-
-__device__ __forceinline__ float unit(float v) { return v > 0.f ? (v < 1.f ? v : 1.f) : 0.f; }    // NaN compares false: 0
 
 __device__ __forceinline__ uint32_t code(float v, float s, float o, float lo, float hi) {
     float q = rintf(__fadd_rn(__fmul_rn(v, s), o));             // round half to even
@@ -37,10 +35,10 @@ __device__ __forceinline__ uint32_t code(float v, float s, float o, float lo, fl
 }
 
 __device__ __forceinline__ void ycc(const YuvArgs& a, float r, float g, float b, float& y, float& cb, float& cr) {
-    r = unit(r); g = unit(g); b = unit(b);
-    y = __fadd_rn(__fadd_rn(__fmul_rn(a.kr, r), __fmul_rn(a.kg, g)), __fmul_rn(a.kb, b));
-    cb = __fmul_rn(__fsub_rn(b, y), a.sb);
-    cr = __fmul_rn(__fsub_rn(r, y), a.sr);
+    r = rgb_unit(r); g = rgb_unit(g); b = rgb_unit(b);
+    y = rgb_luma(a.c.k, r, g, b);
+    cb = __fmul_rn(__fsub_rn(b, y), a.c.sb);
+    cr = __fmul_rn(__fsub_rn(r, y), a.c.sr);
 }
 
 // P codes of TO into the four dwords of a strip.
@@ -160,8 +158,6 @@ struct YuvPlan {
     int esize;
 };
 
-static const double kKrKb[3][2] = RC_YUV_KR_KB;
-
 // nullptr, or what is wrong with the format for an (h, w) frame.
 static const char* yuv_plan(const rc_out_format* f, int h, int w, YuvPlan* p) {
     if (!f) return "null format";
@@ -214,26 +210,21 @@ size_t rc_yuv_frame_bytes(const rc_out_format* fmt, int h, int w) {
 
 int rc_yuv_encode(const void* d_src, int src_dtype, const rc_out_format* fmt, void* d_dst, int batch, int H, int W, int h, int w, void* stream) {
     RC_REQUIRE(d_src && fmt && d_dst, "rc_yuv_encode: null pointer");
-    RC_REQUIRE(src_dtype == RC_F32 || src_dtype == RC_BF16 || src_dtype == RC_F16, "rc_yuv_encode: bad dtype");
-    RC_REQUIRE(batch >= 1 && h >= 1 && w >= 1 && h <= H && w <= W, "rc_yuv_encode: bad shape");
+    RgbSide src;
+    if (int e = rgb_source("rc_yuv_encode", d_src, src_dtype, batch, H, W, h, w, &src)) return e;
     YuvPlan p;
     const char* err = yuv_plan(fmt, h, w, &p);
     if (err) return fail(RC_ERR_INVALID, std::string("rc_yuv_encode: ") + err);
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_dst) % 16 == 0, "rc_yuv_encode: dst must be 16-byte aligned");
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % dtype_size(src_dtype) == 0, "rc_yuv_encode: src misaligned");
 
     YuvArgs a;
     a.batch = batch; a.H = H; a.W = W; a.h = h; a.w = w;
     a.pitch = (int)p.pitch; a.rows = (int)p.rows; a.crows = (int)p.crows;
     a.nstrip = (int)((p.pitch + 15) / 16);
     a.off_c0 = p.off_c0; a.off_c1 = p.off_c1; a.frame = p.frame;
-    const size_t es = dtype_size(src_dtype);
-    a.vec_src = reinterpret_cast<uintptr_t>(d_src) % 16 == 0 && ((size_t)W * es) % 16 == 0;       // then every plane and row starts on 16 bytes
+    a.vec_src = reinterpret_cast<uintptr_t>(d_src) % 16 == 0 && ((size_t)W * src.esize) % 16 == 0;        // a strip here is 16 bytes, not 4 pixels: every plane and row starts on 16 bytes
     a.vec_dst = p.pitch % 16 == 0 && p.off_c0 % 16 == 0 && p.off_c1 % 8 == 0 && p.frame % 16 == 0;
-    // Kr, Kb -> Kg, sb, sr in double, rounded to fp32 once
-    const double kr = kKrKb[fmt->matrix][0], kb = kKrKb[fmt->matrix][1];
-    a.kr = (float)kr; a.kb = (float)kb; a.kg = (float)(1.0 - kr - kb);
-    a.sb = (float)(0.5 / (1.0 - kb)); a.sr = (float)(0.5 / (1.0 - kr));
+    a.c = rgb_coef(fmt->matrix);
     const int n = fmt->layout == RC_YUV_P010 ? 10 : 8;
     const float k = (float)(1 << (n - 8)), top = (float)((1 << n) - 1);
     if (fmt->range == RC_RANGE_LIMITED) {
@@ -245,25 +236,14 @@ int rc_yuv_encode(const void* d_src, int src_dtype, const rc_out_format* fmt, vo
     }
     const dim3 grid((a.nstrip + kYuvStrips - 1) / kYuvStrips, (a.crows + kYuvPairs - 1) / kYuvPairs, batch);
     RC_REQUIRE(grid.y <= 65535u && grid.z <= 65535u, "rc_yuv_encode: more than 65535 frames or 524280 rows");
-#define LAUNCH(TI, L, S) \
-    hipLaunchKernelGGL((yuv420_kernel<TI, L, S>), grid, dim3(kYuvStrips, kYuvPairs), 0, as_stream(stream), a, static_cast<const TI*>(d_src), static_cast<uint8_t*>(d_dst))
-#define BY_SITING(TI, L)                                            \
-    do {                                                            \
-        if (fmt->siting == RC_SITING_LEFT) LAUNCH(TI, L, RC_SITING_LEFT); \
-        else LAUNCH(TI, L, RC_SITING_CENTER);                       \
-    } while (0)
-#define BY_LAYOUT(TI)                                               \
-    do {                                                            \
-        if (fmt->layout == RC_YUV_NV12) BY_SITING(TI, RC_YUV_NV12); \
-        else if (fmt->layout == RC_YUV_P010) BY_SITING(TI, RC_YUV_P010); \
-        else BY_SITING(TI, RC_YUV_I420);                            \
-    } while (0)
-    if (src_dtype == RC_F32) BY_LAYOUT(float);
-    else if (src_dtype == RC_BF16) BY_LAYOUT(bf16_t);
-    else BY_LAYOUT(f16_t);
-#undef BY_LAYOUT
-#undef BY_SITING
-#undef LAUNCH
+    by_source(src_dtype, [&](auto ti) {
+        typedef typename decltype(ti)::type TI;
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(kYuvStrips, kYuvPairs), 0, as_stream(stream), a, static_cast<const TI*>(d_src), static_cast<uint8_t*>(d_dst)); };
+        const bool left = fmt->siting == RC_SITING_LEFT;
+        if (fmt->layout == RC_YUV_NV12) launch(left ? yuv420_kernel<TI, RC_YUV_NV12, RC_SITING_LEFT> : yuv420_kernel<TI, RC_YUV_NV12, RC_SITING_CENTER>);
+        else if (fmt->layout == RC_YUV_P010) launch(left ? yuv420_kernel<TI, RC_YUV_P010, RC_SITING_LEFT> : yuv420_kernel<TI, RC_YUV_P010, RC_SITING_CENTER>);
+        else launch(left ? yuv420_kernel<TI, RC_YUV_I420, RC_SITING_LEFT> : yuv420_kernel<TI, RC_YUV_I420, RC_SITING_CENTER>);
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

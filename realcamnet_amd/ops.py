@@ -697,17 +697,28 @@ def raw_temporal(mosaic: torch.Tensor, raw_format, prev: Optional[torch.Tensor] 
     return out
 
 
+def _planar_source(y, what, crop_hw, out_dtype=None, crop=True, frames=True):
+    """The checks every op on the planar result (B,3,H,W) shares: (y contiguous on the GPU, h, w).  out_dtype, where the op has one, is
+    fp32 or y's.  crop=False leaves the crop's bounds to the library, frames=False an empty batch."""
+    y = _req(y, f"{what} input")
+    if y.dim() != 4 or y.shape[1] != 3:
+        raise ValueError(f"{what}: expected (B,3,H,W), got {tuple(y.shape)}")
+    _dt(y)
+    if out_dtype is not None and out_dtype not in (torch.float32, y.dtype):
+        raise ValueError(f"{what}: out_dtype must be torch.float32 or the source's {y.dtype}, got {out_dtype}")
+    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
+    if crop and ((frames and y.shape[0] < 1) or h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]):
+        raise ValueError(f"{what}: crop {(h, w)} of the source {tuple(y.shape)} is empty or exceeds it")
+    return y, h, w
+
+
 def rgb_encode(y: torch.Tensor, bits: int, crop_hw: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """Planar float result (B,3,H,W) -> interleaved (B,h,w,3) uint8 (bits 8) or uint16 (bits 16), cropped to crop_hw:
     clamp(rint(float(y) * S), 0, S) with S = 2**bits - 1, round half to even, NaN -> 0 (rc_rgb_encode)."""
-    y = _req(y, "rgb_encode input")
+    y, h, w = _planar_source(y, "rgb_encode", crop_hw, crop=False)
     if bits not in (8, 16):
         raise ValueError(f"rgb_encode: bits must be 8 or 16, got {bits!r}")
-    if y.dim() != 4 or y.shape[1] != 3:
-        raise ValueError(f"rgb_encode: expected (B,3,H,W), got {tuple(y.shape)}")
-    _dt(y)
-    h, w = crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])
-    return _R.rgb_encode(y, int(bits), int(h), int(w))
+    return _R.rgb_encode(y, int(bits), h, w)
 
 
 def yuv_encode(y: torch.Tensor, fmt, crop_hw: Optional[Tuple[int, int]] = None):
@@ -717,13 +728,7 @@ def yuv_encode(y: torch.Tensor, fmt, crop_hw: Optional[Tuple[int, int]] = None):
     from .out_format import LAYOUTS, MATRICES, RANGES, SITINGS, OutFormat, YuvFrames
     if not isinstance(fmt, OutFormat):
         raise TypeError(f"yuv_encode: fmt must be an OutFormat, got {type(fmt).__name__}")
-    y = _req(y, "yuv_encode input")
-    if y.dim() != 4 or y.shape[1] != 3:
-        raise ValueError(f"yuv_encode: expected (B,3,H,W), got {tuple(y.shape)}")
-    _dt(y)
-    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
-    if h > y.shape[2] or w > y.shape[3]:
-        raise ValueError(f"yuv_encode: crop {(h, w)} exceeds the source {tuple(y.shape[2:])}")
+    y, h, w = _planar_source(y, "yuv_encode", crop_hw, frames=False)
     pl = fmt.plane_layout(h, w)
     buf = _R.yuv_encode(y, LAYOUTS[fmt.layout], MATRICES[fmt.matrix], RANGES[fmt.range], SITINGS[fmt.chroma_siting], pl.pitch,
                         pl.planes[0].alloc_rows, h, w)
@@ -756,15 +761,7 @@ def resize(y: torch.Tensor, rs, crop_hw: Optional[Tuple[int, int]] = None, out_d
     from .resize import MAX_TAPS, Resize
     if not isinstance(rs, Resize):
         raise TypeError(f"resize: rs must be a Resize, got {type(rs).__name__}")
-    y = _req(y, "resize input")
-    if y.dim() != 4 or y.shape[1] != 3:
-        raise ValueError(f"resize: expected (B,3,H,W), got {tuple(y.shape)}")
-    _dt(y)
-    if out_dtype not in (torch.float32, y.dtype):
-        raise ValueError(f"resize: out_dtype must be torch.float32 or the source's {y.dtype}, got {out_dtype}")
-    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
-    if h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]:
-        raise ValueError(f"resize: crop {(h, w)} exceeds the source {tuple(y.shape[2:])}")
+    y, h, w = _planar_source(y, "resize", crop_hw, out_dtype, frames=False)
     rs.window(h, w)
     if isinstance(y, FakeTensor):                              # a trace: shapes only, nothing is built, copied or kept
         tables = (y.new_empty((rs.size[0],), dtype=torch.int32), y.new_empty((rs.size[0], MAX_TAPS), dtype=torch.float32),
@@ -795,15 +792,7 @@ def lut3d(y: torch.Tensor, lut, crop_hw: Optional[Tuple[int, int]] = None, out_d
     from .look import Lut3D
     if not isinstance(lut, Lut3D):
         raise TypeError(f"lut3d: lut must be a Lut3D, got {type(lut).__name__}")
-    y = _req(y, "lut3d input")
-    if y.dim() != 4 or y.shape[1] != 3:
-        raise ValueError(f"lut3d: expected (B,3,H,W), got {tuple(y.shape)}")
-    _dt(y)
-    if out_dtype not in (torch.float32, y.dtype):
-        raise ValueError(f"lut3d: out_dtype must be torch.float32 or the source's {y.dtype}, got {out_dtype}")
-    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
-    if y.shape[0] < 1 or h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]:
-        raise ValueError(f"lut3d: crop {(h, w)} of the source {tuple(y.shape)} is empty or exceeds it")
+    y, h, w = _planar_source(y, "lut3d", crop_hw, out_dtype)
     if isinstance(y, FakeTensor):                              # a trace: shapes only, nothing is built, copied or kept
         table = y.new_empty((lut.size ** 3, 4), dtype=torch.float32)
     else:
@@ -818,15 +807,7 @@ def sharpen(y: torch.Tensor, sharpen, crop_hw: Optional[Tuple[int, int]] = None,
     from .sharpen import Sharpen
     if not isinstance(sharpen, Sharpen):
         raise TypeError(f"sharpen: sharpen must be a Sharpen, got {type(sharpen).__name__}")
-    y = _req(y, "sharpen input")
-    if y.dim() != 4 or y.shape[1] != 3:
-        raise ValueError(f"sharpen: expected (B,3,H,W), got {tuple(y.shape)}")
-    _dt(y)
-    if out_dtype not in (torch.float32, y.dtype):
-        raise ValueError(f"sharpen: out_dtype must be torch.float32 or the source's {y.dtype}, got {out_dtype}")
-    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
-    if y.shape[0] < 1 or h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]:
-        raise ValueError(f"sharpen: crop {(h, w)} of the source {tuple(y.shape)} is empty or exceeds it")
+    y, h, w = _planar_source(y, "sharpen", crop_hw, out_dtype)
     return _R.sharpen(y, sharpen.radius, sharpen.matrix_code, sharpen.amount, sharpen.core, sharpen.overshoot, h, w, out_dtype)
 
 
@@ -846,18 +827,12 @@ def tone_axis_tables(n: int, g: int, device):
     return derived(_TONE_TABLES, ("tone_axis",) + key, (), lambda: tuple(torch.from_numpy(a).to(device) for a in axis(int(n), int(g))))
 
 
-def _tone_source(y, tm, crop_hw, what):
+def _tone_source(y, tm, crop_hw, what, out_dtype=None):
     """The checks the tone ops share: (y contiguous on the GPU, h, w)."""
     from .tone import ToneMap
     if not isinstance(tm, ToneMap):
         raise TypeError(f"{what}: tm must be a ToneMap, got {type(tm).__name__}")
-    y = _req(y, f"{what} input")
-    if y.dim() != 4 or y.shape[1] != 3:
-        raise ValueError(f"{what}: expected (B,3,H,W), got {tuple(y.shape)}")
-    _dt(y)
-    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
-    if y.shape[0] < 1 or h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]:
-        raise ValueError(f"{what}: crop {(h, w)} of the source {tuple(y.shape)} is empty or exceeds it")
+    y, h, w = _planar_source(y, what, crop_hw, out_dtype)
     if y.shape[2] * y.shape[3] >= 1 << 29:
         raise ValueError(f"{what}: a source plane of {tuple(y.shape[2:])} has 2^29 samples or more")
     tm.check(h, w)
@@ -895,9 +870,7 @@ def tone_apply(y: torch.Tensor, gains: torch.Tensor, tm, crop_hw: Optional[Tuple
     the gain that its luma finds in the tables of the four nearest tile centres, bilinearly interpolated (rc_tone_apply).  out_dtype:
     torch.float32, or y's dtype (rounded to nearest even once).  One launch; the gains are read when the kernel runs."""
     from .tone import BINS
-    y, h, w = _tone_source(y, tm, crop_hw, "tone_apply")
-    if out_dtype not in (torch.float32, y.dtype):
-        raise ValueError(f"tone_apply: out_dtype must be torch.float32 or the source's {y.dtype}, got {out_dtype}")
+    y, h, w = _tone_source(y, tm, crop_hw, "tone_apply", out_dtype)
     if (not isinstance(gains, torch.Tensor) or gains.dtype != torch.float32 or gains.device != y.device or gains.dim() != 4
             or gains.shape[0] not in (1, y.shape[0]) or tuple(gains.shape[1:]) != (*tm.grid, BINS)):
         raise ValueError(f"tone_apply: the gains must be a float32 tensor (1 or {y.shape[0]}, {tm.grid[0]}, {tm.grid[1]}, {BINS}) on {y.device}")
@@ -942,15 +915,7 @@ def warp(y: torch.Tensor, warp_or_mesh, size: Optional[Tuple[int, int]] = None, 
     mesh per frame: stabilisation), used in place, with `size` = (oh, ow) required.  A mesh tensor's nodes need not be finite: the kernel
     guards every coordinate and every index."""
     from .warp import BORDERS, INTERPS, Warp, _cell, _hw, mesh_shape
-    y = _req(y, "warp input")
-    if y.dim() != 4 or y.shape[1] != 3:
-        raise ValueError(f"warp: expected (B,3,H,W), got {tuple(y.shape)}")
-    _dt(y)
-    if out_dtype not in (torch.float32, y.dtype):
-        raise ValueError(f"warp: out_dtype must be torch.float32 or the source's {y.dtype}, got {out_dtype}")
-    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
-    if y.shape[0] < 1 or h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]:
-        raise ValueError(f"warp: crop {(h, w)} of the source {tuple(y.shape)} is empty or exceeds it")
+    y, h, w = _planar_source(y, "warp", crop_hw, out_dtype)
     if isinstance(warp_or_mesh, Warp):
         wp = warp_or_mesh
         if size is not None:
@@ -992,13 +957,7 @@ def frame_stats(y: torch.Tensor, stats, crop_hw: Optional[Tuple[int, int]] = Non
     from .stats import FrameStats, Stats
     if not isinstance(stats, Stats):
         raise TypeError(f"frame_stats: stats must be a Stats, got {type(stats).__name__}")
-    y = _req(y, "frame_stats input")
-    if y.dim() != 4 or y.shape[1] != 3:
-        raise ValueError(f"frame_stats: expected (B,3,H,W), got {tuple(y.shape)}")
-    _dt(y)
-    h, w = (int(v) for v in (crop_hw if crop_hw is not None else (y.shape[2], y.shape[3])))
-    if y.shape[0] < 1 or h < 1 or w < 1 or h > y.shape[2] or w > y.shape[3]:
-        raise ValueError(f"frame_stats: crop {(h, w)} of the source {tuple(y.shape)} is empty or exceeds it")
+    y, h, w = _planar_source(y, "frame_stats", crop_hw)
     if y.shape[2] * y.shape[3] >= 1 << 29:
         raise ValueError(f"frame_stats: a source plane of {tuple(y.shape[2:])} has 2^29 samples or more")
     roi = stats.check(h, w)
