@@ -609,6 +609,55 @@ size_t rc_temporal_desc_size(void);
 int rc_raw_temporal(const void* d_src, const rc_raw_format* fmt, const rc_temporal_desc* desc, const float* d_prev, int prev_pitch_bytes,
                     const float* d_gain, int gain_batch, void* d_dst, int dst_pitch_bytes, int batch, int h, int w, void* stream);
 
+/* ---- Quad-Bayer (tetracell) sensors (ABI 15, additive): the new first box of the input side, in front of the defects stage.  Each colour of
+ * the Bayer cell covers a 2x2 block of photosites, so the pattern repeats every 4x4; what leaves the stage is an ordinary Bayer mosaic with
+ * the same cfa and the same levels.
+ * Replaces: unpacking the RAW10 / RAW12 lines into a tensor and a dozen gather / select passes over fp32 copies of it.  Here one launch over
+ * the bytes as delivered. */
+#define RC_QUAD_REMOSAIC 0        /* rc_quad_desc.mode: the full-resolution quad mosaic -> a Bayer mosaic of the same size */
+#define RC_QUAD_BIN 1             /* ... -> the 2x2 same-colour binned Bayer mosaic at half size */
+typedef struct rc_quad_desc {
+    int mode;              /* RC_QUAD_REMOSAIC or RC_QUAD_BIN */
+    int reserved[3];       /* zero */
+} rc_quad_desc;
+size_t rc_quad_desc_size(void);
+
+/* src: B frames (H, W) as rc_raw_defects reads them (fmt: storage, line_bytes, width = 0 or W; cfa is checked and names the colours of the
+ * four 2x2 blocks of the 4x4 tile; black and white are not looked at).  H and W are the frame's rows and columns (not halves), multiples
+ * of 4.  Sensor sample (y,x) has colour cfa[2 ((y>>1)&1) + ((x>>1)&1)]; the result has colour cfa[2 (y&1) + (x&1)] at (y,x).  The two G
+ * of the cell are one colour.
+ * d_dst, rows dst_pitch_bytes apart (0: dense):
+ *   REMOSAIC  (B, H, W), frames H rows apart: uint16 for RC_RAW_U16 / U8 / MIPI10 / MIPI12, the source type for RC_RAW_F32 / BF16 / F16.
+ *   BIN       (B, H/2, W/2) fp32 for every storage, frames H/2 rows apart.
+ *
+ * v(y,x) is the decoded sample as fp32 (counts are exact).  Every sum, difference and quotient is rounded to fp32 on its own (no fused
+ * multiply-add); /3 is one correctly rounded fp32 division.  A coordinate outside the frame reflects so that the colour is kept:
+ * y' = 1 - y for y < 0, y' = 2H - 3 - y for y >= H, the same in x (the stencil reaches 2 samples: one reflection suffices).
+ * REMOSAIC, with T the wanted colour at (y,x), S the sensor's colour there, sy = +1 for odd y and -1 for even y, sx alike from x:
+ *   1. S = T (6 of the 16 sites of a tile): out = v(y,x), unchanged.
+ *   2. along a row or a column the colours come in pairs (A A B B ..).  If T occurs on that line its nearest samples to the two sides are
+ *      near = the sample at distance 1 (x + sx, or y + sy) and far = the one at distance 2 on the other side (x - 2 sx, or y - 2 sy).
+ *      The axis estimate is e = near + (far - near) / 3, the axis gradient d = |far - near|.
+ *   3. T on both axes (G wanted at an R or B site): d_H < d_V: out = e_H;  d_V < d_H: out = e_V;  equal: out = (e_H + e_V) 0.5.
+ *   4. T on one axis only (R or B wanted at a G site): out = that axis' e.
+ *   5. T on neither axis (R wanted at a B site, or B at an R site): the diagonal neighbour (y + sy, x + sx) has colour T, and so have
+ *      (y + sy, x - 2 sx), (y - 2 sy, x + sx), (y - 2 sy, x - 2 sx).  Per row:
+ *        r_near = v(y+sy, x+sx) + (v(y+sy, x-2sx) - v(y+sy, x+sx)) / 3;   r_far the same on row y - 2 sy;
+ *      then out = r_near + (r_far - r_near) / 3.
+ *   6. count storages store rint(out), half to even, as uint16; float storages round to nearest even to the source type.  A kept sample
+ *      keeps its exact value.
+ * BIN:  out(y,x) = ((v(2y,2x) + v(2y,2x+1)) + (v(2y+1,2x) + v(2y+1,2x+1))) 0.25, stored as fp32 (the mean of four counts is exact).
+ * Hence, exactly: per-colour flat fields come out unchanged; a plane affine in x and y with integer slopes comes out as the true Bayer
+ * sampling wherever the stencil does not reflect (2 samples from every border).
+ * Single pass over source samples only: the result does not depend on the traversal order and is the same from run to run.  No atomics, no
+ * device state, one launch, capturable.  Frames holding NaN / Inf are outside this contract (no fault, any value).
+ * Null d_src / fmt / desc / d_dst, an unknown storage or cfa, line_bytes shorter than a row or no multiple of the sample size, fmt->width
+ * other than 0 or W, a source misaligned for its sample (MIPI: 4 bytes), a dst pitch shorter than a row or no multiple of the sample size,
+ * dst misaligned, H or W below 4 or no multiple of 4, an unknown mode, non-zero reserved (fmt's too), more than 65535 frames:
+ * RC_ERR_INVALID before anything is enqueued. */
+int rc_raw_quad(const void* d_src, const rc_raw_format* fmt, const rc_quad_desc* desc, void* d_dst, int dst_pitch_bytes,
+                int batch, int H, int W, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

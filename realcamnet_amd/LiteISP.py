@@ -257,6 +257,23 @@ class Color_Condition_GFM_LFM(nn.Module):
         return vec.to(global_raw.dtype).view(vec.shape[0], vec.shape[1], 1, 1), ops.to_nchw(lfm)
 
 
+def _quad(mosaic, raw_format):
+    """raw_format.quad (a QuadBayer): the sensor is Quad-Bayer.  ops.raw_quad (one launch) turns the frame -- every exposure of it, with
+    Exposures(layout="frames"): (B,E,...) viewed as (B E,...) -- into an ordinary Bayer mosaic of the same cfa and levels: remosaiced at full
+    size, or binned to half size (fp32).  Returns that mosaic and the format that describes it; every later stage reads it as it would a
+    Bayer sensor's frame."""
+    import dataclasses
+    h2, w2 = raw_format.validate(mosaic.shape)                # every refusal, before any launch; the size of what leaves the stage
+    one = dataclasses.replace(raw_format, exposures=None, defects=None, temporal=None, calibration=None)
+    if raw_format.exposures is not None:                      # layout "frames": validate refuses "lines"
+        b, e = mosaic.shape[0], mosaic.shape[1]
+        out = ops.raw_quad(mosaic.reshape((b * e,) + tuple(mosaic.shape[2:])), one).view(b, e, h2, w2)
+    else:
+        out = ops.raw_quad(mosaic, one)
+    storage = "float" if raw_format.quad.mode == "bin" or raw_format.storage == "float" else "u16"
+    return out, dataclasses.replace(raw_format, quad=None, storage=storage, width=None)
+
+
 def _merge_exposures(net, mosaic, raw_format):
     """raw_format.exposures (an Exposures): the tensor holds E exposures of each frame.  The defects stage, when asked for, runs on every
     exposure (layout "frames": (B,E,...) viewed as (B E,...); net.defect_counts is then (B,E,3)); ops.raw_hdr_merge (one launch) fuses them
@@ -322,11 +339,15 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
     raw_format.exposures (an Exposures): the tensor holds E exposures of each frame; they are repaired one by one and merged first
     (_merge_exposures), and the calibration and the ingest then read the merged fp32 mosaic with the same levels.
     raw_format.temporal (a Temporal): the repaired / merged frame is filtered against the last call's result (_temporal) in front of the
-    calibration.  The order is merge (with its per-exposure repair), repair, temporal, calibration, ingest.
+    calibration.
+    raw_format.quad (a QuadBayer): a Quad-Bayer sensor's frame is remosaiced or binned to a Bayer mosaic first (_quad), and everything
+    else reads that.  The order is quad, merge (with its per-exposure repair), repair, temporal, calibration, ingest.
     A cond the caller supplies is used as it is: it is NOT corrected and NOT calibrated."""
     need_cond = hasattr(net, "classifier") and cond is None and not getattr(net, "cond_from_raw", False)
     if raw_format is not None and raw_format.temporal is not None:
         _temporal_check(raw_format)
+    if raw_format is not None and raw_format.quad is not None:
+        mosaic, raw_format = _quad(mosaic, raw_format)
     if raw_format is not None and raw_format.exposures is not None:
         mosaic, raw_format = _merge_exposures(net, mosaic, raw_format)
     if raw_format is not None and raw_format.defects is not None:

@@ -36,6 +36,7 @@ RC_DEFECT_HOT, RC_DEFECT_COLD = 1, 2
 RC_CALIB_GAINS, RC_CALIB_CLIP, RC_CALIB_MAX_KNOTS = 1, 2, 16
 RC_HDR_MOTION = 1
 RC_TNR_RESET, RC_TNR_GAIN = 1, 2
+RC_QUAD_REMOSAIC, RC_QUAD_BIN = 0, 1
 
 
 class ConvDesc(C.Structure):
@@ -141,6 +142,11 @@ class TemporalDesc(C.Structure):
     ]
 
 
+class QuadDesc(C.Structure):
+    """Mirror of `struct rc_quad_desc`."""
+    _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 def declared_symbols() -> list[str]:
     """Every function the public header declares (used by the CPU-side ABI test)."""
     text = HEADER.read_text()
@@ -183,6 +189,8 @@ _SIGS = {
     "rc_raw_hdr_merge": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(HdrDesc), _P, _I, _P, _I, _I, _I, _I, _P]),
     "rc_temporal_desc_size": (_SZ, []),
     "rc_raw_temporal": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(TemporalDesc), _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
+    "rc_quad_desc_size": (_SZ, []),
+    "rc_raw_quad": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(QuadDesc), _P, _I, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

@@ -470,16 +470,19 @@ _RAW_TENSOR_DTYPE = {"u16": torch.uint16, "u8": torch.uint8, "mipi10": torch.uin
 _RAW_STORAGE = {"u16": _lib.RC_RAW_U16, "u8": _lib.RC_RAW_U8, "mipi10": _lib.RC_RAW_MIPI10, "mipi12": _lib.RC_RAW_MIPI12}
 
 
-def _raw_source(mosaic, raw_format, who):
+def _raw_source(mosaic, raw_format, who, quad=False):
     """The sensor frame the mosaic front-end ops read (raw_ingest(raw_format=), raw_defects, raw_calibrate, raw_hdr_merge): checks `mosaic` against
     `raw_format` (a RawFormat) and returns the frame as a contiguous (B, 2h, X) tensor on the device -- with raw_format.exposures set,
     (B, E, 2h, X) or (B, E 2h, X) as its layout says -- its rc_raw_storage and (2h, 2w) of one exposure.  `who` opens the message that names
-    the op."""
+    the op.  Only raw_quad (`quad`) reads a Quad-Bayer frame; (2h, 2w) is then the size of its result."""
     from .raw_format import RawFormat
     if not isinstance(raw_format, RawFormat):
         raise TypeError(f"{who}raw_format must be a RawFormat, got {type(raw_format).__name__}")
     if not isinstance(mosaic, torch.Tensor):
         raise TypeError("mosaic: expected a tensor")
+    if raw_format.quad is not None and not quad:
+        raise ValueError(f"{who}the frame is Quad-Bayer (raw_format.quad is set) and this op reads a Bayer mosaic: run ops.raw_quad first and "
+                         "hand its result on with quad=None (forward_mosaic does both)")
     hw = raw_format.validate(mosaic.shape)
     want = _RAW_TENSOR_DTYPE.get(raw_format.storage)
     if want is None:
@@ -529,6 +532,31 @@ def _raw_ingest_fmt(mosaic, dtype, pad_to, black_level, white_level, cond_hw, fm
     _DT[dtype]
     return _R.raw_ingest_fmt(mosaic, dtype, int(pad_to), storage, CFAS[fmt.cfa], int(w2), list(fmt.blacks()), float(fmt.white_level),
                              int(cond_hw[0]), int(cond_hw[1]))
+
+
+def raw_quad(mosaic: torch.Tensor, raw_format, quad=None) -> torch.Tensor:
+    """A Quad-Bayer (tetracell) frame -> an ordinary Bayer mosaic, in front of every other stage (rc_raw_quad; the arithmetic is fixed in
+    include/realcam_hip.h): a sensor frame (B,[1,]H,X) as `raw_format` (a RawFormat) describes it, whose cfa names the colours of the four
+    2x2 blocks of the 4x4 tile -> the mosaic with that cfa, unpacked and dense.  `quad` (a QuadBayer; default: raw_format.quad) names the
+    mode: "remosaic" -> (B,H,W), uint16 for the u16 / u8 / mipi10 / mipi12 storages, the frame's own dtype for float; "bin" -> (B,H/2,W/2)
+    fp32.  H and W must be multiples of 4.  One launch, no device state, nothing is synchronised: capturable.  The format's later stages
+    (defects, temporal, calibration) are not looked at; with exposures set, pass the (B E, H, X) view of whole frames and a format without
+    them.  Frames holding NaN / Inf are outside the contract."""
+    import dataclasses
+    from .quad import QuadBayer
+    from .raw_format import CFAS, RawFormat
+    if not isinstance(raw_format, RawFormat):
+        raise TypeError(f"raw_quad: raw_format must be a RawFormat, got {type(raw_format).__name__}")
+    if raw_format.exposures is not None:
+        raise ValueError("raw_quad reads one exposure: pass Exposures(layout='frames') frames as their (B E, H, X) view, with exposures=None "
+                         "(forward_mosaic does)")
+    quad = raw_format.quad if quad is None else quad
+    if not isinstance(quad, QuadBayer):
+        raise ValueError(f"raw_quad: quad must be a QuadBayer (or raw_format.quad set), got {type(quad).__name__}")
+    fmt = dataclasses.replace(raw_format, quad=quad, defects=None, temporal=None, calibration=None)
+    mosaic, storage, _ = _raw_source(mosaic, fmt, "raw_quad: ", quad=True)
+    width = fmt.width if fmt.packed else mosaic.shape[-1]
+    return _R.raw_quad(mosaic, storage, CFAS[fmt.cfa], int(width), quad.code)
 
 
 def raw_defects(mosaic: torch.Tensor, raw_format, defects=None):

@@ -40,6 +40,13 @@ class RawFormat:
                  frame, which its TemporalState carries from call to call (the B frames of a call are B streams).  The noise model is in
                  this storage's own code units and uses these black levels; a calibration must not carry a curve (the noise model needs
                  linear samples).
+    quad         None, or a QuadBayer: the sensor is Quad-Bayer (tetracell) -- `cfa` then names the colours of the four 2x2 blocks of the 4x4
+                 tile (sample (y,x) has colour cfa[2 ((y>>1)&1) + ((x>>1)&1)]) and forward_mosaic first turns the frame into an ordinary
+                 Bayer mosaic with this cfa and these levels (ops.raw_quad, one launch: mode "remosaic" at full size, "bin" at half size),
+                 in front of every other stage -- per exposure with Exposures(layout="frames").  Height and width must be multiples of
+                 4; validate then returns the size of what leaves the stage, and the other stages are checked against it.  It takes no
+                 Exposures(layout="lines") (de-interleave first) and no Defects.map (the map addresses photosites that the stage mixes
+                 or merges; hot / cold thresholds are fine).
     calibration  None, or a Calibration: forward_mosaic then runs ops.raw_calibrate (a linearisation curve, these levels, a flat-field gain
                  map, white-balance gains, a clip) after the defects stage and ingests its fp32 result.  With a curve, black_level and
                  white_level are in the curve's linear units.  A gain map must have the node count the mosaic needs.
@@ -50,6 +57,7 @@ class RawFormat:
     width: Optional[int] = None
     black_level: Union[float, Tuple[float, float, float, float]] = 0.0
     white_level: float = 1.0
+    quad: Optional[object] = None
     temporal: Optional[object] = None
     exposures: Optional[object] = None
     defects: Optional[object] = None
@@ -94,6 +102,9 @@ class RawFormat:
             if self.defects is not None:
                 raise ValueError("Exposures(layout='lines') takes no defects: the defects stage reads whole frames -- de-interleave the lines "
                                  "into (B,E,2h,X) first")
+            if self.quad is not None:
+                raise ValueError("Exposures(layout='lines') takes no quad: the quad stage reads whole frames -- de-interleave the lines "
+                                 "into (B,E,H,X) first")
         if self.calibration is not None and getattr(self.calibration, "curve", None) is not None:
             raise ValueError("a Calibration.curve cannot follow exposures: the merge needs linear samples -- linearise each exposure first")
         return one
@@ -101,7 +112,8 @@ class RawFormat:
     def validate(self, mosaic_shape: Sequence[int]) -> Tuple[int, int]:
         """Check this format against a mosaic tensor's shape (B,[1,]2h,X); returns the mosaic size (2h, 2w).  X is 2w for the sample
         storages and the line stride in bytes for the MIPI ones.  With exposures set the tensor is (B,E,2h,X) or (B,[1,]E 2h,X) (its layout)
-        and the size returned is that of one exposure.  Raises ValueError."""
+        and the size returned is that of one exposure.  With quad set the size returned is that of the Bayer mosaic the quad stage hands on:
+        (H, W), or (H/2, W/2) for mode "bin".  Raises ValueError."""
         if self.cfa not in CFAS:
             raise ValueError(f"RawFormat.cfa must be one of {sorted(CFAS)}, got {self.cfa!r}")
         if self.storage not in STORAGES:
@@ -136,6 +148,14 @@ class RawFormat:
             raise ValueError(f"RAW10 packs 4 samples in 5 bytes: the mosaic width must be a multiple of 4, got {w2}")
         if self.packed and x < self.min_line_bytes(w2):
             raise ValueError(f"{self.storage} line of {w2} samples needs {self.min_line_bytes(w2)} bytes, the tensor's lines have {x}")
+        if self.quad is not None:
+            from .quad import QuadBayer
+            if not isinstance(self.quad, QuadBayer):
+                raise ValueError(f"RawFormat.quad must be None or a QuadBayer, got {type(self.quad).__name__}")
+            if getattr(self.defects, "map", None) is not None:
+                raise ValueError("a Defects.map cannot follow quad: the map addresses photosites that the remosaic has mixed or the binning "
+                                 "has merged -- use the dynamic hot / cold tests, which run on the Bayer result")
+            h2, w2 = self.quad.out_size(h2, w2)                # from here on: the Bayer mosaic that leaves the quad stage
         if self.exposures is not None:
             self.exposures.check(h2, w2, shape[0])
         if self.defects is not None:

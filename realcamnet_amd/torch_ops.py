@@ -400,6 +400,24 @@ def _temporal_launch(ret, src, prev, gain, out, storage, cfa, width, black, para
 define("raw_temporal(Tensor src, Tensor? prev, Tensor? gain, Tensor(a!) out, int storage, int cfa, int width, float[] black, float[] params, "
        "float[] host_gain) -> Tensor", lambda src, prev, gain, out, storage, cfa, width, black, params, host_gain: out.new_empty((0,)), _temporal_launch)
 
+def _quad_alloc(src, storage, cfa, width, mode):
+    b, h, _ = src.shape
+    if mode == _lib.RC_QUAD_BIN:
+        return src.new_empty((b, h // 2, width // 2), dtype=torch.float32)
+    return src.new_empty((b, h, width), dtype=torch.uint16 if storage in _DEFECT_COUNT_STORAGES else src.dtype)
+
+
+def _quad_launch(out, src, storage, cfa, width, mode):
+    b, h, _ = src.shape
+    src, f = _raw_source(src, storage, cfa, width, (0.0,) * 4, 0.0)
+    d = _lib.QuadDesc(mode=mode)
+    check(lib().rc_raw_quad(src.data_ptr(), C.byref(f), C.byref(d), out.data_ptr(), 0, b, h, width, _stream()), "rc_raw_quad")
+
+
+# src (B, H, X) as raw_ingest_fmt takes it, a Quad-Bayer frame whose 2x2 blocks have the colours `cfa` names; mode: RC_QUAD_REMOSAIC -> the Bayer
+# mosaic (B, H, W) (uint16 for the count storages, src's dtype for float), RC_QUAD_BIN -> the binned Bayer mosaic (B, H/2, W/2) fp32
+define("raw_quad(Tensor src, int storage, int cfa, int width, int mode) -> Tensor", _quad_alloc, _quad_launch)
+
 define("nchw_to_nhwc(Tensor x, ScalarType dtype, int hp, int wp) -> Tensor",
        lambda x, dtype, hp, wp: x.new_empty((x.shape[0], hp, wp, x.shape[1]), dtype=dtype),
        lambda out, x, dtype, hp, wp: check(lib().rc_nchw_to_nhwc(x.data_ptr(), _dt(x), out.data_ptr(), _DT[dtype], x.shape[0], x.shape[1],
