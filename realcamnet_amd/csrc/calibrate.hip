@@ -158,12 +158,12 @@ size_t rc_calib_desc_size(void) { return sizeof(rc_calib_desc); }
 int rc_raw_calibrate(const void* d_src, const rc_raw_format* fmt, const rc_calib_desc* desc, const float* d_gain_map, const float* d_frame_gains,
                      int frame_gains_batch, void* d_dst, int dst_dtype, int dst_pitch_bytes, int batch, int h, int w, void* stream) {
     RC_REQUIRE(d_src && fmt && desc && d_dst, "rc_raw_calibrate: null pointer");
-    RC_REQUIRE(batch >= 1 && batch <= 65535 && h >= 1 && w >= 1 && h <= (1 << 20) && w <= (1 << 24), "rc_raw_calibrate: bad shape (empty, more than 65535 frames, or too large)");
+    if (const int e = raw_frames("rc_raw_calibrate", batch, h, w)) return e;
     RawSource rs;
     if (const int e = raw_source("rc_raw_calibrate", d_src, fmt, w, &rs)) return e;
     const long long lb = rs.line_bytes;
     RC_REQUIRE(dst_dtype == RC_F32 || dst_dtype == RC_BF16 || dst_dtype == RC_F16, "rc_raw_calibrate: dst dtype must be RC_F32, RC_BF16 or RC_F16");
-    RC_REQUIRE(desc->reserved[0] == 0 && desc->reserved[1] == 0 && desc->reserved[2] == 0, "rc_raw_calibrate: reserved fields must be zero");
+    RC_REQUIRE(all_zero(desc->reserved), "rc_raw_calibrate: reserved fields must be zero");
     RC_REQUIRE((desc->flags & ~(RC_CALIB_GAINS | RC_CALIB_CLIP)) == 0, "rc_raw_calibrate: unknown flags");
     for (int p = 0; p < 4; ++p)
         RC_REQUIRE(std::isfinite(fmt->black[p]) && std::isfinite(fmt->white) && fmt->white > fmt->black[p], "rc_raw_calibrate: white must exceed every black level (all finite)");
@@ -195,10 +195,9 @@ int rc_raw_calibrate(const void* d_src, const rc_raw_format* fmt, const rc_calib
     if (clip) RC_REQUIRE(std::isfinite(desc->clip_lo) && std::isfinite(desc->clip_hi) && desc->clip_lo < desc->clip_hi, "rc_raw_calibrate: clip needs finite lo < hi");
     RC_REQUIRE(K || cell || host_gains || d_frame_gains || clip, "rc_raw_calibrate: nothing enabled (no curve, no gain map, no gains, no clip)");
     // the destination
-    const int osize = dst_dtype == RC_F32 ? 4 : 2;
-    const long long dp = dst_pitch_bytes ? dst_pitch_bytes : 2LL * w * osize;
-    RC_REQUIRE(dp >= 2LL * w * osize && dp <= 0x7fffffffLL && dp % osize == 0, "rc_raw_calibrate: dst pitch shorter than one row or no multiple of the sample size");
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_dst) % osize == 0, "rc_raw_calibrate: dst misaligned");
+    const int osize = (int)dtype_size(dst_dtype);
+    long long dp;
+    if (const int e = raw_pitch("rc_raw_calibrate", "dst", d_dst, dst_pitch_bytes, 2LL * w * osize, osize, &dp)) return e;
     // a frame's byte offsets are formed in 32 bits
     RC_REQUIRE(2LL * h * lb <= 0x7fffffffLL && 2LL * h * dp <= 0x7fffffffLL, "rc_raw_calibrate: a frame (rows x pitch) must stay below 2 GiB");
 
@@ -209,8 +208,7 @@ int rc_raw_calibrate(const void* d_src, const rc_raw_format* fmt, const rc_calib
     a.dst = static_cast<uint8_t*>(d_dst);
     a.H = 2 * h; a.W = 2 * w;
     a.line_bytes = (int)lb; a.dst_pitch = (int)dp;
-    a.vec_in = !rs.packed && reinterpret_cast<uintptr_t>(d_src) % (kCalPx * rs.esize) == 0 && lb % (kCalPx * rs.esize) == 0;
-    a.vec_out = reinterpret_cast<uintptr_t>(d_dst) % (kCalPx * osize) == 0 && dp % (kCalPx * osize) == 0;
+    a.vec_in = rs.vec; a.vec_out = raw_vec(d_dst, dp, osize);
     a.nseg = K ? K - 1 : 0;
     a.cell_log2 = 0; a.Gw = 0; a.plane = 0;
     if (cell) {
@@ -235,22 +233,11 @@ int rc_raw_calibrate(const void* d_src, const rc_raw_format* fmt, const rc_calib
     }
     const hipStream_t s = as_stream(stream);
     const dim3 grid((unsigned)ceil_div(ceil_div(a.W, kCalSpan), kCalStrips), (unsigned)ceil_div(a.H, kCalRows), (unsigned)batch), block(kCalThreads);
-#define LAUNCH3(ST, TI)                                                                                                \
-    do {                                                                                                               \
-        if (dst_dtype == RC_F32) hipLaunchKernelGGL((raw_calibrate_kernel<ST, TI, float>), grid, block, 0, s, a);      \
-        else if (dst_dtype == RC_BF16) hipLaunchKernelGGL((raw_calibrate_kernel<ST, TI, bf16_t>), grid, block, 0, s, a); \
-        else hipLaunchKernelGGL((raw_calibrate_kernel<ST, TI, f16_t>), grid, block, 0, s, a);                          \
-    } while (0)
-    switch (fmt->storage) {
-        case RC_RAW_F32: LAUNCH3(kElem, float); break;
-        case RC_RAW_BF16: LAUNCH3(kElem, bf16_t); break;
-        case RC_RAW_F16: LAUNCH3(kElem, f16_t); break;
-        case RC_RAW_U16: LAUNCH3(kElem, uint16_t); break;
-        case RC_RAW_U8: LAUNCH3(kElem, uint8_t); break;
-        case RC_RAW_MIPI10: LAUNCH3(kMipi10, uint8_t); break;
-        default: LAUNCH3(kMipi12, uint8_t); break;
-    }
-#undef LAUNCH3
+    by_storage(fmt->storage, [&](auto sg) {
+        by_dtype(dst_dtype, [&](auto to) {
+            hipLaunchKernelGGL((raw_calibrate_kernel<decltype(sg)::ST, typename decltype(sg)::type, typename decltype(to)::type>), grid, block, 0, s, a);
+        });
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

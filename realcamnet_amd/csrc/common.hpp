@@ -44,6 +44,15 @@ template <> struct dtype_of<f16_t> { static constexpr int value = RC_F16; };
 
 __host__ __device__ inline size_t dtype_size(int dt) { return dt == RC_F32 ? 4 : 2; }
 
+// The host's dispatch over the float element types: f(Elem<T>()) for a checked RC_F32 / RC_BF16 / RC_F16; its result is returned.
+template <typename T> struct Elem { typedef T type; };
+template <typename F>
+inline auto by_dtype(int dtype, F&& f) {
+    if (dtype == RC_F32) return f(Elem<float>());
+    if (dtype == RC_BF16) return f(Elem<bf16_t>());
+    return f(Elem<f16_t>());
+}
+
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return static_cast<float>(v); }
 template <typename T> __device__ __forceinline__ T from_f32(float v) { return static_cast<T>(v); }
 

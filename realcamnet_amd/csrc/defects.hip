@@ -193,20 +193,16 @@ size_t rc_defect_desc_size(void) { return sizeof(rc_defect_desc); }
 int rc_raw_defects(const void* d_src, const rc_raw_format* fmt, const rc_defect_desc* desc, const void* d_map, int map_pitch_bytes,
                    void* d_dst, int dst_pitch_bytes, long long* d_counts, int batch, int h, int w, void* stream) {
     RC_REQUIRE(d_src && fmt && desc && d_dst, "rc_raw_defects: null pointer");
-    RC_REQUIRE(batch >= 1 && batch <= 65535 && h >= 1 && w >= 1 && h <= (1 << 20) && w <= (1 << 24), "rc_raw_defects: bad shape (empty, more than 65535 frames, or too large)");
+    if (const int e = raw_frames("rc_raw_defects", batch, h, w)) return e;
     RawSource rs;
     if (const int e = raw_source("rc_raw_defects", d_src, fmt, w, &rs)) return e;
-    const int st = fmt->storage, esize = rs.esize;
-    const long long lb = rs.line_bytes;
-    RC_REQUIRE(desc->reserved[0] == 0 && desc->reserved[1] == 0 && desc->reserved[2] == 0, "rc_raw_defects: reserved fields must be zero");
+    RC_REQUIRE(all_zero(desc->reserved), "rc_raw_defects: reserved fields must be zero");
     RC_REQUIRE((desc->flags & ~(RC_DEFECT_HOT | RC_DEFECT_COLD)) == 0, "rc_raw_defects: unknown flags");
     RC_REQUIRE(desc->flags != 0 || d_map, "rc_raw_defects: nothing enabled (no map, no hot test, no cold test)");
     const float thr[4] = {desc->hot_abs, desc->hot_rel, desc->cold_abs, desc->cold_rel};
     for (int k = 0; k < 4; ++k) RC_REQUIRE(std::isfinite(thr[k]) && thr[k] >= 0.f, "rc_raw_defects: thresholds must be finite and >= 0");
-    const int osize = st == RC_RAW_F32 ? 4 : 2;
-    const long long dp = dst_pitch_bytes ? dst_pitch_bytes : 2LL * w * osize;
-    RC_REQUIRE(dp >= 2LL * w * osize && dp <= 0x7fffffffLL && dp % osize == 0, "rc_raw_defects: dst pitch shorter than one row or no multiple of the sample size");
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_dst) % osize == 0, "rc_raw_defects: dst misaligned");
+    long long dp;
+    if (const int e = raw_pitch("rc_raw_defects", "dst", d_dst, dst_pitch_bytes, 2LL * w * rs.usize, rs.usize, &dp)) return e;
     if (d_map) {
         RC_REQUIRE(map_pitch_bytes % 4 == 0 && map_pitch_bytes >= 4 * ceil_div(2 * w, 32), "rc_raw_defects: the map pitch must be a multiple of 4 and hold 2w bits");
         RC_REQUIRE(reinterpret_cast<uintptr_t>(d_map) % 4 == 0, "rc_raw_defects: the map must be 4-byte aligned");
@@ -219,26 +215,18 @@ int rc_raw_defects(const void* d_src, const rc_raw_format* fmt, const rc_defect_
     a.dst = static_cast<uint8_t*>(d_dst);
     a.counts = reinterpret_cast<unsigned long long*>(d_counts);
     a.H = 2 * h; a.W = 2 * w;
-    a.line_bytes = (int)lb; a.map_pitch_dw = d_map ? map_pitch_bytes / 4 : 0; a.dst_pitch = (int)dp;
-    a.vec_in = !rs.packed && reinterpret_cast<uintptr_t>(d_src) % (kDfPx * esize) == 0 && lb % (kDfPx * esize) == 0;
-    a.vec_out = reinterpret_cast<uintptr_t>(d_dst) % (kDfPx * osize) == 0 && dp % (kDfPx * osize) == 0;
+    a.line_bytes = (int)rs.line_bytes; a.map_pitch_dw = d_map ? map_pitch_bytes / 4 : 0; a.dst_pitch = (int)dp;
+    a.vec_in = rs.vec; a.vec_out = raw_vec(d_dst, dp, rs.usize);
     a.hot = (desc->flags & RC_DEFECT_HOT) != 0; a.cold = (desc->flags & RC_DEFECT_COLD) != 0;
     a.hot_abs = desc->hot_abs; a.hot_rel = desc->hot_rel; a.cold_abs = desc->cold_abs; a.cold_rel = desc->cold_rel;
     for (int k = 0; k < 4; ++k) a.black[k] = fmt->black[k];
     const hipStream_t s = as_stream(stream);
     if (d_counts) RC_HIP_CHECK(hipMemsetAsync(d_counts, 0, (size_t)batch * 3 * sizeof(long long), s));
     const dim3 grid((unsigned)ceil_div(ceil_div(a.W, kDfSpan), kDfStrips), (unsigned)ceil_div(a.H, kDfRows), (unsigned)batch), block(kDfThreads);
-#define LAUNCH(ST, TI, TO) hipLaunchKernelGGL((raw_defects_kernel<ST, TI, TO>), grid, block, 0, s, a)
-    switch (st) {
-        case RC_RAW_F32: LAUNCH(kElem, float, float); break;
-        case RC_RAW_BF16: LAUNCH(kElem, bf16_t, bf16_t); break;
-        case RC_RAW_F16: LAUNCH(kElem, f16_t, f16_t); break;
-        case RC_RAW_U16: LAUNCH(kElem, uint16_t, uint16_t); break;
-        case RC_RAW_U8: LAUNCH(kElem, uint8_t, uint16_t); break;
-        case RC_RAW_MIPI10: LAUNCH(kMipi10, uint8_t, uint16_t); break;
-        default: LAUNCH(kMipi12, uint8_t, uint16_t); break;
-    }
-#undef LAUNCH
+    by_storage(fmt->storage, [&](auto sg) {
+        typedef typename decltype(sg)::type TI;
+        hipLaunchKernelGGL((raw_defects_kernel<decltype(sg)::ST, TI, unpacked_t<TI>>), grid, block, 0, s, a);
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

@@ -118,14 +118,14 @@ size_t rc_hdr_desc_size(void) { return sizeof(rc_hdr_desc); }
 int rc_raw_hdr_merge(const void* d_src, const rc_raw_format* fmt, const rc_hdr_desc* desc, const float* d_times, int times_batch, void* d_dst,
                      int dst_pitch_bytes, int batch, int h, int w, void* stream) {
     RC_REQUIRE(d_src && fmt && desc && d_dst, "rc_raw_hdr_merge: null pointer");
-    RC_REQUIRE(batch >= 1 && batch <= 65535 && h >= 1 && w >= 1 && h <= (1 << 20) && w <= (1 << 24), "rc_raw_hdr_merge: bad shape (empty, more than 65535 frames, or too large)");
+    if (const int e = raw_frames("rc_raw_hdr_merge", batch, h, w)) return e;
     RawSource rs;
     if (const int e = raw_source("rc_raw_hdr_merge", d_src, fmt, w, &rs)) return e;
     const long long lb = rs.line_bytes;
-    for (int p = 0; p < 4; ++p) RC_REQUIRE(std::isfinite(fmt->black[p]), "rc_raw_hdr_merge: black levels must be finite");
+    if (const int e = raw_blacks_finite("rc_raw_hdr_merge", fmt)) return e;
     const int E = desc->exposures;
     RC_REQUIRE(E >= 2 && E <= kHdrMaxE, "rc_raw_hdr_merge: 2 to 4 exposures");
-    RC_REQUIRE(desc->reserved[0] == 0 && desc->reserved[1] == 0 && desc->reserved[2] == 0 && desc->reserved[3] == 0, "rc_raw_hdr_merge: reserved fields must be zero");
+    RC_REQUIRE(all_zero(desc->reserved), "rc_raw_hdr_merge: reserved fields must be zero");
     RC_REQUIRE((desc->flags & ~RC_HDR_MOTION) == 0, "rc_raw_hdr_merge: unknown flags");
     // the times
     if (d_times) {
@@ -149,9 +149,8 @@ int rc_raw_hdr_merge(const void* d_src, const rc_raw_format* fmt, const rc_hdr_d
     RC_REQUIRE(es > 0 && fs > 0, "rc_raw_hdr_merge: strides must be positive (0: whole frames, dense)");
     RC_REQUIRE(es % unit == 0 && fs % unit == 0, "rc_raw_hdr_merge: strides misaligned (MIPI: 4 bytes, else one sample)");
     // the destination
-    const long long dp = dst_pitch_bytes ? dst_pitch_bytes : 2LL * w * 4;
-    RC_REQUIRE(dp >= 2LL * w * 4 && dp <= 0x7fffffffLL && dp % 4 == 0, "rc_raw_hdr_merge: dst pitch shorter than one row or no multiple of the sample size");
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_dst) % 4 == 0, "rc_raw_hdr_merge: dst misaligned");
+    long long dp;
+    if (const int e = raw_pitch("rc_raw_hdr_merge", "dst", d_dst, dst_pitch_bytes, 2LL * w * 4, 4, &dp)) return e;
     // a frame's byte offsets, over all its exposures, are formed in 32 bits
     RC_REQUIRE(es <= 0x7fffffffLL && (E - 1) * es + 2LL * h * lb <= 0x7fffffffLL && 2LL * h * dp <= 0x7fffffffLL,
                "rc_raw_hdr_merge: a frame (all its exposures: strides, rows x pitch) must stay below 2 GiB");
@@ -164,8 +163,8 @@ int rc_raw_hdr_merge(const void* d_src, const rc_raw_format* fmt, const rc_hdr_d
     a.H = 2 * h; a.W = 2 * w;
     a.line_bytes = (int)lb; a.exp_stride = (int)es; a.dst_pitch = (int)dp;
     const long long quad = (long long)kHdrPx * rs.esize;
-    a.vec_in = !rs.packed && reinterpret_cast<uintptr_t>(d_src) % quad == 0 && lb % quad == 0 && es % quad == 0 && fs % quad == 0;
-    a.vec_out = reinterpret_cast<uintptr_t>(d_dst) % (kHdrPx * 4) == 0 && dp % (kHdrPx * 4) == 0;
+    a.vec_in = rs.vec && es % quad == 0 && fs % quad == 0;
+    a.vec_out = raw_vec(d_dst, dp, 4);
     a.times_stride = d_times && times_batch > 1 ? E : 0;
     a.motion = motion;
     for (int p = 0; p < 4; ++p) a.black[p] = fmt->black[p];
@@ -179,22 +178,13 @@ int rc_raw_hdr_merge(const void* d_src, const rc_raw_format* fmt, const rc_hdr_d
     a.m_abs = motion ? desc->motion_abs : 0.f; a.m_rel = motion ? desc->motion_rel : 0.f;
     const hipStream_t s = as_stream(stream);
     const dim3 grid((unsigned)ceil_div(ceil_div(a.W, kHdrSpan), kHdrStrips), (unsigned)ceil_div(a.H, kHdrRows), (unsigned)batch), block(kHdrThreads);
-#define LAUNCH_E(ST, TI)                                                                                    \
-    do {                                                                                                    \
-        if (E == 2) hipLaunchKernelGGL((raw_hdr_merge_kernel<ST, TI, 2>), grid, block, 0, s, a);            \
-        else if (E == 3) hipLaunchKernelGGL((raw_hdr_merge_kernel<ST, TI, 3>), grid, block, 0, s, a);       \
-        else hipLaunchKernelGGL((raw_hdr_merge_kernel<ST, TI, 4>), grid, block, 0, s, a);                   \
-    } while (0)
-    switch (fmt->storage) {
-        case RC_RAW_F32: LAUNCH_E(kElem, float); break;
-        case RC_RAW_BF16: LAUNCH_E(kElem, bf16_t); break;
-        case RC_RAW_F16: LAUNCH_E(kElem, f16_t); break;
-        case RC_RAW_U16: LAUNCH_E(kElem, uint16_t); break;
-        case RC_RAW_U8: LAUNCH_E(kElem, uint8_t); break;
-        case RC_RAW_MIPI10: LAUNCH_E(kMipi10, uint8_t); break;
-        default: LAUNCH_E(kMipi12, uint8_t); break;
-    }
-#undef LAUNCH_E
+    by_storage(fmt->storage, [&](auto sg) {
+        constexpr int ST = decltype(sg)::ST;
+        typedef typename decltype(sg)::type TI;
+        if (E == 2) hipLaunchKernelGGL((raw_hdr_merge_kernel<ST, TI, 2>), grid, block, 0, s, a);
+        else if (E == 3) hipLaunchKernelGGL((raw_hdr_merge_kernel<ST, TI, 3>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((raw_hdr_merge_kernel<ST, TI, 4>), grid, block, 0, s, a);
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

@@ -198,59 +198,32 @@ int rc_raw_quad(const void* d_src, const rc_raw_format* fmt, const rc_quad_desc*
     RC_REQUIRE(H % 4 == 0 && W % 4 == 0, "rc_raw_quad: H and W must be multiples of 4 (the quad tile)");
     RawSource rs;
     if (const int e = raw_source("rc_raw_quad", d_src, fmt, W / 2, &rs)) return e;
-    const int st = fmt->storage, esize = rs.esize;
-    const long long lb = rs.line_bytes;
-    RC_REQUIRE(desc->reserved[0] == 0 && desc->reserved[1] == 0 && desc->reserved[2] == 0, "rc_raw_quad: reserved fields must be zero");
+    RC_REQUIRE(all_zero(desc->reserved), "rc_raw_quad: reserved fields must be zero");
     RC_REQUIRE(desc->mode == RC_QUAD_REMOSAIC || desc->mode == RC_QUAD_BIN, "rc_raw_quad: unknown mode");
     const bool bin = desc->mode == RC_QUAD_BIN;
-    const int osize = bin || st == RC_RAW_F32 ? 4 : 2;
-    const long long row = (bin ? W / 2 : W) * (long long)osize;
-    const long long dp = dst_pitch_bytes ? dst_pitch_bytes : row;
-    RC_REQUIRE(dp >= row && dp <= 0x7fffffffLL && dp % osize == 0, "rc_raw_quad: dst pitch shorter than one row or no multiple of the sample size");
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_dst) % osize == 0, "rc_raw_quad: dst misaligned");
+    const int osize = bin ? 4 : rs.usize;
+    long long dp;
+    if (const int e = raw_pitch("rc_raw_quad", "dst", d_dst, dst_pitch_bytes, (bin ? W / 2 : W) * (long long)osize, osize, &dp)) return e;
 
     QuadArgs a;
     a.src = static_cast<const uint8_t*>(d_src);
     a.dst = static_cast<uint8_t*>(d_dst);
     a.H = H; a.W = W;
-    a.line_bytes = (int)lb; a.dst_pitch = (int)dp;
-    a.vec_in = !rs.packed && reinterpret_cast<uintptr_t>(d_src) % (kQdPx * esize) == 0 && lb % (kQdPx * esize) == 0;
-    const int ovec = bin ? 8 : kQdPx * osize;                                      // bin: a lane stores two floats
-    a.vec_out = reinterpret_cast<uintptr_t>(d_dst) % ovec == 0 && dp % ovec == 0;
+    a.line_bytes = (int)rs.line_bytes; a.dst_pitch = (int)dp;
+    a.vec_in = rs.vec;
+    a.vec_out = raw_vec(d_dst, dp, bin ? osize / 2 : osize);                       // bin: a lane stores two floats, half a vector of four
     const bool ga = fmt->cfa == RC_CFA_RGGB || fmt->cfa == RC_CFA_BGGR;            // G on the cell's anti-diagonal
     const hipStream_t s = as_stream(stream);
     const dim3 block(kQdThreads);
-    if (bin) {
-        const dim3 grid((unsigned)ceil_div(W / kQdPx, kQdThreads), (unsigned)ceil_div(H / 2, kQbRows), (unsigned)batch);
-#define LAUNCH(ST, TI) hipLaunchKernelGGL((raw_quad_bin_kernel<ST, TI>), grid, block, 0, s, a)
-        switch (st) {
-            case RC_RAW_F32: LAUNCH(kElem, float); break;
-            case RC_RAW_BF16: LAUNCH(kElem, bf16_t); break;
-            case RC_RAW_F16: LAUNCH(kElem, f16_t); break;
-            case RC_RAW_U16: LAUNCH(kElem, uint16_t); break;
-            case RC_RAW_U8: LAUNCH(kElem, uint8_t); break;
-            case RC_RAW_MIPI10: LAUNCH(kMipi10, uint8_t); break;
-            default: LAUNCH(kMipi12, uint8_t); break;
-        }
-#undef LAUNCH
-    } else {
-        const dim3 grid((unsigned)ceil_div(ceil_div(W, kQdSpan), kQdStrips), (unsigned)ceil_div(H, kQdRows), (unsigned)batch);
-#define LAUNCH(ST, TI, TO)                                                                                    \
-    do {                                                                                                      \
-        if (ga) hipLaunchKernelGGL((raw_quad_remosaic_kernel<ST, TI, TO, true>), grid, block, 0, s, a);       \
-        else hipLaunchKernelGGL((raw_quad_remosaic_kernel<ST, TI, TO, false>), grid, block, 0, s, a);         \
-    } while (0)
-        switch (st) {
-            case RC_RAW_F32: LAUNCH(kElem, float, float); break;
-            case RC_RAW_BF16: LAUNCH(kElem, bf16_t, bf16_t); break;
-            case RC_RAW_F16: LAUNCH(kElem, f16_t, f16_t); break;
-            case RC_RAW_U16: LAUNCH(kElem, uint16_t, uint16_t); break;
-            case RC_RAW_U8: LAUNCH(kElem, uint8_t, uint16_t); break;
-            case RC_RAW_MIPI10: LAUNCH(kMipi10, uint8_t, uint16_t); break;
-            default: LAUNCH(kMipi12, uint8_t, uint16_t); break;
-        }
-#undef LAUNCH
-    }
+    const dim3 grid = bin ? dim3((unsigned)ceil_div(W / kQdPx, kQdThreads), (unsigned)ceil_div(H / 2, kQbRows), (unsigned)batch)
+                          : dim3((unsigned)ceil_div(ceil_div(W, kQdSpan), kQdStrips), (unsigned)ceil_div(H, kQdRows), (unsigned)batch);
+    by_storage(fmt->storage, [&](auto sg) {
+        constexpr int ST = decltype(sg)::ST;
+        typedef typename decltype(sg)::type TI;
+        if (bin) hipLaunchKernelGGL((raw_quad_bin_kernel<ST, TI>), grid, block, 0, s, a);
+        else if (ga) hipLaunchKernelGGL((raw_quad_remosaic_kernel<ST, TI, unpacked_t<TI>, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((raw_quad_remosaic_kernel<ST, TI, unpacked_t<TI>, false>), grid, block, 0, s, a);
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

@@ -225,26 +225,13 @@ int rc_raw_ingest_fmt(const void* d_src, const rc_raw_format* fmt, void* d_packe
     }
     a.scale_y = (float)h / (float)cond_h; a.scale_x = (float)w / (float)cond_w;
     const size_t total = (size_t)batch * hp * ((wp + 1) / 2) + (size_t)batch * cond_h * cond_w;
-#define LAUNCH(ST, TI, TO)                                                                                          \
-    hipLaunchKernelGGL((raw_ingest_fmt_kernel<ST, TI, TO>), dim3(rf_grid(total)), dim3(kRfThreads), 0, as_stream(stream), a, \
-                       static_cast<TO*>(d_packed), static_cast<TO*>(d_cond))
-#define BY_OUT(ST, TI)                                                              \
-    do {                                                                            \
-        if (out_dtype == RC_F32) LAUNCH(ST, TI, float);                             \
-        else if (out_dtype == RC_BF16) LAUNCH(ST, TI, bf16_t);                      \
-        else LAUNCH(ST, TI, f16_t);                                                 \
-    } while (0)
-    switch (fmt->storage) {
-        case RC_RAW_F32: BY_OUT(kElem, float); break;
-        case RC_RAW_BF16: BY_OUT(kElem, bf16_t); break;
-        case RC_RAW_F16: BY_OUT(kElem, f16_t); break;
-        case RC_RAW_U16: BY_OUT(kElem, uint16_t); break;
-        case RC_RAW_U8: BY_OUT(kElem, uint8_t); break;
-        case RC_RAW_MIPI10: BY_OUT(kMipi10, uint8_t); break;
-        default: BY_OUT(kMipi12, uint8_t); break;
-    }
-#undef BY_OUT
-#undef LAUNCH
+    by_storage(fmt->storage, [&](auto sg) {
+        by_dtype(out_dtype, [&](auto to) {
+            typedef typename decltype(to)::type TO;
+            hipLaunchKernelGGL((raw_ingest_fmt_kernel<decltype(sg)::ST, typename decltype(sg)::type, TO>), dim3(rf_grid(total)), dim3(kRfThreads), 0,
+                               as_stream(stream), a, static_cast<TO*>(d_packed), static_cast<TO*>(d_cond));
+        });
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }
@@ -257,19 +244,16 @@ int rc_rgb_encode(const void* d_src, int src_dtype, void* d_dst, int out_bits, i
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_dst) % 16 == 0, "rc_rgb_encode: dst must be 16-byte aligned");
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % dtype_size(src_dtype) == 0, "rc_rgb_encode: src misaligned");
     const size_t total = (size_t)batch * h * w;
-#define LAUNCH(TI, BITS)                                                                                                     \
-    hipLaunchKernelGGL((rgb_encode_kernel<TI, BITS>), dim3(rf_grid((total + RgbOut<BITS>::P - 1) / RgbOut<BITS>::P)), dim3(kRfThreads), 0, \
-                       as_stream(stream), static_cast<const TI*>(d_src), static_cast<typename RgbOut<BITS>::T*>(d_dst), batch, H, W, h, w)
-#define BY_BITS(TI)                         \
-    do {                                    \
-        if (out_bits == 8) LAUNCH(TI, 8);   \
-        else LAUNCH(TI, 16);                \
-    } while (0)
-    if (src_dtype == RC_F32) BY_BITS(float);
-    else if (src_dtype == RC_BF16) BY_BITS(bf16_t);
-    else BY_BITS(f16_t);
-#undef BY_BITS
-#undef LAUNCH
+    by_dtype(src_dtype, [&](auto ti) {
+        typedef typename decltype(ti)::type TI;
+        const TI* src = static_cast<const TI*>(d_src);
+        const dim3 block(kRfThreads);
+        const hipStream_t s = as_stream(stream);
+        if (out_bits == 8)
+            hipLaunchKernelGGL((rgb_encode_kernel<TI, 8>), dim3(rf_grid((total + RgbOut<8>::P - 1) / RgbOut<8>::P)), block, 0, s, src, static_cast<uint8_t*>(d_dst), batch, H, W, h, w);
+        else
+            hipLaunchKernelGGL((rgb_encode_kernel<TI, 16>), dim3(rf_grid((total + RgbOut<16>::P - 1) / RgbOut<16>::P)), block, 0, s, src, static_cast<uint16_t*>(d_dst), batch, H, W, h, w);
+    });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

@@ -1,10 +1,14 @@
-// How a sensor mosaic row is stored, and nothing else: the one reader of the rc_raw_storage forms for rc_raw_ingest_fmt (raw_format.hip),
-// rc_raw_defects (defects.hip) and rc_raw_calibrate (calibrate.hip).  A row is either one TI per sample (fp32 / bf16 / fp16 / uint16 /
-// uint8) or MIPI CSI-2 packed bytes: RAW10 = groups of 5 bytes (bytes 0-3: bits [9:2] of samples 0-3, byte 4: their bits [1:0], sample k
-// at bits 2k+1..2k), RAW12 = groups of 3 bytes (bytes 0, 1: bits [11:4] of samples 0, 1, byte 2: their bits [3:0], sample 1 high).  A lane
-// works on kRowPx consecutive samples that start on a multiple of kRowPx: one RAW10 group, two RAW12 groups.  A further storage is added
-// here -- the window, its unpack, row_load / row_decode, and raw_source on the host -- and in the three entry points' switch.
+// How a sensor mosaic row is stored, and nothing else: the one reader of the rc_raw_storage forms for the six entry points that read a frame
+// as rc_raw_format describes it -- rc_raw_ingest_fmt (raw_format.hip), rc_raw_defects (defects.hip), rc_raw_calibrate (calibrate.hip),
+// rc_raw_hdr_merge (hdr_merge.hip), rc_raw_temporal (temporal.hip) and rc_raw_quad (quad.hip).  A row is either one TI per sample (fp32 /
+// bf16 / fp16 / uint16 / uint8) or MIPI CSI-2 packed bytes: RAW10 = groups of 5 bytes (bytes 0-3: bits [9:2] of samples 0-3, byte 4: their
+// bits [1:0], sample k at bits 2k+1..2k), RAW12 = groups of 3 bytes (bytes 0, 1: bits [11:4] of samples 0, 1, byte 2: their bits [3:0],
+// sample 1 high).  A lane works on kRowPx consecutive samples that start on a multiple of kRowPx: one RAW10 group, two RAW12 groups.  The
+// host half is here too: by_storage for an entry's launch, and the checks the entries share (raw_frames, raw_source, raw_pitch ...).  A
+// further storage is added in this header alone: the window, its unpack, row_load / row_decode, and by_storage and raw_source on the host.
 #pragma once
+#include <cmath>
+
 #include "common.hpp"
 
 namespace rc {
@@ -155,21 +159,60 @@ __device__ __forceinline__ void row_store(TO* o, const float* v, int n, bool ful
     }
 }
 
-// ---- the host's check of a source frame -----------------------------------------------------------------------------------------------------
+// ---- the host half: the launch ---------------------------------------------------------------------------------------------------------------
+// The one map from rc_raw_storage to how a kernel reads it: f(Stored<ST, TI>()) for a checked storage; its result is returned.  The choices
+// that belong to one stage (a destination type: common.hpp's by_dtype; hdr's E, quad's mode) are made inside f.
+template <int S, typename T> struct Stored { static constexpr int ST = S; typedef T type; };
+
+template <typename F>
+inline auto by_storage(int storage, F&& f) {
+    switch (storage) {
+        case RC_RAW_F32: return f(Stored<kElem, float>());
+        case RC_RAW_BF16: return f(Stored<kElem, bf16_t>());
+        case RC_RAW_F16: return f(Stored<kElem, f16_t>());
+        case RC_RAW_U16: return f(Stored<kElem, uint16_t>());
+        case RC_RAW_U8: return f(Stored<kElem, uint8_t>());
+        case RC_RAW_MIPI10: return f(Stored<kMipi10, uint8_t>());
+        default: return f(Stored<kMipi12, uint8_t>());
+    }
+}
+
+// What a stage that keeps the storage writes: a float storage as itself, counts (u16 / u8 / RAW10 / RAW12) as uint16 (RawSource::usize bytes).
+template <typename TI> using unpacked_t = typename std::conditional<std::is_integral<TI>::value, uint16_t, TI>::type;
+
+// ---- the host half: the checks ---------------------------------------------------------------------------------------------------------------
+// Each returns RC_OK, or the error as RC_REQUIRE reports it; `who` names the entry point in the messages.
+template <typename T, size_t N>
+inline bool all_zero(const T (&v)[N]) {                                            // reserved fields
+    for (size_t i = 0; i < N; ++i)
+        if (v[i] != 0) return false;
+    return true;
+}
+
+// Every lane's kRowPx samples of `bytes` each are one vector access: the base and the pitch are multiples of it.
+inline bool raw_vec(const void* p, long long pitch, int bytes) { return reinterpret_cast<uintptr_t>(p) % (kRowPx * bytes) == 0 && pitch % (kRowPx * bytes) == 0; }
+
+// `batch` frames of a mosaic (2h, 2w): the grid's z takes 65535, and rows and columns stay far inside an int.
+inline int raw_frames(const char* who, int batch, int h, int w) {
+    RC_REQUIRE(batch >= 1 && batch <= 65535 && h >= 1 && w >= 1 && h <= (1 << 20) && w <= (1 << 24), std::string(who) + ": bad shape (empty, more than 65535 frames, or too large)");
+    return RC_OK;
+}
+
 struct RawSource {
     long long line_bytes;      // the frame's line stride (fmt->line_bytes, or one dense row): fits an int
     int esize;                 // bytes per sample of an element storage (2 for the packed ones: what they unpack to)
+    int usize;                 // bytes per sample of unpacked_t
     bool packed;               // MIPI RAW10 / RAW12
+    bool vec;                  // an element storage whose base and lines are multiples of kRowPx samples
 };
 
-// What every entry point that reads a sensor frame (B, 2h, 2w) at d_src as `fmt` describes it requires of the two; `who` names it in the
-// messages.  RC_OK, or the error as RC_REQUIRE reports it.
+// What every entry point that reads a sensor frame (B, 2h, 2w) at d_src as `fmt` describes it requires of the two.
 inline int raw_source(const char* who, const void* d_src, const rc_raw_format* fmt, int w, RawSource* out) {
     const std::string at = std::string(who) + ": ";
     const int st = fmt->storage;
     RC_REQUIRE(st >= RC_RAW_F32 && st <= RC_RAW_MIPI12, at + "unknown storage");
     RC_REQUIRE(fmt->cfa >= RC_CFA_RGGB && fmt->cfa <= RC_CFA_GBRG, at + "unknown cfa");
-    RC_REQUIRE(fmt->reserved[0] == 0 && fmt->reserved[1] == 0 && fmt->reserved[2] == 0 && fmt->reserved[3] == 0, at + "the format's reserved fields must be zero");
+    RC_REQUIRE(all_zero(fmt->reserved), at + "the format's reserved fields must be zero");
     RC_REQUIRE(fmt->width == 0 || fmt->width == 2 * w, at + "width must be 0 or the mosaic width 2w");
     const bool packed = st == RC_RAW_MIPI10 || st == RC_RAW_MIPI12;
     RC_REQUIRE(st != RC_RAW_MIPI10 || (2 * w) % 4 == 0, at + "RAW10 needs a mosaic width 2w divisible by 4");
@@ -179,7 +222,22 @@ inline int raw_source(const char* who, const void* d_src, const rc_raw_format* f
     RC_REQUIRE(lb >= need && lb <= 0x7fffffffLL, at + "line_bytes shorter than one mosaic row");
     RC_REQUIRE(packed || lb % esize == 0, at + "line_bytes must be a multiple of the sample size");
     RC_REQUIRE(reinterpret_cast<uintptr_t>(d_src) % (packed ? 4 : esize) == 0, at + "source misaligned (MIPI: 4 bytes, else one sample)");
-    out->line_bytes = lb; out->esize = esize; out->packed = packed;
+    *out = {lb, esize, st == RC_RAW_F32 ? 4 : 2, packed, !packed && raw_vec(d_src, lb, esize)};
+    return RC_OK;
+}
+
+inline int raw_blacks_finite(const char* who, const rc_raw_format* fmt) {
+    for (int p = 0; p < 4; ++p) RC_REQUIRE(std::isfinite(fmt->black[p]), std::string(who) + ": black levels must be finite");
+    return RC_OK;
+}
+
+// A destination or state buffer (`name`: "dst", "prev") at p, rows of row_bytes, samples of esize bytes: its pitch (0: dense) into *out.
+inline int raw_pitch(const char* who, const char* name, const void* p, int pitch_bytes, long long row_bytes, int esize, long long* out) {
+    const long long pitch = pitch_bytes ? pitch_bytes : row_bytes;
+    RC_REQUIRE(pitch >= row_bytes && pitch <= 0x7fffffffLL && pitch % esize == 0,
+               std::string(who) + ": " + name + " pitch shorter than one row or no multiple of the sample size");
+    RC_REQUIRE(reinterpret_cast<uintptr_t>(p) % esize == 0, std::string(who) + ": " + name + " misaligned");
+    *out = pitch;
     return RC_OK;
 }
 

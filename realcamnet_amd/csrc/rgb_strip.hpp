@@ -99,15 +99,9 @@ inline LumaChroma rgb_coef(int matrix) {
 }
 
 // ---- the host's dispatch over the element types -----------------------------------------------------------------------------------------
-template <typename T> struct Elem { typedef T type; };
-
-// f(Elem<TI>()) for a checked source dtype; its result is returned.
+// f(Elem<TI>()) for a checked source dtype; its result is returned (common.hpp's by_dtype, under the name the stages use).
 template <typename F>
-inline auto by_source(int src_dtype, F&& f) {
-    if (src_dtype == RC_F32) return f(Elem<float>());
-    if (src_dtype == RC_BF16) return f(Elem<bf16_t>());
-    return f(Elem<f16_t>());
-}
+inline auto by_source(int src_dtype, F&& f) { return by_dtype(src_dtype, f); }
 
 // f(Elem<TI>(), Elem<TO>()) for a checked pair: TO is float or TI.
 template <typename F>

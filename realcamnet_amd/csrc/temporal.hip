@@ -169,12 +169,12 @@ size_t rc_temporal_desc_size(void) { return sizeof(rc_temporal_desc); }
 int rc_raw_temporal(const void* d_src, const rc_raw_format* fmt, const rc_temporal_desc* desc, const float* d_prev, int prev_pitch_bytes,
                     const float* d_gain, int gain_batch, void* d_dst, int dst_pitch_bytes, int batch, int h, int w, void* stream) {
     RC_REQUIRE(d_src && fmt && desc && d_dst, "rc_raw_temporal: null pointer");
-    RC_REQUIRE(batch >= 1 && batch <= 65535 && h >= 1 && w >= 1 && h <= (1 << 20) && w <= (1 << 24), "rc_raw_temporal: bad shape (empty, more than 65535 frames, or too large)");
+    if (const int e = raw_frames("rc_raw_temporal", batch, h, w)) return e;
     RawSource rs;
     if (const int e = raw_source("rc_raw_temporal", d_src, fmt, w, &rs)) return e;
     const long long lb = rs.line_bytes;
-    for (int p = 0; p < 4; ++p) RC_REQUIRE(std::isfinite(fmt->black[p]), "rc_raw_temporal: black levels must be finite");
-    RC_REQUIRE(desc->reserved[0] == 0 && desc->reserved[1] == 0 && desc->reserved[2] == 0 && desc->reserved[3] == 0, "rc_raw_temporal: reserved fields must be zero");
+    if (const int e = raw_blacks_finite("rc_raw_temporal", fmt)) return e;
+    RC_REQUIRE(all_zero(desc->reserved), "rc_raw_temporal: reserved fields must be zero");
     RC_REQUIRE((desc->flags & ~(RC_TNR_RESET | RC_TNR_GAIN)) == 0, "rc_raw_temporal: unknown flags");
     const bool reset = (desc->flags & RC_TNR_RESET) != 0, host_gain = (desc->flags & RC_TNR_GAIN) != 0;
     // the parameters
@@ -193,13 +193,11 @@ int rc_raw_temporal(const void* d_src, const rc_raw_format* fmt, const rc_tempor
     }
     // the state and the destination
     const long long row = 2LL * w * 4, rows = (long long)batch * 2LL * h;
-    const long long dp = dst_pitch_bytes ? dst_pitch_bytes : row, pp = prev_pitch_bytes ? prev_pitch_bytes : row;
-    RC_REQUIRE(dp >= row && dp <= 0x7fffffffLL && dp % 4 == 0, "rc_raw_temporal: dst pitch shorter than one row or no multiple of 4");
-    RC_REQUIRE(reinterpret_cast<uintptr_t>(d_dst) % 4 == 0, "rc_raw_temporal: dst misaligned");
+    long long dp, pp = prev_pitch_bytes ? prev_pitch_bytes : row;                  // pp without a state: not looked at
+    if (const int e = raw_pitch("rc_raw_temporal", "dst", d_dst, dst_pitch_bytes, row, 4, &dp)) return e;
     RC_REQUIRE(reset || d_prev, "rc_raw_temporal: no state (d_prev is null) and no RC_TNR_RESET");
     if (d_prev) {
-        RC_REQUIRE(pp >= row && pp <= 0x7fffffffLL && pp % 4 == 0, "rc_raw_temporal: prev pitch shorter than one row or no multiple of 4");
-        RC_REQUIRE(reinterpret_cast<uintptr_t>(d_prev) % 4 == 0, "rc_raw_temporal: prev misaligned");
+        if (const int e = raw_pitch("rc_raw_temporal", "prev", d_prev, prev_pitch_bytes, row, 4, &pp)) return e;
         const uintptr_t p0 = reinterpret_cast<uintptr_t>(d_prev), p1 = p0 + (uintptr_t)((rows - 1) * pp + row);
         const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_dst), o1 = o0 + (uintptr_t)((rows - 1) * dp + row);
         RC_REQUIRE(p1 <= o0 || o1 <= p0, "rc_raw_temporal: dst overlaps prev (a row's neighbours are read after it is written)");
@@ -215,10 +213,7 @@ int rc_raw_temporal(const void* d_src, const rc_raw_format* fmt, const rc_tempor
     a.dst = static_cast<uint8_t*>(d_dst);
     a.H = 2 * h; a.W = 2 * w;
     a.line_bytes = (int)lb; a.prev_pitch = (int)pp; a.dst_pitch = (int)dp;
-    const long long quad = (long long)kTnrPx * rs.esize;
-    a.vec_in = !rs.packed && reinterpret_cast<uintptr_t>(d_src) % quad == 0 && lb % quad == 0;
-    a.vec_prev = d_prev && reinterpret_cast<uintptr_t>(d_prev) % (kTnrPx * 4) == 0 && pp % (kTnrPx * 4) == 0;
-    a.vec_out = reinterpret_cast<uintptr_t>(d_dst) % (kTnrPx * 4) == 0 && dp % (kTnrPx * 4) == 0;
+    a.vec_in = rs.vec; a.vec_prev = d_prev && raw_vec(d_prev, pp, 4); a.vec_out = raw_vec(d_dst, dp, 4);
     a.reset = reset;
     a.has_gain = !reset && (host_gain || d_gain);
     a.gain_stride = d_gain && gain_batch > 1 ? 1 : 0;
@@ -229,15 +224,7 @@ int rc_raw_temporal(const void* d_src, const rc_raw_format* fmt, const rc_tempor
     const hipStream_t s = as_stream(stream);
     const int strips = 1 + (a.W > kTnrSpan ? ceil_div(a.W - kTnrSpan, kTnrOut) : 0);
     const dim3 grid((unsigned)ceil_div(strips, kTnrStrips), (unsigned)ceil_div(a.H, kTnrRows), (unsigned)batch), block(kTnrThreads);
-    switch (fmt->storage) {
-        case RC_RAW_F32: hipLaunchKernelGGL((raw_temporal_kernel<kElem, float>), grid, block, 0, s, a); break;
-        case RC_RAW_BF16: hipLaunchKernelGGL((raw_temporal_kernel<kElem, bf16_t>), grid, block, 0, s, a); break;
-        case RC_RAW_F16: hipLaunchKernelGGL((raw_temporal_kernel<kElem, f16_t>), grid, block, 0, s, a); break;
-        case RC_RAW_U16: hipLaunchKernelGGL((raw_temporal_kernel<kElem, uint16_t>), grid, block, 0, s, a); break;
-        case RC_RAW_U8: hipLaunchKernelGGL((raw_temporal_kernel<kElem, uint8_t>), grid, block, 0, s, a); break;
-        case RC_RAW_MIPI10: hipLaunchKernelGGL((raw_temporal_kernel<kMipi10, uint8_t>), grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL((raw_temporal_kernel<kMipi12, uint8_t>), grid, block, 0, s, a); break;
-    }
+    by_storage(fmt->storage, [&](auto sg) { hipLaunchKernelGGL((raw_temporal_kernel<decltype(sg)::ST, typename decltype(sg)::type>), grid, block, 0, s, a); });
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

@@ -470,19 +470,37 @@ _RAW_TENSOR_DTYPE = {"u16": torch.uint16, "u8": torch.uint8, "mipi10": torch.uin
 _RAW_STORAGE = {"u16": _lib.RC_RAW_U16, "u8": _lib.RC_RAW_U8, "mipi10": _lib.RC_RAW_MIPI10, "mipi12": _lib.RC_RAW_MIPI12}
 
 
-def _raw_source(mosaic, raw_format, who, quad=False):
-    """The sensor frame the mosaic front-end ops read (raw_ingest(raw_format=), raw_defects, raw_calibrate, raw_hdr_merge): checks `mosaic` against
-    `raw_format` (a RawFormat) and returns the frame as a contiguous (B, 2h, X) tensor on the device -- with raw_format.exposures set,
-    (B, E, 2h, X) or (B, E 2h, X) as its layout says -- its rc_raw_storage and (2h, 2w) of one exposure.  `who` opens the message that names
-    the op.  Only raw_quad (`quad`) reads a Quad-Bayer frame; (2h, 2w) is then the size of its result."""
+# What a sensor-side op says of a stage it does not run when the format still asks for it, in the order the refusals are tried.
+_STAGE_REFUSALS = (
+    ("exposures", "{op} reads one exposure: merge first.  The order is ops.raw_defects (per exposure), ops.raw_hdr_merge, ops.raw_calibrate, "
+                  "ops.raw_ingest, with ops.raw_temporal behind the merge where the format filters (forward_mosaic runs them all)"),
+    ("temporal", "{op} does not filter: raw_format.temporal is set.  The order is ops.raw_defects, ops.raw_hdr_merge, ops.raw_temporal, "
+                 "ops.raw_calibrate, ops.raw_ingest, each on a format without the stages already run (forward_mosaic runs all five)"),
+    ("quad", "{op}: the frame is Quad-Bayer (raw_format.quad is set) and this op reads a Bayer mosaic: run ops.raw_quad first and hand its "
+             "result on with quad=None (forward_mosaic does both)"),
+    ("defects", "{op} does not correct defects: run ops.raw_defects first, on each exposure where there are several, and hand its result on "
+                "(forward_mosaic does both)"),
+    ("calibration", "{op} does not calibrate: run ops.raw_calibrate first and ingest its float result with levels 0 / 1 (forward_mosaic does both)"),
+)
+
+
+def _raw_stages(raw_format, op, sees):
+    """Where every sensor-side op starts: `raw_format` is a RawFormat, and of its stages only those in `sees` -- the ones `op` runs itself or
+    leaves to a later op -- are set.  An op refuses the others rather than skip them silently or misread the frame."""
     from .raw_format import RawFormat
     if not isinstance(raw_format, RawFormat):
-        raise TypeError(f"{who}raw_format must be a RawFormat, got {type(raw_format).__name__}")
+        raise TypeError(f"{op}: raw_format must be a RawFormat, got {type(raw_format).__name__}")
+    for stage, why in _STAGE_REFUSALS:
+        if stage not in sees and getattr(raw_format, stage) is not None:
+            raise ValueError(why.format(op=op))
+
+
+def _raw_source(mosaic, raw_format):
+    """The sensor frame the mosaic front-end ops read: checks `mosaic` against `raw_format` (a RawFormat: _raw_stages) and returns the frame as a
+    contiguous (B, 2h, X) tensor on the device -- with raw_format.exposures set, (B, E, 2h, X) or (B, E 2h, X) as its layout says -- its
+    rc_raw_storage and (2h, 2w) of one exposure; of a Quad-Bayer frame (raw_quad), the size of its result."""
     if not isinstance(mosaic, torch.Tensor):
         raise TypeError("mosaic: expected a tensor")
-    if raw_format.quad is not None and not quad:
-        raise ValueError(f"{who}the frame is Quad-Bayer (raw_format.quad is set) and this op reads a Bayer mosaic: run ops.raw_quad first and "
-                         "hand its result on with quad=None (forward_mosaic does both)")
     hw = raw_format.validate(mosaic.shape)
     want = _RAW_TENSOR_DTYPE.get(raw_format.storage)
     if want is None:
@@ -498,33 +516,30 @@ def _raw_source(mosaic, raw_format, who, quad=False):
     return (mosaic[:, 0] if mosaic.dim() == 4 else mosaic), storage, hw
 
 
-def _one_exposure(raw_format, op):
-    """The single-exposure front-end ops refuse a format whose exposures are set, rather than read E frames as one."""
-    if getattr(raw_format, "exposures", None) is not None:
-        raise ValueError(f"{op} reads one exposure: merge first.  The order is ops.raw_defects (per exposure), ops.raw_hdr_merge, "
-                         "ops.raw_calibrate, ops.raw_ingest (forward_mosaic runs all four)")
-    _no_temporal(raw_format, op)
+def _read_in_place(t, noun, op, mosaic, instead):
+    """A device tensor the kernel reads in place when it runs (frame gains, exposure times, the temporal gain): on the mosaic's device and
+    contiguous, or refused -- it is not copied."""
+    if not t.is_cuda or t.device != mosaic.device:
+        raise RuntimeError(f"{op}: the {noun} tensor is on {t.device}, the mosaic on {mosaic.device}; give {instead} or a tensor on the mosaic's device")
+    if not t.is_contiguous():
+        raise ValueError(f"{op}: the {noun} tensor must be contiguous (it is read in place, not copied)")
+    return t
 
 
-def _no_temporal(raw_format, op):
-    """The other front-end ops refuse a format whose temporal filter is set, rather than skip the stage silently."""
-    if getattr(raw_format, "temporal", None) is not None:
-        raise ValueError(f"{op} does not filter: raw_format.temporal is set.  The order is ops.raw_defects, ops.raw_hdr_merge, "
-                         "ops.raw_temporal, ops.raw_calibrate, ops.raw_ingest, each on a format without the stages already run "
-                         "(forward_mosaic runs all five)")
+def _device_table(like, shape, dtype, upload):
+    """A table an op keeps on the device per (table, device): upload(device) -- or, under a FakeTensor trace, its shape only: nothing is
+    built, copied or kept."""
+    if isinstance(like, FakeTensor):
+        return like.new_empty(shape, dtype=dtype)
+    return upload(like.device)
 
 
 def _raw_ingest_fmt(mosaic, dtype, pad_to, black_level, white_level, cond_hw, fmt):
     from .raw_format import CFAS
-    _one_exposure(fmt, "raw_ingest")
-    mosaic, storage, (_, w2) = _raw_source(mosaic, fmt, "")
+    _raw_stages(fmt, "raw_ingest", ())
+    mosaic, storage, (_, w2) = _raw_source(mosaic, fmt)
     if black_level != 0.0 or white_level != 1.0:
         raise ValueError("raw_format carries the black / white levels: leave black_level / white_level at their defaults")
-    if fmt.defects is not None:
-        raise ValueError("raw_ingest does not correct defects: run ops.raw_defects first and ingest its result (forward_mosaic does both)")
-    if fmt.calibration is not None:
-        raise ValueError("raw_ingest does not calibrate: run ops.raw_calibrate first and ingest its float result with levels 0 / 1 "
-                         "(forward_mosaic does both)")
     if dtype is None:
         if fmt.storage in _RAW_STORAGE:
             raise ValueError(f"raw_ingest: give the activation dtype for a {fmt.storage} mosaic")
@@ -544,17 +559,16 @@ def raw_quad(mosaic: torch.Tensor, raw_format, quad=None) -> torch.Tensor:
     them.  Frames holding NaN / Inf are outside the contract."""
     import dataclasses
     from .quad import QuadBayer
-    from .raw_format import CFAS, RawFormat
-    if not isinstance(raw_format, RawFormat):
-        raise TypeError(f"raw_quad: raw_format must be a RawFormat, got {type(raw_format).__name__}")
-    if raw_format.exposures is not None:
+    from .raw_format import CFAS
+    _raw_stages(raw_format, "raw_quad", ("quad", "defects", "exposures", "temporal", "calibration"))
+    if raw_format.exposures is not None:                        # in front of the merge: its own advice
         raise ValueError("raw_quad reads one exposure: pass Exposures(layout='frames') frames as their (B E, H, X) view, with exposures=None "
                          "(forward_mosaic does)")
     quad = raw_format.quad if quad is None else quad
     if not isinstance(quad, QuadBayer):
         raise ValueError(f"raw_quad: quad must be a QuadBayer (or raw_format.quad set), got {type(quad).__name__}")
     fmt = dataclasses.replace(raw_format, quad=quad, defects=None, temporal=None, calibration=None)
-    mosaic, storage, _ = _raw_source(mosaic, fmt, "raw_quad: ", quad=True)
+    mosaic, storage, _ = _raw_source(mosaic, fmt)
     width = fmt.width if fmt.packed else mosaic.shape[-1]
     return _R.raw_quad(mosaic, storage, CFAS[fmt.cfa], int(width), quad.code)
 
@@ -568,18 +582,13 @@ def raw_defects(mosaic: torch.Tensor, raw_format, defects=None):
     synchronised.  Frames holding NaN / Inf are outside the contract."""
     from .defects import Defects
     from .raw_format import CFAS
-    _one_exposure(raw_format, "raw_defects")
-    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format, "raw_defects: ")
+    _raw_stages(raw_format, "raw_defects", ("defects", "calibration"))
+    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format)
     defects = raw_format.defects if defects is None else defects
     if not isinstance(defects, Defects):
         raise TypeError(f"raw_defects: defects must be a Defects (or raw_format.defects set), got {type(defects).__name__}")
     defects.check(h2, w2)
-    words = None
-    if defects.map is not None:
-        if isinstance(mosaic, FakeTensor):                     # a trace: shapes only, nothing is built, copied or kept
-            words = mosaic.new_empty(defects.map.words.shape, dtype=torch.int32)
-        else:
-            words = defects.map.device_words(mosaic.device)
+    words = None if defects.map is None else _device_table(mosaic, defects.map.words.shape, torch.int32, defects.map.device_words)
     out, counts = _R.raw_defects(mosaic, words, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), defects.flags,
                                  list(defects.thresholds()), defects.counts)
     return (out, counts) if defects.counts else out
@@ -596,31 +605,21 @@ def raw_calibrate(mosaic: torch.Tensor, raw_format, calibration=None, dtype: tor
     Frames holding NaN / Inf are outside the contract."""
     from .calibration import Calibration
     from .raw_format import CFAS
-    _one_exposure(raw_format, "raw_calibrate")
-    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format, "raw_calibrate: ")
+    _raw_stages(raw_format, "raw_calibrate", ("calibration",))
+    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format)
     calibration = raw_format.calibration if calibration is None else calibration
     if not isinstance(calibration, Calibration):
         raise TypeError(f"raw_calibrate: calibration must be a Calibration (or raw_format.calibration set), got {type(calibration).__name__}")
-    if raw_format.defects is not None:
-        raise ValueError("raw_calibrate does not correct defects: run ops.raw_defects first and calibrate its result (forward_mosaic does both)")
     calibration.check(h2, w2, mosaic.shape[0])
     if dtype not in _DT:
         raise TypeError(f"raw_calibrate: dtype must be fp32 / bf16 / fp16, got {dtype}")
     gain_map, cell = None, 0
     if calibration.shading is not None:
         cell = calibration.shading.cell
-        if isinstance(mosaic, FakeTensor):                     # a trace: shapes only, nothing is built, copied or kept
-            gain_map = mosaic.new_empty(calibration.shading.gains.shape, dtype=torch.float32)
-        else:
-            gain_map = calibration.shading.device_gains(mosaic.device)
+        gain_map = _device_table(mosaic, calibration.shading.gains.shape, torch.float32, calibration.shading.device_gains)
     frame_gains, host_gains = None, []
     if calibration.device_gains:
-        frame_gains = calibration.gains
-        if not frame_gains.is_cuda or frame_gains.device != mosaic.device:
-            raise RuntimeError(f"raw_calibrate: the gains tensor is on {frame_gains.device}, the mosaic on {mosaic.device}; give four host numbers "
-                               "or a tensor on the mosaic's device")
-        if not frame_gains.is_contiguous():
-            raise ValueError("raw_calibrate: the gains tensor must be contiguous (it is read in place, not copied)")
+        frame_gains = _read_in_place(calibration.gains, "gains", "raw_calibrate", mosaic, "four host numbers")
     elif calibration.gains is not None:
         host_gains = list(calibration.gains)
     curve = calibration.curve
@@ -639,27 +638,17 @@ def raw_hdr_merge(mosaic: torch.Tensor, raw_format, exposures=None) -> torch.Ten
     refused (the merge needs linear samples).  Non-finite samples are outside the contract."""
     import dataclasses
     from .exposures import Exposures
-    from .raw_format import CFAS, RawFormat
-    if not isinstance(raw_format, RawFormat):
-        raise TypeError(f"raw_hdr_merge: raw_format must be a RawFormat, got {type(raw_format).__name__}")
+    from .raw_format import CFAS
+    _raw_stages(raw_format, "raw_hdr_merge", ("exposures", "calibration"))
     exposures = raw_format.exposures if exposures is None else exposures
     if not isinstance(exposures, Exposures):
         raise TypeError(f"raw_hdr_merge: exposures must be an Exposures (or raw_format.exposures set), got {type(exposures).__name__}")
-    if raw_format.defects is not None:
-        raise ValueError("raw_hdr_merge does not correct defects: run ops.raw_defects on each exposure first and merge its result "
-                         "(forward_mosaic does both)")
-    _no_temporal(raw_format, "raw_hdr_merge")
     if raw_format.exposures is not exposures:
         raw_format = dataclasses.replace(raw_format, exposures=exposures)
-    mosaic, storage, (_, w2) = _raw_source(mosaic, raw_format, "raw_hdr_merge: ")
+    mosaic, storage, (_, w2) = _raw_source(mosaic, raw_format)
     times, host_times = None, []
     if exposures.device_times:
-        times = exposures.times
-        if not times.is_cuda or times.device != mosaic.device:
-            raise RuntimeError(f"raw_hdr_merge: the times tensor is on {times.device}, the mosaic on {mosaic.device}; give host numbers or a "
-                               "tensor on the mosaic's device")
-        if not times.is_contiguous():
-            raise ValueError("raw_hdr_merge: the times tensor must be contiguous (it is read in place, not copied)")
+        times = _read_in_place(exposures.times, "times", "raw_hdr_merge", mosaic, "host numbers")
     else:
         host_times = list(exposures.times)
     return _R.raw_hdr_merge(mosaic, times, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), exposures.count,
@@ -675,19 +664,13 @@ def raw_temporal(mosaic: torch.Tensor, raw_format, prev: Optional[torch.Tensor] 
     the call is capturable; a gain tensor is read in place by the kernel; nothing is synchronised.  The Temporal's state is not looked at:
     the caller chains prev / out.  raw_format.defects and raw_format.exposures must be None (run those stages first); a Calibration.curve is
     refused (the noise model needs linear samples).  Non-finite samples or state are outside the contract."""
-    from .raw_format import CFAS, RawFormat
+    from .raw_format import CFAS
     from .temporal import Temporal
-    if not isinstance(raw_format, RawFormat):
-        raise TypeError(f"raw_temporal: raw_format must be a RawFormat, got {type(raw_format).__name__}")
+    _raw_stages(raw_format, "raw_temporal", ("temporal", "calibration"))
     t = raw_format.temporal
     if not isinstance(t, Temporal):
         raise TypeError(f"raw_temporal: raw_format.temporal must be a Temporal, got {type(t).__name__}")
-    if raw_format.exposures is not None:
-        raise ValueError("raw_temporal reads one exposure: merge first.  The order is ops.raw_defects (per exposure), ops.raw_hdr_merge, "
-                         "ops.raw_temporal, ops.raw_calibrate, ops.raw_ingest (forward_mosaic runs all five)")
-    if raw_format.defects is not None:
-        raise ValueError("raw_temporal does not correct defects: run ops.raw_defects first and filter its result (forward_mosaic does both)")
-    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format, "raw_temporal: ")
+    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format)
     shape = (mosaic.shape[0], h2, w2)
 
     def state(x, name):
@@ -713,12 +696,7 @@ def raw_temporal(mosaic: torch.Tensor, raw_format, prev: Optional[torch.Tensor] 
                 raise ValueError("raw_temporal: out must not alias prev (a row's neighbours are read after it is written): swap two buffers")
     gain, host_gain = None, []
     if t.device_gain:
-        gain = t.gain
-        if not gain.is_cuda or gain.device != mosaic.device:
-            raise RuntimeError(f"raw_temporal: the gain tensor is on {gain.device}, the mosaic on {mosaic.device}; give a host number or a "
-                               "tensor on the mosaic's device")
-        if not gain.is_contiguous():
-            raise ValueError("raw_temporal: the gain tensor must be contiguous (it is read in place, not copied)")
+        gain = _read_in_place(t.gain, "gain", "raw_temporal", mosaic, "a host number")
     elif t.gain is not None:
         host_gain = [t.gain]
     _R.raw_temporal(mosaic, prev, gain, out, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), list(t.params()), host_gain)
@@ -821,10 +799,7 @@ def lut3d(y: torch.Tensor, lut, crop_hw: Optional[Tuple[int, int]] = None, out_d
     if not isinstance(lut, Lut3D):
         raise TypeError(f"lut3d: lut must be a Lut3D, got {type(lut).__name__}")
     y, h, w = _planar_source(y, "lut3d", crop_hw, out_dtype)
-    if isinstance(y, FakeTensor):                              # a trace: shapes only, nothing is built, copied or kept
-        table = y.new_empty((lut.size ** 3, 4), dtype=torch.float32)
-    else:
-        table = lut3d_table(lut, y.device)
+    table = _device_table(y, (lut.size ** 3, 4), torch.float32, lambda device: lut3d_table(lut, device))
     return _R.lut3d(y, table, lut.size, h, w, out_dtype)
 
 
@@ -950,10 +925,7 @@ def warp(y: torch.Tensor, warp_or_mesh, size: Optional[Tuple[int, int]] = None, 
             raise ValueError("warp: size belongs to the mesh-tensor form; a Warp carries its own")
         wp.check_source(h, w)
         size, cell, interp, border, fill = wp.size, wp.cell, wp.interp, wp.border, wp.fill
-        if isinstance(y, FakeTensor):                          # a trace: shapes only, nothing is built, copied or kept
-            mesh = y.new_empty((1, *mesh_shape(size, cell), 2), dtype=torch.float32)
-        else:
-            mesh = warp_mesh(wp, y.device)
+        mesh = _device_table(y, (1, *mesh_shape(size, cell), 2), torch.float32, lambda device: warp_mesh(wp, device))
     elif isinstance(warp_or_mesh, torch.Tensor):
         mesh = warp_or_mesh
         if size is None:

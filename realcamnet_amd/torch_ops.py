@@ -124,8 +124,11 @@ def _fmt_alloc(src, dtype, pad_to, storage, cfa, width, black, white, cond_h, co
 
 
 def _raw_source(src, storage, cfa, width, black, white):
-    """The rc_raw_format of the frame src (B, 2h, X) and the tensor to pass for it: src itself, or a copy when a MIPI frame starts mid-dword
-    (a view may; packed lines are read as whole dwords from a 4-byte aligned base, element storages need their own alignment only)."""
+    """How every launch that reads a sensor frame opens: the rc_raw_format of the frame src (B, 2h, X) and the tensor to pass for it, src
+    itself, or a copy when a MIPI frame starts mid-dword (a view may; packed lines are read as whole dwords from a 4-byte aligned base,
+    element storages need their own alignment only)."""
+    if len(black) != 4:
+        raise ValueError(f"realcam: black holds four floats in CFA-position order, got {black!r}")
     if storage in (_lib.RC_RAW_MIPI10, _lib.RC_RAW_MIPI12) and src.data_ptr() % 4:
         src = src.clone()
     return src, _lib.RawFormatDesc(storage=storage, cfa=cfa, line_bytes=src.shape[2] * src.element_size(), width=width,
@@ -289,20 +292,22 @@ def _stats_launch(outs, y, h, w, roi, gy, gx, bits, matrix, dark, clip):
 define("frame_stats(Tensor y, int h, int w, int[] roi, int gy, int gx, int bits, int matrix, int dark, int clip) -> (Tensor, Tensor)",
        _stats_alloc, _stats_launch)
 
-_DEFECT_COUNT_STORAGES = (_lib.RC_RAW_U16, _lib.RC_RAW_U8, _lib.RC_RAW_MIPI10, _lib.RC_RAW_MIPI12)
+def _unpacked_dtype(src, storage):
+    """What a stage that keeps the storage writes (raw_defects, raw_quad's remosaic): uint16 for the count storages, src's dtype for float."""
+    return torch.uint16 if storage in (_lib.RC_RAW_U16, _lib.RC_RAW_U8, _lib.RC_RAW_MIPI10, _lib.RC_RAW_MIPI12) else src.dtype
 
 
 def _defects_alloc(src, map_words, storage, cfa, width, black, flags, thr, want_counts):
     b, h2, _ = src.shape
-    return (src.new_empty((b, h2, width), dtype=torch.uint16 if storage in _DEFECT_COUNT_STORAGES else src.dtype),
+    return (src.new_empty((b, h2, width), dtype=_unpacked_dtype(src, storage)),
             src.new_empty((b, 3), dtype=torch.int64) if want_counts else _none(src))
 
 
 def _defects_launch(outs, src, map_words, storage, cfa, width, black, flags, thr, want_counts):
     out, counts = outs
     b, h2, _ = src.shape
-    if len(black) != 4 or len(thr) != 4:
-        raise ValueError(f"realcam::raw_defects: black and thr hold four floats each, got {black!r} and {thr!r}")
+    if len(thr) != 4:
+        raise ValueError(f"realcam::raw_defects: thr holds four floats, got {thr!r}")
     src, f = _raw_source(src, storage, cfa, width, black, 0.0)
     d = _lib.DefectDesc(flags=flags, hot_abs=thr[0], hot_rel=thr[1], cold_abs=thr[2], cold_rel=thr[3])
     check(lib().rc_raw_defects(src.data_ptr(), C.byref(f), C.byref(d), _p(map_words), 0 if map_words is None else 4 * map_words.shape[1],
@@ -319,9 +324,9 @@ define("raw_defects(Tensor src, Tensor? map_words, int storage, int cfa, int wid
 
 def _calib_launch(out, src, gain_map, frame_gains, storage, cfa, width, black, white, curve_x, curve_y, cell, gains, clip, dtype):
     b, h2, _ = src.shape
-    if len(black) != 4 or len(gains) not in (0, 4) or len(clip) not in (0, 2) or len(curve_x) != len(curve_y) or len(curve_x) > _lib.RC_CALIB_MAX_KNOTS:
-        raise ValueError(f"realcam::raw_calibrate: black holds four floats, gains none or four, clip none or two, the curve at most "
-                         f"{_lib.RC_CALIB_MAX_KNOTS} knots; got {black!r}, {gains!r}, {clip!r}, {curve_x!r}, {curve_y!r}")
+    if len(gains) not in (0, 4) or len(clip) not in (0, 2) or len(curve_x) != len(curve_y) or len(curve_x) > _lib.RC_CALIB_MAX_KNOTS:
+        raise ValueError(f"realcam::raw_calibrate: gains holds none or four floats, clip none or two, the curve at most "
+                         f"{_lib.RC_CALIB_MAX_KNOTS} knots; got {gains!r}, {clip!r}, {curve_x!r}, {curve_y!r}")
     src, f = _raw_source(src, storage, cfa, width, black, white)
     d = _lib.CalibDesc(flags=(_lib.RC_CALIB_GAINS if gains else 0) | (_lib.RC_CALIB_CLIP if clip else 0), knots=len(curve_x), cell=cell)
     for k, (cx, cy) in enumerate(zip(curve_x, curve_y)):
@@ -347,9 +352,9 @@ def _hdr_alloc(src, times, storage, cfa, width, black, exposures, lines, host_ti
 
 
 def _hdr_launch(out, src, times, storage, cfa, width, black, exposures, lines, host_times, knee, motion):
-    if len(black) != 4 or len(knee) != 2 or len(motion) not in (0, 2) or len(host_times) not in (0, exposures) or (times is None) == (not host_times):
-        raise ValueError(f"realcam::raw_hdr_merge: black holds four floats, knee two, motion none or two, the times E host numbers or a tensor; "
-                         f"got {black!r}, {knee!r}, {motion!r}, {host_times!r}")
+    if len(knee) != 2 or len(motion) not in (0, 2) or len(host_times) not in (0, exposures) or (times is None) == (not host_times):
+        raise ValueError(f"realcam::raw_hdr_merge: knee holds two floats, motion none or two, the times E host numbers or a tensor; "
+                         f"got {knee!r}, {motion!r}, {host_times!r}")
     if src.dim() != (3 if lines else 4) or (not lines and src.shape[1] != exposures) or (times is not None and times.shape[1] != exposures):
         raise ValueError(f"realcam::raw_hdr_merge: src must be (B, E, 2h, X), or (B, E 2h, X) for interleaved lines, and times (1 or B, E); got "
                          f"{tuple(src.shape)} for E = {exposures}")
@@ -378,9 +383,9 @@ define("raw_hdr_merge(Tensor src, Tensor? times, int storage, int cfa, int width
        "float[] knee, float[] motion) -> Tensor", _hdr_alloc, _hdr_launch)
 
 def _temporal_launch(ret, src, prev, gain, out, storage, cfa, width, black, params, host_gain):
-    if len(black) != 4 or len(params) != 4 or len(host_gain) not in (0, 1) or (gain is not None and host_gain):
-        raise ValueError(f"realcam::raw_temporal: black holds four floats, params n_abs, n_rel, alpha, ramp, the gain one host number or a tensor; "
-                         f"got {black!r}, {params!r}, {host_gain!r}")
+    if len(params) != 4 or len(host_gain) not in (0, 1) or (gain is not None and host_gain):
+        raise ValueError(f"realcam::raw_temporal: params holds n_abs, n_rel, alpha, ramp, the gain one host number or a tensor; "
+                         f"got {params!r}, {host_gain!r}")
     b, h2, _ = src.shape
     if out.dtype != torch.float32 or tuple(out.shape) != (b, h2, width) or (prev is not None and (prev.dtype != torch.float32 or prev.shape != out.shape)):
         raise ValueError(f"realcam::raw_temporal: prev and out must be ({b}, {h2}, {width}) fp32, got {None if prev is None else tuple(prev.shape)} and {tuple(out.shape)}")
@@ -404,7 +409,7 @@ def _quad_alloc(src, storage, cfa, width, mode):
     b, h, _ = src.shape
     if mode == _lib.RC_QUAD_BIN:
         return src.new_empty((b, h // 2, width // 2), dtype=torch.float32)
-    return src.new_empty((b, h, width), dtype=torch.uint16 if storage in _DEFECT_COUNT_STORAGES else src.dtype)
+    return src.new_empty((b, h, width), dtype=_unpacked_dtype(src, storage))
 
 
 def _quad_launch(out, src, storage, cfa, width, mode):
