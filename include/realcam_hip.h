@@ -178,6 +178,62 @@ size_t rc_yuv_frame_bytes(const rc_out_format* fmt, int h, int w);
  * Odd h / w, a pitch below the row's bytes, overlapping planes, a misaligned d_dst: RC_ERR_INVALID before any launch. */
 int rc_yuv_encode(const void* d_src, int src_dtype, const rc_out_format* fmt, void* d_dst, int batch, int H, int W, int h, int w, void* stream);
 
+/* ---- JPEG out (ABI 15, additive): the same planar result as one baseline JFIF file per frame, coded on the device ------------------------
+ * The one compressed still of the output side: 8-bit baseline sequential DCT, Huffman coded with the typical tables of ITU-T T.81
+ * Annex K.3.3, three components, 4:2:0 or 4:4:4, restart intervals.  Three launches per call and no host sync: every restart interval is
+ * coded by one wave, twice -- once to count its bytes, once, after a scan of the counts, straight to its place in the file. */
+typedef enum rc_jpeg_subsampling { RC_JPEG_420 = 0 /* MCU 16x16: Y00 Y01 Y10 Y11 Cb Cr */, RC_JPEG_444 = 1 /* MCU 8x8: Y Cb Cr */ } rc_jpeg_subsampling;
+
+typedef struct rc_jpeg_desc {
+    int quality;           /* 1 .. 100: the IJG scaling of the Annex K.1 / K.2 tables (rc_jpeg_tables) */
+    int subsampling;       /* rc_jpeg_subsampling */
+    int restart;           /* MCUs per restart interval, 1 .. 65535 (the DRI segment's 16 bits) */
+    int reserved[5];       /* zero */
+} rc_jpeg_desc;
+size_t rc_jpeg_desc_size(void);
+
+/* What a (h, w) frame needs, 1 <= h, w <= 65535 (the SOF0 segment's 16 bits).  hp, wp = h, w rounded up to the MCU. */
+typedef struct rc_jpeg_plan_info {
+    long long header_bytes;    /* SOI .. the end of SOS (rc_jpeg_header) */
+    long long mcu_cols, mcu_rows;
+    long long intervals;       /* ceil(mcu_cols mcu_rows / restart) */
+    long long capacity;        /* the default bytes per frame: header_bytes + 3 hp wp (4:4:4) or 3 hp wp / 2 (4:2:0) + 2 intervals + 2 */
+    long long scratch_bytes;   /* per frame of the batch: 4 per interval */
+} rc_jpeg_plan_info;
+
+/* Host only.  The two 8-bit quantisation tables of `quality` in natural (row-major) order: the Annex K.1 (luma) and K.2 (chroma) tables
+ * scaled by the IJG rule, in integers: s = quality < 50 ? 5000 / quality : 200 - 2 quality; entry = clamp((base s + 50) / 100, 1, 255). */
+int rc_jpeg_tables(int quality, uint8_t* luma, uint8_t* chroma);
+/* Host only.  RC_ERR_INVALID for a description or a size outside the limits above. */
+int rc_jpeg_plan(const rc_jpeg_desc* desc, int h, int w, rc_jpeg_plan_info* plan);
+/* Host only.  The file's bytes from SOI to the end of SOS into buf[0 .. cap), *len = header_bytes: JFIF APP0 (version 1.01, aspect 1:1,
+ * no thumbnail); one DQT with both 8-bit tables (0 luma, 1 chroma) in zigzag order; SOF0 (8 bit, h, w, Y id 1 sampling 2x2 or 1x1 table 0,
+ * Cb id 2 and Cr id 3 sampling 1x1 table 1); one DHT with the four Annex K.3.3 tables (DC 0, DC 1, AC 0, AC 1); DRI (restart); SOS. */
+int rc_jpeg_header(const rc_jpeg_desc* desc, int h, int w, uint8_t* buf, size_t cap, size_t* len);
+
+/* src (B,3,H,W) RC_F32 / RC_BF16 / RC_F16 planar R,G,B, cropped to (h,w); d_header: rc_jpeg_header(desc, h, w) on the device (the
+ * quantiser reads the very tables the decoder will); d_scratch: batch * scratch_bytes, 4-byte aligned, no state between calls; d_dst:
+ * batch * capacity bytes, frame b at b * capacity; d_lengths (batch) int64: the bytes each complete file NEEDS, whether or not they fit.
+ * Frame b is d_dst[b capacity .. b capacity + lengths[b]) when lengths[b] <= capacity; otherwise its `capacity` bytes are unspecified.
+ * Nothing outside a frame's `capacity` bytes is written, whatever the data.  The stream, bit for bit:
+ *   1. samples: pixel (y, x) of the padded MCU grid is the crop's pixel (min(y, h-1), min(x, w-1)); r,g,b, Y', Cb, Cr exactly as
+ *      rc_yuv_encode forms them for RC_MATRIX_BT601; codes as its RC_RANGE_FULL: Y clamp(rint(255 Y), 0, 255), chroma
+ *      clamp(rint(255 c + 128), 0, 255) -- at 4:4:4 per pixel, at 4:2:0 of ((c00 + c01) + (c10 + c11)) 0.25 (RC_SITING_CENTER).  For even
+ *      h, w the codes are the planes of rc_yuv_encode's I420 / BT601 / FULL / CENTER surface.
+ *   2. DCT per 8x8 block, exact in int32: s = code - 128;  M[u][x] = rint(2^14 a(u) cos((2x+1) u pi / 16)), a(0) = sqrt(1/8), a(u) = 1/2;
+ *      R[y][u] = sum_x M[u][x] s[y][x];  R' = (R + 2^8) >> 9 (arithmetic);  F[v][u] = sum_y M[v][y] R'[y][u]: the DCT times 2^19.
+ *      |R'| <= 11586, |F| <= 536941584 < 2^30.
+ *   3. quantise with the table entry Q of the coefficient: q = sign(F) ((|F| + (Q << 18)) div (Q << 19)).
+ *   4. baseline Huffman, the K.3.3 tables; blocks in MCU order, MCUs in raster order; the DC predictor per component, 0 at the start of each
+ *      interval; ZRL for every 16 zeros in front of a non-zero coefficient, EOB unless coefficient 63 is non-zero; bits MSB first; each
+ *      interval padded with 1-bits to a byte; 0xFF -> 0xFF 0x00; RSTm, m = i mod 8, between intervals i and i + 1; EOI. */
+int rc_jpeg_encode(const void* d_src, int src_dtype, const rc_jpeg_desc* desc, const void* d_header, void* d_scratch, void* d_dst, void* d_lengths,
+                   int batch, int H, int W, int h, int w, long long capacity, void* stream);
+/* Measurement only (tools/jpeg_bench.py times the launches one by one): which of rc_jpeg_encode's three launches run from now on -- bit 0 the
+ * counting pass, bit 1 the scan, bit 2 the writing pass.  7, the default, is the only value that gives files; with another value the frames'
+ * bytes are unspecified, and still nothing outside them is written. */
+int rc_debug_jpeg_passes(int mask);
+
 /* ---- scaled and cropped renditions (ABI 15, additive): a window of the same planar result, downscaled, between the tail and the encoders --
  * One network pass, any number of outputs: each is a window (ROI) of the cropped result, a size and -- through rc_rgb_encode /
  * rc_yuv_encode on what this stage returns -- a format.  The stage is separable and only ever downscales: per axis 1 <= ROI / out <= 8. */

@@ -17,6 +17,7 @@ from . import networks as N
 from . import ops
 from .groupmix import GMA_Block, SUPPORTED_DTYPES
 from ._lib import RC_OUT_NCHW, RC_OUT_PIXEL_SHUFFLE2
+from .jpeg import Jpeg
 from .out_format import OutFormat
 from .stats import Stats
 from .resize import Output
@@ -385,24 +386,27 @@ _OUT_BITS = {None: None, "rgb8": 8, "rgb16": 16}
 
 
 def _out_bits(out_format):
-    """What _encode does with the result: None (as it is), 8 / 16 (interleaved RGB), the OutFormat itself (an encoder surface) or the Stats
-    itself (frame statistics)."""
-    if isinstance(out_format, (OutFormat, Stats)):
+    """What _encode does with the result: None (as it is), 8 / 16 (interleaved RGB), the OutFormat itself (an encoder surface), the Jpeg itself (compressed
+    stills) or the Stats itself (frame statistics)."""
+    if isinstance(out_format, (OutFormat, Jpeg, Stats)):
         return out_format
     if out_format is not None and not isinstance(out_format, str):
-        raise TypeError(f"out_format must be None, 'rgb8', 'rgb16', an OutFormat or a Stats, got {type(out_format).__name__}")
+        raise TypeError(f"out_format must be None, 'rgb8', 'rgb16', an OutFormat, a Jpeg or a Stats, got {type(out_format).__name__}")
     if out_format not in _OUT_BITS:
-        raise ValueError(f"out_format must be None, 'rgb8', 'rgb16', an OutFormat or a Stats, got {out_format!r}")
+        raise ValueError(f"out_format must be None, 'rgb8', 'rgb16', an OutFormat, a Jpeg or a Stats, got {out_format!r}")
     return _OUT_BITS[out_format]
 
 
 def _encode(y, bits):
     """out_format: the planar float sRGB (B,3,2h,2w) as it is, interleaved (B,2h,2w,3) uint8 / uint16 (rc_rgb_encode), a YuvFrames
-    holding one Y'CbCr 4:2:0 surface per frame (rc_yuv_encode), or a FrameStats (rc_frame_stats)."""
+    holding one Y'CbCr 4:2:0 surface per frame (rc_yuv_encode), a JpegFrames holding one JFIF file per frame (rc_jpeg_encode), or a
+    FrameStats (rc_frame_stats)."""
     if bits is None:
         return y
     if isinstance(bits, Stats):
         return ops.frame_stats(y, bits)
+    if isinstance(bits, Jpeg):
+        return ops.jpeg_encode(y, bits)
     return ops.yuv_encode(y, bits) if isinstance(bits, OutFormat) else ops.rgb_encode(y, bits)
 
 
@@ -411,6 +415,8 @@ def _plan_outputs(outputs, out_format, hw):
     if outputs is None:
         if isinstance(out_format, Stats):
             out_format.check(*hw)                         # the refusals that depend on the frame, as Output.plan raises them
+        if isinstance(out_format, Jpeg):
+            out_format.plan(*hw)
         return None
     if out_format is not None:
         raise ValueError("give either out_format or outputs, not both (an Output carries its own format)")
@@ -553,7 +559,8 @@ class _DwtUNet(nn.Module):
         raw_format (a RawFormat): the sensor frame's CFA phase, storage (MIPI RAW10 / RAW12 lines: (B,[1,]2h,line_bytes) uint8) and
         per-position levels.  out_format "rgb8" / "rgb16": the result as interleaved (B,2h,2w,3) uint8 / uint16; an OutFormat: a YuvFrames
         (one NV12 / P010 / I420 encoder surface per frame, and views of its planes); a Stats: a FrameStats (the histograms and the 3A zone
-        grid of the result, ops.frame_stats, in place of a picture).
+        grid of the result, ops.frame_stats, in place of a picture); a Jpeg: a JpegFrames (one baseline JFIF file per frame, coded on the
+        device, ops.jpeg_encode).
         outputs [Output(format, resize, look, warp), ...] instead of out_format: one network pass, then per Output, in this order, an optional
         geometric correction (a Warp: ops.warp, fp32 out, whose size is the frame the next stages see), an optional scaled / cropped
         rendition (ops.resize, fp32) and an optional colour look (a Lut3D: ops.lut3d, fp32) in its own format; returns the list in the

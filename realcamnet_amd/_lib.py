@@ -24,6 +24,7 @@ RC_YUV_NV12, RC_YUV_P010, RC_YUV_I420 = 0, 1, 2
 RC_MATRIX_BT601, RC_MATRIX_BT709, RC_MATRIX_BT2020 = 0, 1, 2
 RC_RANGE_LIMITED, RC_RANGE_FULL = 0, 1
 RC_SITING_LEFT, RC_SITING_CENTER = 0, 1
+RC_JPEG_420, RC_JPEG_444 = 0, 1
 RC_FILTER_AREA, RC_FILTER_BILINEAR = 0, 1
 RC_RESIZE_MAX_TAPS, RC_RESIZE_MAX_RATIO = 20, 8
 RC_LUT3D_MIN_SIZE, RC_LUT3D_MAX_SIZE = 2, 65
@@ -88,6 +89,17 @@ class OutFormatDesc(C.Structure):
         ("layout", C.c_int32), ("matrix", C.c_int32), ("range", C.c_int32), ("siting", C.c_int32),
         ("pitch", C.c_int32), ("rows", C.c_int32), ("chroma_offset", C.c_int32 * 2), ("reserved", C.c_int32 * 4),
     ]
+
+
+class JpegDesc(C.Structure):
+    """Mirror of `struct rc_jpeg_desc`."""
+    _fields_ = [("quality", C.c_int32), ("subsampling", C.c_int32), ("restart", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class JpegPlanInfo(C.Structure):
+    """Mirror of `struct rc_jpeg_plan_info`."""
+    _fields_ = [("header_bytes", C.c_longlong), ("mcu_cols", C.c_longlong), ("mcu_rows", C.c_longlong), ("intervals", C.c_longlong),
+                ("capacity", C.c_longlong), ("scratch_bytes", C.c_longlong)]
 
 
 class StatsDesc(C.Structure):
@@ -168,6 +180,12 @@ _SIGS = {
     "rc_out_format_size": (_SZ, []),
     "rc_yuv_frame_bytes": (_SZ, [C.POINTER(OutFormatDesc), _I, _I]),
     "rc_yuv_encode": (C.c_int, [_P, _I, C.POINTER(OutFormatDesc), _P, _I, _I, _I, _I, _I, _P]),
+    "rc_jpeg_desc_size": (_SZ, []),
+    "rc_jpeg_tables": (C.c_int, [_I, _P, _P]),
+    "rc_jpeg_plan": (C.c_int, [C.POINTER(JpegDesc), _I, _I, C.POINTER(JpegPlanInfo)]),
+    "rc_jpeg_header": (C.c_int, [C.POINTER(JpegDesc), _I, _I, _P, _SZ, C.POINTER(_SZ)]),
+    "rc_jpeg_encode": (C.c_int, [_P, _I, C.POINTER(JpegDesc), _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_longlong, _P]),
+    "rc_debug_jpeg_passes": (C.c_int, [_I]),
     "rc_resize_taps": (C.c_int, [_I, _I, _I, _I, _P, _P, C.POINTER(C.c_int)]),
     "rc_resize": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "rc_lut3d": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -7,7 +7,7 @@
 // pitch / height padding write it as zero in the same launch.  Arithmetic: fp32, every product and every sum rounded on its own in
 // the order the header states (__fmul_rn / __fadd_rn: no contraction whatever the compile flags say), so the vector path, the
 // element path and a plain elementwise restatement give the same bits.
-#include "rgb_strip.hpp"
+#include "ycc_code.hpp"
 
 namespace rc {
 
@@ -28,18 +28,7 @@ struct YuvArgs {
     float ys, yo, ylo, yhi, cs, co, clo, chi;
 };
 
-__device__ __forceinline__ uint32_t code(float v, float s, float o, float lo, float hi) {
-    float q = rintf(__fadd_rn(__fmul_rn(v, s), o));             // round half to even
-    q = q < lo ? lo : (q > hi ? hi : q);
-    return (uint32_t)q;
-}
-
-__device__ __forceinline__ void ycc(const YuvArgs& a, float r, float g, float b, float& y, float& cb, float& cr) {
-    r = rgb_unit(r); g = rgb_unit(g); b = rgb_unit(b);
-    y = rgb_luma(a.c.k, r, g, b);
-    cb = __fmul_rn(__fsub_rn(b, y), a.c.sb);
-    cr = __fmul_rn(__fsub_rn(r, y), a.c.sr);
-}
+__device__ __forceinline__ void ycc(const YuvArgs& a, float r, float g, float b, float& y, float& cb, float& cr) { ycc(a.c, r, g, b, y, cb, cr); }
 
 // P codes of TO into the four dwords of a strip.
 template <typename TO>

@@ -746,6 +746,36 @@ def yuv_encode(y: torch.Tensor, fmt, crop_hw: Optional[Tuple[int, int]] = None):
     return YuvFrames(buf, tuple(views))
 
 
+class _JpegHeaders:
+    """The owner of the JPEG headers' entries in the derived-value cache (`derived` keeps its values on an object)."""
+
+
+_JPEG_HEADERS = _JpegHeaders()
+
+
+def jpeg_header(fmt, h: int, w: int, device):
+    """rc_jpeg_header(fmt, h, w) as a uint8 tensor on `device`: written on the host and copied once per (Jpeg, h, w, device), then kept through
+    `derived` -- a warmed-up ops.jpeg_encode makes no host-to-device copy."""
+    import numpy as np
+    device = torch.device(device)
+    key = (fmt.quality, fmt.subsampling, fmt.restart, int(h), int(w), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    return derived(_JPEG_HEADERS, ("jpeg_header",) + key, (), lambda: torch.from_numpy(np.frombuffer(fmt.header(int(h), int(w)), dtype=np.uint8).copy()).to(device))
+
+
+def jpeg_encode(y: torch.Tensor, fmt, crop_hw: Optional[Tuple[int, int]] = None):
+    """Planar float result (B,3,H,W), cropped to crop_hw (any size: padded to whole MCUs by repeating the last row and column), -> a
+    JpegFrames: one baseline JFIF file per frame, coded on the device (rc_jpeg_encode; the stream is fixed bit for bit in
+    include/realcam_hip.h).  Three launches, no host sync, no device state: `lengths` stays on the device until JpegFrames.tobytes / files."""
+    from .jpeg import SUBSAMPLINGS, Jpeg, JpegFrames
+    if not isinstance(fmt, Jpeg):
+        raise TypeError(f"jpeg_encode: fmt must be a Jpeg, got {type(fmt).__name__}")
+    y, h, w = _planar_source(y, "jpeg_encode", crop_hw, frames=False)
+    plan = fmt.plan(h, w)
+    header = _device_table(y, (plan.header_bytes,), torch.uint8, lambda device: jpeg_header(fmt, h, w, device))
+    buf, lengths = _R.jpeg_encode(y, header, fmt.quality, SUBSAMPLINGS[fmt.subsampling], fmt.restart, plan.capacity, h, w)
+    return JpegFrames(buf, lengths, fmt, (h, w))
+
+
 _RESIZE_TABLES = {}      # (Resize, frame h, frame w, device) -> the four device tables of rc_resize_taps
 
 

@@ -11,6 +11,7 @@ from typing import Optional, Tuple
 
 from . import _lib
 from .look import Lut3D
+from .jpeg import Jpeg
 from .out_format import OutFormat
 from .sharpen import Sharpen
 from .stats import Stats
@@ -101,8 +102,8 @@ class Output:
     """One entry of forward_mosaic(outputs=[...]): an optional Warp of the float result, an optional Resize, an optional ToneMap, an
     optional colour look, an optional Sharpen, then its format.
 
-    format  None (the planar float tensor), "rgb8" / "rgb16" (interleaved uint8 / uint16), an OutFormat (a YuvFrames) or a Stats (a
-            FrameStats: the statistics of the frame after this output's own warp / resize / look, in place of a picture).
+    format  None (the planar float tensor), "rgb8" / "rgb16" (interleaved uint8 / uint16), an OutFormat (a YuvFrames), a Jpeg (a JpegFrames:
+            any size, the 4:2:0 evenness rule below is the encoder surfaces' alone) or a Stats (a FrameStats: the statistics of the frame after this output's own warp / resize / look, in place of a picture).
     resize  None (the result's own size) or a Resize.
     look    None or a Lut3D, applied after the resize and before the encoder (ops.lut3d; with format None the looked tensor is fp32).
     warp    None or a Warp, applied first (ops.warp, fp32): the resize's window and the format then see a frame of warp.size.
@@ -124,10 +125,10 @@ class Output:
 
     def __post_init__(self, tone=None):
         f = self.format
-        if f is not None and not isinstance(f, (str, OutFormat, Stats)):
-            raise TypeError(f"Output.format must be None, 'rgb8', 'rgb16', an OutFormat or a Stats, got {type(f).__name__}")
+        if f is not None and not isinstance(f, (str, OutFormat, Jpeg, Stats)):
+            raise TypeError(f"Output.format must be None, 'rgb8', 'rgb16', an OutFormat, a Jpeg or a Stats, got {type(f).__name__}")
         if isinstance(f, str) and f not in ("rgb8", "rgb16"):
-            raise ValueError(f"Output.format must be None, 'rgb8', 'rgb16', an OutFormat or a Stats, got {f!r}")
+            raise ValueError(f"Output.format must be None, 'rgb8', 'rgb16', an OutFormat, a Jpeg or a Stats, got {f!r}")
         if self.resize is not None and not isinstance(self.resize, Resize):
             raise TypeError(f"Output.resize must be None or a Resize, got {type(self.resize).__name__}")
         if self.look is not None and not isinstance(self.look, Lut3D):
@@ -168,6 +169,8 @@ class Output:
             self.tone.check(h, w)
         if isinstance(self.format, OutFormat):
             self.format.plane_layout(h, w)
+        if isinstance(self.format, Jpeg):
+            self.format.plan(h, w)
         if isinstance(self.format, Stats):
             self.format.check(h, w)
         return h, w

@@ -174,6 +174,28 @@ def _yuv_launch(out, y, layout, matrix, range_, siting, pitch, rows, h, w):
 # matrix / range / siting: the rc_yuv_* enums; pitch in bytes, rows = allocated Y rows
 define("yuv_encode(Tensor y, int layout, int matrix, int vrange, int siting, int pitch, int rows, int h, int w) -> Tensor", _yuv_alloc, _yuv_launch)
 
+def _jpeg_alloc(y, header, quality, subsampling, restart, capacity, h, w):
+    return y.new_empty((y.shape[0], capacity), dtype=torch.uint8), y.new_empty((y.shape[0],), dtype=torch.int64)
+
+
+def _jpeg_launch(outs, y, header, quality, subsampling, restart, capacity, h, w):
+    buf, lengths = outs
+    d = _lib.JpegDesc(quality=quality, subsampling=subsampling, restart=restart)
+    p = _lib.JpegPlanInfo()
+    check(lib().rc_jpeg_plan(C.byref(d), h, w, C.byref(p)), "rc_jpeg_plan")
+    if header.dtype != torch.uint8 or header.device != y.device or not header.is_contiguous() or header.numel() != p.header_bytes:
+        raise ValueError(f"realcam::jpeg_encode: the header must be a contiguous uint8 tensor of {p.header_bytes} bytes on {y.device}")
+    scratch = y.new_empty((y.shape[0], p.scratch_bytes // 4), dtype=torch.int32)       # the intervals' byte counts, then offsets: nothing outlives the call
+    check(lib().rc_jpeg_encode(y.data_ptr(), _dt(y), C.byref(d), header.data_ptr(), scratch.data_ptr(), buf.data_ptr(), lengths.data_ptr(), y.shape[0],
+                               y.shape[2], y.shape[3], h, w, capacity, _stream()), "rc_jpeg_encode")
+
+
+# y (B,3,H,W) planar sRGB cropped to (h,w) -> (B, capacity) uint8, one JFIF file per frame, and (B,) int64, the bytes each file needs; header:
+# rc_jpeg_header's bytes on the device; quality / subsampling / restart: the fields of rc_jpeg_desc
+define("jpeg_encode(Tensor y, Tensor header, int quality, int subsampling, int restart, int capacity, int h, int w) -> (Tensor, Tensor)",
+       _jpeg_alloc, _jpeg_launch)
+
+
 def _resize_launch(out, y, first_y, wy, first_x, wx, dtype):
     for name, t, dt, n in (("first_y", first_y, torch.int32, out.shape[2]), ("wy", wy, torch.float32, out.shape[2]),
                            ("first_x", first_x, torch.int32, out.shape[3]), ("wx", wx, torch.float32, out.shape[3])):
