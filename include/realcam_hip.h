@@ -473,6 +473,55 @@ size_t rc_stats_desc_size(void);
 int rc_frame_stats(const void* d_src, int src_dtype, const rc_stats_desc* desc, long long* d_hist, long long* d_zones,
                    int batch, int H, int W, int h, int w, void* stream);
 
+/* ---- motion estimation (ABI 15, additive): hierarchical block matching on the luma code of the same planar result -----------------------
+ * Replaces: copying frames to the host, or per candidate a shifted abs difference and a pooling pass in torch, each reading the frame
+ * again.  What rc_warp's per-frame mesh (stabilisation), a scene-cut detector, a motion mask and an encoder hint read.  Two entries: the
+ * luma pyramid of a frame (one launch) and the full search of one pyramid level of two frames (one launch per level).  Stateless and
+ * capturable; no device buffer of their own. */
+#define RC_MOTION_MAX_LEVELS 4
+#define RC_MOTION_MAX_RANGE 8
+
+/* src (B,3,H,W) RC_F32 / RC_BF16 / RC_F16 planar R,G,B, cropped to (h,w).  d_levels: a HOST array of `levels` (1 .. 4) device pointers;
+ * level k is (B, h >> k, w >> k) uint8, contiguous; h >> (levels-1) and w >> (levels-1) must be >= 1.
+ *   level 0      qY of rc_frame_stats steps 1 - 3 at bits = 8, exactly: NaN -> 0, clamp to [0,1], Y = ((Kr r) + (Kg g)) + (Kb b) with every
+ *                product and sum rounded on its own, clamp(rint(255 Y), 0, 255) with half to even (the Y plane of a full-range NV12
+ *                surface of the same matrix).
+ *   level k+1    pixel (x, y) = (a + b + c + d + 2) >> 2 over level k's pixels (2x .. 2x+1, 2y .. 2y+1), which always exist
+ *                (2 (n >> 1) <= n); a trailing odd row or column of level k feeds nothing.
+ * One launch reads every source sample once and writes every element of every level.
+ * Null pointers (a level's included), a bad dtype or matrix, levels outside 1 .. 4, an empty coarsest level, h > H or w > W, a misaligned
+ * source, a source plane of 2^29 samples or more, more than 65535 frames: RC_ERR_INVALID before any launch. */
+int rc_motion_pyramid(const void* d_src, int src_dtype, int matrix, int levels, void* const* d_levels, int batch, int H, int W, int h, int w,
+                      void* stream);
+
+typedef struct rc_motion_desc {
+    int block;             /* 8, 16 or 32: a matching block is block x block pixels */
+    int range;             /* R, 0 .. 8: offsets -R .. R per axis around the predictor */
+    int pred_shift;        /* s, 0 or 1: the predictor grid is of the same level (0) or of the next coarser one (1) */
+    int reserved[5];       /* zero */
+} rc_motion_desc;
+size_t rc_motion_desc_size(void);
+
+/* cur, ref (B,hs,ws) uint8, contiguous: one pyramid level of two frames.  by = hs / block, bx = ws / block (floored, both >= 1); block
+ * (j, i) covers rows j block .. and columns i block ..; pixels right of or under the last whole block belong to no block.
+ * d_out (B,by,bx,4) int32, 16-byte aligned.  d_pred: null (the predictor is 0), or (B,pred_by,pred_bx,4) int32, 16-byte aligned -- a
+ * coarser (s = 1) or equal (s = 0) level's output.  Per block, all in integers:
+ *   1. predictor  (px, py) = slots 0 and 1 of node (min(j >> s, pred_by-1), min(i >> s, pred_bx-1)), each clamped to [-32768, 32767], then
+ *                 shifted left by s.  Device data is never trusted.
+ *   2. cost       for every offset (ox, oy) in [-R, R]^2, dx = px + ox, dy = py + oy:
+ *                 cost = sum over the block's pixels (x, y) of |cur[y][x] - ref[clamp(y+dy, 0, hs-1)][clamp(x+dx, 0, ws-1)]|.
+ *                 Every index is clamped: no predictor makes the kernel read outside its buffers.  cost <= 32 * 32 * 255 = 261120.
+ *   3. winner     the offset with the lexicographically smallest key (cost, |oy| + |ox|, oy, ox): a flat frame returns its predictor.
+ *   4. texture    sum of |c[y][x] - c[y][x+1]| over the block's horizontal neighbour pairs plus sum of |c[y][x] - c[y+1][x]| over its
+ *                 vertical pairs, c = cur; both pixels of a pair lie inside the block.
+ *   5. out        (dx, dy, cost, texture) of the winner.
+ * Integer arithmetic throughout: the order of summation is free, the result bit-exact and the same from run to run.  Every element of
+ * d_out is written.  One launch.
+ * Null or misaligned pointers, a bad block, range or pred_shift, non-zero reserved, by or bx < 1, pred_by or pred_bx < 1 with a predictor,
+ * hs ws >= 2^29, more than 65535 frames: RC_ERR_INVALID before any launch. */
+int rc_motion_search(const uint8_t* d_cur, const uint8_t* d_ref, const rc_motion_desc* desc, const int* d_pred, int pred_by, int pred_bx,
+                     int* d_out, int batch, int hs, int ws, void* stream);
+
 /* ---- defective-pixel correction (ABI 15, additive): the first box of the input side, on the mosaic itself, before the ingest ------------
  * Replaces: unpacking the RAW10 / RAW12 lines into a tensor, eight shifted fp32 planes, masked min / max / direction selects -- a dozen
  * full-frame passes.  Here one launch over the bytes the ingest reads anyway; the one stage that is a stencil. */

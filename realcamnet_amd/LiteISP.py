@@ -20,6 +20,7 @@ from ._lib import RC_OUT_NCHW, RC_OUT_PIXEL_SHUFFLE2
 from .jpeg import Jpeg
 from .out_format import OutFormat
 from .stats import Stats
+from .motion import Motion
 from .resize import Output
 
 
@@ -387,22 +388,24 @@ _OUT_BITS = {None: None, "rgb8": 8, "rgb16": 16}
 
 def _out_bits(out_format):
     """What _encode does with the result: None (as it is), 8 / 16 (interleaved RGB), the OutFormat itself (an encoder surface), the Jpeg itself (compressed
-    stills) or the Stats itself (frame statistics)."""
-    if isinstance(out_format, (OutFormat, Jpeg, Stats)):
+    stills), the Stats itself (frame statistics) or the Motion itself (motion vectors)."""
+    if isinstance(out_format, (OutFormat, Jpeg, Stats, Motion)):
         return out_format
     if out_format is not None and not isinstance(out_format, str):
-        raise TypeError(f"out_format must be None, 'rgb8', 'rgb16', an OutFormat, a Jpeg or a Stats, got {type(out_format).__name__}")
+        raise TypeError(f"out_format must be None, 'rgb8', 'rgb16', an OutFormat, a Jpeg, a Stats or a Motion, got {type(out_format).__name__}")
     if out_format not in _OUT_BITS:
-        raise ValueError(f"out_format must be None, 'rgb8', 'rgb16', an OutFormat, a Jpeg or a Stats, got {out_format!r}")
+        raise ValueError(f"out_format must be None, 'rgb8', 'rgb16', an OutFormat, a Jpeg, a Stats or a Motion, got {out_format!r}")
     return _OUT_BITS[out_format]
 
 
 def _encode(y, bits):
     """out_format: the planar float sRGB (B,3,2h,2w) as it is, interleaved (B,2h,2w,3) uint8 / uint16 (rc_rgb_encode), a YuvFrames
-    holding one Y'CbCr 4:2:0 surface per frame (rc_yuv_encode), a JpegFrames holding one JFIF file per frame (rc_jpeg_encode), or a
-    FrameStats (rc_frame_stats)."""
+    holding one Y'CbCr 4:2:0 surface per frame (rc_yuv_encode), a JpegFrames holding one JFIF file per frame (rc_jpeg_encode), a
+    FrameStats (rc_frame_stats) or a MotionField (_motion)."""
     if bits is None:
         return y
+    if isinstance(bits, Motion):
+        return _motion(y, bits)
     if isinstance(bits, Stats):
         return ops.frame_stats(y, bits)
     if isinstance(bits, Jpeg):
@@ -410,9 +413,41 @@ def _encode(y, bits):
     return ops.yuv_encode(y, bits) if isinstance(bits, OutFormat) else ops.rgb_encode(y, bits)
 
 
+def _motion(y, motion):
+    """A Motion as a format: the luma pyramid of the frame (ops.motion_pyramid, one launch) is estimated (ops.motion_estimate, one launch
+    per level) against the pyramid the Motion's state holds from the last call, and becomes the state: two sets of buffers that swap from
+    call to call.  With no state, an empty one, or one of another shape or device, the frame is estimated against itself: zero vectors,
+    zero cost, the real texture."""
+    st = motion.state
+    if st is None:
+        cur = ops.motion_pyramid(y, motion.levels, motion.matrix)
+        return ops.motion_estimate(cur, cur, motion)
+    shapes = [tuple(s) for s in motion.level_shapes(y.shape[0], y.shape[2], y.shape[3])]
+    prev = st.levels if st.matches(shapes, y.device) else None
+    out = st._spare
+    if out is None or out is prev or not st._fits(out, shapes, y.device):
+        out = None
+    cur = ops.motion_pyramid(y, motion.levels, motion.matrix, out=out)
+    field = ops.motion_estimate(cur, cur if prev is None else prev, motion)
+    st.levels, st._spare = cur, prev
+    return field
+
+
+def _motion_check(motion, hw):
+    """What forward_mosaic asks of a Motion format before any stage runs."""
+    if hw is not None:
+        motion.check(*hw)
+    if motion.state is not None and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("forward_mosaic with a Motion that has a state cannot be captured: it swaps its pyramid buffers between calls and a "
+                           "graph would replay one direction of the swap forever.  Capture ops.motion_pyramid(y, levels, out=) and "
+                           "ops.motion_estimate(cur_levels, ref_levels, motion) on explicit buffers instead")
+
+
 def _plan_outputs(outputs, out_format, hw):
     """forward_mosaic(outputs=[Output, ...]) checked before any launch: None, or the tuple of Outputs for an (h, w) result."""
     if outputs is None:
+        if isinstance(out_format, Motion):
+            _motion_check(out_format, hw)
         if isinstance(out_format, Stats):
             out_format.check(*hw)                         # the refusals that depend on the frame, as Output.plan raises them
         if isinstance(out_format, Jpeg):
@@ -426,6 +461,8 @@ def _plan_outputs(outputs, out_format, hw):
         if not isinstance(o, Output):
             raise TypeError(f"outputs must be a list of Output, got an entry of type {type(o).__name__}")
         o.plan(*hw)
+        if isinstance(o.format, Motion):
+            _motion_check(o.format, None)                 # plan has checked the frame this output's stages leave
     return tuple(outputs)
 
 
@@ -560,7 +597,8 @@ class _DwtUNet(nn.Module):
         per-position levels.  out_format "rgb8" / "rgb16": the result as interleaved (B,2h,2w,3) uint8 / uint16; an OutFormat: a YuvFrames
         (one NV12 / P010 / I420 encoder surface per frame, and views of its planes); a Stats: a FrameStats (the histograms and the 3A zone
         grid of the result, ops.frame_stats, in place of a picture); a Jpeg: a JpegFrames (one baseline JFIF file per frame, coded on the
-        device, ops.jpeg_encode).
+        device, ops.jpeg_encode); a Motion: a MotionField (the block motion vectors of the result against the previous call's result, kept in
+        the Motion's state; ops.motion_pyramid and ops.motion_estimate, in place of a picture).
         outputs [Output(format, resize, look, warp), ...] instead of out_format: one network pass, then per Output, in this order, an optional
         geometric correction (a Warp: ops.warp, fp32 out, whose size is the frame the next stages see), an optional scaled / cropped
         rendition (ops.resize, fp32) and an optional colour look (a Lut3D: ops.lut3d, fp32) in its own format; returns the list in the

@@ -19,6 +19,7 @@ from .jpeg import Jpeg, JpegFrames  # noqa: F401
 from .look import Lut3D  # noqa: F401
 from .warp import Warp  # noqa: F401
 from .stats import FrameStats, Stats  # noqa: F401
+from .motion import Motion, MotionField, MotionState, Stabilizer  # noqa: F401
 from .resize import Output, Resize  # noqa: F401
 from .sharpen import Sharpen  # noqa: F401
 from .tone import ToneMap  # noqa: F401
@@ -30,4 +31,4 @@ from .quad import QuadBayer  # noqa: F401
 
 __all__ = ["networks", "LiteISP", "groupmix", "tcm", "raw2bit", "LiteISPNet", "LiteISPNet_GFM_LSC", "LiteISPNet_GFM_LSC_GMA", "LiteISPNet_LSC",
            "LiteISPNet_GFM", "LiteISPNet_GFMresize", "ISPUNet_GFM_LSC", "ISPUNet_GFM", "ISPUNet_GFM_LFM", "ISPUNet_LSC", "ResUNet", "ISPUNet_GFM_crop", "ISPUNet_GFM_LSC1",
-           "ISPUNet_GFM_LSC_noskip", "GMA_Block", "graphs", "GraphedCall", "RawFormat", "OutFormat", "YuvFrames", "Jpeg", "JpegFrames", "Resize", "Output", "Lut3D", "Warp", "Stats", "FrameStats", "DefectMap", "Defects", "Calibration", "GainMap", "Pwl", "Exposures", "Temporal", "TemporalState", "Sharpen", "ToneMap", "QuadBayer"]
+           "ISPUNet_GFM_LSC_noskip", "GMA_Block", "graphs", "GraphedCall", "RawFormat", "OutFormat", "YuvFrames", "Jpeg", "JpegFrames", "Resize", "Output", "Lut3D", "Warp", "Stats", "FrameStats", "Motion", "MotionField", "MotionState", "Stabilizer", "DefectMap", "Defects", "Calibration", "GainMap", "Pwl", "Exposures", "Temporal", "TemporalState", "Sharpen", "ToneMap", "QuadBayer"]

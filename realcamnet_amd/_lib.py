@@ -32,6 +32,7 @@ RC_WARP_BILINEAR, RC_WARP_BICUBIC = 0, 1
 RC_WARP_CLAMP, RC_WARP_CONSTANT = 0, 1
 RC_WARP_MIN_CELL_LOG2, RC_WARP_MAX_CELL_LOG2, RC_WARP_MAX_DIM = 3, 6, 1 << 23
 RC_STATS_MAX_GRID, RC_STATS_SLOTS = 64, 8
+RC_MOTION_MAX_LEVELS, RC_MOTION_MAX_RANGE = 4, 8
 RC_TONE_MAX_GRID, RC_TONE_BINS = 16, 256
 RC_DEFECT_HOT, RC_DEFECT_COLD = 1, 2
 RC_CALIB_GAINS, RC_CALIB_CLIP, RC_CALIB_MAX_KNOTS = 1, 2, 16
@@ -108,6 +109,11 @@ class StatsDesc(C.Structure):
         ("roi", C.c_int32 * 4), ("grid", C.c_int32 * 2), ("bits", C.c_int32), ("matrix", C.c_int32), ("dark", C.c_int32), ("clip", C.c_int32),
         ("reserved", C.c_int32 * 4),
     ]
+
+
+class MotionDesc(C.Structure):
+    """Mirror of `struct rc_motion_desc`."""
+    _fields_ = [("block", C.c_int32), ("range", C.c_int32), ("pred_shift", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
 class DefectDesc(C.Structure):
@@ -199,6 +205,9 @@ _SIGS = {
     "rc_warp": (C.c_int, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _F, _F, _F, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_stats_desc_size": (_SZ, []),
     "rc_frame_stats": (C.c_int, [_P, _I, C.POINTER(StatsDesc), _P, _P, _I, _I, _I, _I, _I, _P]),
+    "rc_motion_desc_size": (_SZ, []),
+    "rc_motion_pyramid": (C.c_int, [_P, _I, _I, _I, C.POINTER(_P), _I, _I, _I, _I, _I, _P]),
+    "rc_motion_search": (C.c_int, [_P, _P, C.POINTER(MotionDesc), _P, _I, _I, _P, _I, _I, _I, _P]),
     "rc_defect_desc_size": (_SZ, []),
     "rc_raw_defects": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(DefectDesc), _P, _I, _P, _I, _P, _I, _I, _I, _P]),
     "rc_calib_desc_size": (_SZ, []),

@@ -995,6 +995,88 @@ def frame_stats(y: torch.Tensor, stats, crop_hw: Optional[Tuple[int, int]] = Non
     return FrameStats(hist, zones, stats, roi)
 
 
+def motion_pyramid(y: torch.Tensor, levels: int, matrix: str = "bt709", crop_hw: Optional[Tuple[int, int]] = None, out=None):
+    """Planar result (B,3,H,W), cropped to crop_hw, -> the luma pyramid: a list of `levels` (1 .. 4) uint8 tensors, level k (B, h >> k,
+    w >> k); level 0 is ops.frame_stats' 8-bit Y code, level k + 1 the rounded 2 x 2 means of level k (rc_motion_pyramid; the arithmetic
+    is fixed in include/realcam_hip.h).  `out`: an optional list of such tensors to write.  One launch reads the frame once; stateless and
+    capturable."""
+    from .out_format import MATRICES
+    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= _lib.RC_MOTION_MAX_LEVELS:
+        raise ValueError(f"motion_pyramid: levels must be an int in 1 .. {_lib.RC_MOTION_MAX_LEVELS}, got {levels!r}")
+    if not isinstance(matrix, str) or matrix not in MATRICES:
+        raise ValueError(f"motion_pyramid: matrix must be one of {sorted(MATRICES)}, got {matrix!r}")
+    y, h, w = _planar_source(y, "motion_pyramid", crop_hw)
+    if y.shape[2] * y.shape[3] >= 1 << 29:
+        raise ValueError(f"motion_pyramid: a source plane of {tuple(y.shape[2:])} has 2^29 samples or more")
+    if (h >> (levels - 1)) < 1 or (w >> (levels - 1)) < 1:
+        raise ValueError(f"motion_pyramid: level {levels - 1} of a {(h, w)} frame is empty")
+    shapes = [(y.shape[0], h >> k, w >> k) for k in range(levels)]
+    if out is None:
+        out = [y.new_empty(s, dtype=torch.uint8) for s in shapes]
+    else:
+        out = list(out)
+        if len(out) != levels or not all(isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and tuple(t.shape) == s and t.device == y.device and t.is_contiguous()
+                                         for t, s in zip(out, shapes)):
+            raise ValueError(f"motion_pyramid: out must be {levels} contiguous uint8 tensors of shapes {shapes} on {y.device}")
+    _R.motion_pyramid(y, out, MATRICES[matrix], h, w)
+    return out
+
+
+def motion_search(cur: torch.Tensor, ref: torch.Tensor, block: int, range: int, pred: Optional[torch.Tensor] = None, pred_shift: int = 0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One pyramid level of two frames, cur and ref (B,hs,ws) uint8, -> (B, hs // block, ws // block, 4) int32: per block of `cur` the offset
+    (dx, dy) into `ref` with the smallest sum of absolute differences among the (2 range + 1)^2 around the predictor, that cost, and the
+    block's texture (rc_motion_search; the arithmetic, the tie rule included, is fixed in include/realcam_hip.h).  pred: None or a coarser
+    (pred_shift 1) or equal (0) level's result.  One launch; stateless and capturable."""
+    from .motion import BLOCKS
+    cur, ref = _req(cur, "motion_search cur"), _req(ref, "motion_search ref")
+    if cur.dtype != torch.uint8 or ref.dtype != torch.uint8 or cur.dim() != 3 or cur.shape != ref.shape or cur.device != ref.device:
+        raise ValueError(f"motion_search: cur and ref must be (B,hs,ws) uint8 tensors of one shape and device, got {tuple(cur.shape)} {cur.dtype} and {tuple(ref.shape)} {ref.dtype}")
+    if block not in BLOCKS or isinstance(range, bool) or not isinstance(range, int) or not 0 <= range <= _lib.RC_MOTION_MAX_RANGE or pred_shift not in (0, 1):
+        raise ValueError(f"motion_search: block must be one of {BLOCKS}, range an int in 0 .. {_lib.RC_MOTION_MAX_RANGE}, pred_shift 0 or 1; got {block!r}, {range!r}, {pred_shift!r}")
+    b, hs, ws = cur.shape
+    if b < 1 or hs // block < 1 or ws // block < 1:
+        raise ValueError(f"motion_search: a plane of {(hs, ws)} in a batch of {b} holds no block of {block}")
+    if hs * ws >= 1 << 29:
+        raise ValueError(f"motion_search: a plane of {(hs, ws)} has 2^29 samples or more")
+    shape = (b, hs // block, ws // block, 4)
+    if pred is not None:
+        pred = _req(pred, "motion_search pred")
+        if pred.dtype != torch.int32 or pred.dim() != 4 or pred.shape[0] != b or pred.shape[1] < 1 or pred.shape[2] < 1 or pred.shape[3] != 4 or pred.device != cur.device:
+            raise ValueError(f"motion_search: pred must be a ({b}, pred_by, pred_bx, 4) int32 tensor on {cur.device}, got {tuple(pred.shape)} {pred.dtype}")
+    if out is None:
+        out = cur.new_empty(shape, dtype=torch.int32)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != shape or out.device != cur.device or not out.is_contiguous():
+        raise ValueError(f"motion_search: out must be a contiguous {shape} int32 tensor on {cur.device}")
+    _R.motion_search(cur, ref, pred, out, int(block), int(range), int(pred_shift))
+    return out
+
+
+def motion_estimate(cur_levels, ref_levels, motion):
+    """The pyramids of two frames (ops.motion_pyramid) -> a MotionField: the coarsest level is searched over `motion.search` with no
+    predictor, then every finer level over `motion.refine` around the level above (pred_shift 1): motion.levels launches, no host sync,
+    stateless and capturable.  vectors (B,by,bx,4) int32 are level 0's (dx, dy, cost, texture): cur's block sits at (x + dx, y + dy) of ref."""
+    from .motion import Motion, MotionField
+    if not isinstance(motion, Motion):
+        raise TypeError(f"motion_estimate: motion must be a Motion, got {type(motion).__name__}")
+    cur_levels, ref_levels = list(cur_levels), list(ref_levels)
+    if len(cur_levels) != motion.levels or len(ref_levels) != motion.levels:
+        raise ValueError(f"motion_estimate: {motion.levels} levels asked, the pyramids hold {len(cur_levels)} and {len(ref_levels)}")
+    if not isinstance(cur_levels[0], torch.Tensor) or cur_levels[0].dim() != 3:
+        raise ValueError("motion_estimate: a pyramid is a list of (B,h,w) uint8 tensors")
+    b, h, w = cur_levels[0].shape
+    motion.check(h, w)
+    for k, (c, r) in enumerate(zip(cur_levels, ref_levels)):
+        for t in (c, r):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or tuple(t.shape) != (b, h >> k, w >> k):
+                raise ValueError(f"motion_estimate: level {k} must be a {(b, h >> k, w >> k)} uint8 tensor, got {tuple(getattr(t, 'shape', ()))}")
+    res, pred = [None] * motion.levels, None
+    for k in reversed(range(motion.levels)):
+        pred = res[k] = motion_search(cur_levels[k], ref_levels[k], motion.block, motion.search if pred is None else motion.refine, pred=pred,
+                                      pred_shift=0 if pred is None else 1)
+    return MotionField(res[0], motion, (h, w), res)
+
+
 def make_coord(b: int, h: int, w: int, device=None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """Normalised pixel-coordinate map (B,2,h,w) in [-1,1], channel 0 = y, channel 1 = x: the lens-shading branch's input x[2]
     (upstream never published its generator; build convention).  Plain tensor construction, no kernel."""

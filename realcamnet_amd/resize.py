@@ -15,6 +15,7 @@ from .jpeg import Jpeg
 from .out_format import OutFormat
 from .sharpen import Sharpen
 from .stats import Stats
+from .motion import Motion
 from .tone import ToneMap
 from .warp import Warp
 
@@ -103,7 +104,8 @@ class Output:
     optional colour look, an optional Sharpen, then its format.
 
     format  None (the planar float tensor), "rgb8" / "rgb16" (interleaved uint8 / uint16), an OutFormat (a YuvFrames), a Jpeg (a JpegFrames:
-            any size, the 4:2:0 evenness rule below is the encoder surfaces' alone) or a Stats (a FrameStats: the statistics of the frame after this output's own warp / resize / look, in place of a picture).
+            any size, the 4:2:0 evenness rule below is the encoder surfaces' alone) or a Stats (a FrameStats: the statistics of the frame after this output's own warp / resize / look, in place of a picture)
+            or a Motion (a MotionField: the block motion vectors of that frame against the previous call's, in place of a picture).
     resize  None (the result's own size) or a Resize.
     look    None or a Lut3D, applied after the resize and before the encoder (ops.lut3d; with format None the looked tensor is fp32).
     warp    None or a Warp, applied first (ops.warp, fp32): the resize's window and the format then see a frame of warp.size.
@@ -125,10 +127,10 @@ class Output:
 
     def __post_init__(self, tone=None):
         f = self.format
-        if f is not None and not isinstance(f, (str, OutFormat, Jpeg, Stats)):
-            raise TypeError(f"Output.format must be None, 'rgb8', 'rgb16', an OutFormat, a Jpeg or a Stats, got {type(f).__name__}")
+        if f is not None and not isinstance(f, (str, OutFormat, Jpeg, Stats, Motion)):
+            raise TypeError(f"Output.format must be None, 'rgb8', 'rgb16', an OutFormat, a Jpeg, a Stats or a Motion, got {type(f).__name__}")
         if isinstance(f, str) and f not in ("rgb8", "rgb16"):
-            raise ValueError(f"Output.format must be None, 'rgb8', 'rgb16', an OutFormat, a Jpeg or a Stats, got {f!r}")
+            raise ValueError(f"Output.format must be None, 'rgb8', 'rgb16', an OutFormat, a Jpeg, a Stats or a Motion, got {f!r}")
         if self.resize is not None and not isinstance(self.resize, Resize):
             raise TypeError(f"Output.resize must be None or a Resize, got {type(self.resize).__name__}")
         if self.look is not None and not isinstance(self.look, Lut3D):
@@ -171,6 +173,6 @@ class Output:
             self.format.plane_layout(h, w)
         if isinstance(self.format, Jpeg):
             self.format.plan(h, w)
-        if isinstance(self.format, Stats):
+        if isinstance(self.format, (Stats, Motion)):
             self.format.check(h, w)
         return h, w

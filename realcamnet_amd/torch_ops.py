@@ -314,6 +314,42 @@ def _stats_launch(outs, y, h, w, roi, gy, gx, bits, matrix, dark, clip):
 define("frame_stats(Tensor y, int h, int w, int[] roi, int gy, int gx, int bits, int matrix, int dark, int clip) -> (Tensor, Tensor)",
        _stats_alloc, _stats_launch)
 
+
+def _pyramid_launch(ret, y, levels, matrix, h, w):
+    n = len(levels)
+    if not 1 <= n <= _lib.RC_MOTION_MAX_LEVELS:
+        raise ValueError(f"realcam::motion_pyramid: 1 .. {_lib.RC_MOTION_MAX_LEVELS} levels, got {n}")
+    for k, t in enumerate(levels):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (y.shape[0], h >> k, w >> k) or not t.is_contiguous():
+            raise ValueError(f"realcam::motion_pyramid: level {k} must be a contiguous {(y.shape[0], h >> k, w >> k)} uint8 tensor, got {tuple(t.shape)} {t.dtype}")
+    ptrs = (C.c_void_p * n)(*(t.data_ptr() for t in levels))
+    check(lib().rc_motion_pyramid(y.data_ptr(), _dt(y), matrix, n, ptrs, y.shape[0], y.shape[2], y.shape[3], h, w, _stream()), "rc_motion_pyramid")
+
+
+# y (B,3,H,W) planar, cropped to (h,w); levels: the 1 .. 4 uint8 tensors (B, h >> k, w >> k) that are written, every element (the luma code and
+# its 2 x 2 rounded means); matrix: the rc_yuv_matrix enum -> nothing (an empty tensor)
+define("motion_pyramid(Tensor y, Tensor(a!)[] levels, int matrix, int h, int w) -> Tensor",
+       lambda y, levels, matrix, h, w: y.new_empty((0,)), _pyramid_launch)
+
+
+def _search_launch(ret, cur, ref, pred, out, block, rng, pred_shift):
+    b, hs, ws = cur.shape
+    if cur.dtype != torch.uint8 or ref.dtype != torch.uint8 or ref.shape != cur.shape or not (cur.is_contiguous() and ref.is_contiguous()):
+        raise ValueError(f"realcam::motion_search: cur and ref must be contiguous uint8 tensors of one shape, got {tuple(cur.shape)} {cur.dtype} and {tuple(ref.shape)} {ref.dtype}")
+    if out.dtype != torch.int32 or tuple(out.shape) != (b, hs // block, ws // block, 4) or not out.is_contiguous():
+        raise ValueError(f"realcam::motion_search: out must be a contiguous {(b, hs // block, ws // block, 4)} int32 tensor, got {tuple(out.shape)} {out.dtype}")
+    if pred is not None and (pred.dtype != torch.int32 or pred.dim() != 4 or pred.shape[0] != b or pred.shape[3] != 4 or not pred.is_contiguous()):
+        raise ValueError(f"realcam::motion_search: pred must be a contiguous ({b}, pred_by, pred_bx, 4) int32 tensor, got {tuple(pred.shape)} {pred.dtype}")
+    d = _lib.MotionDesc(block=block, range=rng, pred_shift=pred_shift)
+    check(lib().rc_motion_search(cur.data_ptr(), ref.data_ptr(), C.byref(d), _p(pred), 0 if pred is None else pred.shape[1], 0 if pred is None else pred.shape[2],
+                                 out.data_ptr(), b, hs, ws, _stream()), "rc_motion_search")
+
+
+# cur, ref (B,hs,ws) uint8: one pyramid level of two frames; pred (B,pred_by,pred_bx,4) int32, a coarser (pred_shift 1) or equal (0) level's
+# result, or None; out (B, hs // block, ws // block, 4) int32 is written, every element: (dx, dy, cost, texture) per block -> nothing (an empty tensor)
+define("motion_search(Tensor cur, Tensor ref, Tensor? pred, Tensor(a!) out, int block, int range, int pred_shift) -> Tensor",
+       lambda cur, ref, pred, out, block, range, pred_shift: cur.new_empty((0,)), _search_launch)
+
 def _unpacked_dtype(src, storage):
     """What a stage that keeps the storage writes (raw_defects, raw_quad's remosaic): uint16 for the count storages, src's dtype for float."""
     return torch.uint16 if storage in (_lib.RC_RAW_U16, _lib.RC_RAW_U8, _lib.RC_RAW_MIPI10, _lib.RC_RAW_MIPI12) else src.dtype
