@@ -501,7 +501,10 @@ using pair::E1_RELU; using pair::E1_FILM_LEAKY; using pair::E2_PLAIN; using pair
 constexpr int C = 48, NT = 3, NV = 12, SPIX = 96, STEPS = 14, ES = 2;
 constexpr int OTH = 8, OTW = 32, MH = OTH + 2, MW = OTW + 2, IH = OTH + 4, IW = OTW + 4;
 constexpr int NMID = MH * MW, NIN = IH * IW, N_MID_TILES = (NMID + 15) / 16;
-constexpr int IN_BYTES = NIN * SPIX, MID_BYTES = NMID * SPIX;
+// An input buffer is filled by whole 1 KB LDS-DMA instructions (stage_issue) and the tile's 41 472 bytes are no multiple of that: the last instruction's lanes past the
+// tile write 512 bytes of zeros BEHIND it.  The buffers are therefore a whole number of kilobytes apart.  Packed tightly, staging into buffer 1 zeroed the first
+// 5 1/3 pixels of mid buffer 0 while conv1 was filling it -- wrong outputs at the top-left of every even tile of a block that walks more than one tile.
+constexpr int IN_BYTES = (NIN * SPIX + 1023) / 1024 * 1024, MID_BYTES = NMID * SPIX;
 constexpr int kMaxBatchGates = 48;                               // every image's CALayer gate sits in LDS (48 x 192 B): a commit reads it from there
 constexpr int OFF_IN = 0, OFF_MID = 2 * IN_BYTES, OFF_BIAS = OFF_MID + 2 * MID_BYTES, OFF_GATE = OFF_BIAS + 2 * C * 4, LDS_BYTES = OFF_GATE + kMaxBatchGates * C * 4;
 static_assert(LDS_BYTES <= 160 * 1024, "pair2 LDS budget");
@@ -558,6 +561,7 @@ struct Mma2 {
 // to wave w (both teams stage: team B's store-heavy epilogue and team A's larger MFMA share leave them about the same slack).
 constexpr int N_PIECES = NIN * VPP, N_DMA = (N_PIECES + 63) / 64, kDmaPerWave = (N_DMA + 7) / 8, kRounds = 3;   // per wave: 6 instructions = 2 batches of 3
 static_assert(N_PIECES == 2592 && N_DMA == 41 && kDmaPerWave == 6, "staging map");
+static_assert(N_DMA * 1024 <= IN_BYTES, "every DMA instruction lands inside its own input buffer");
 
 __device__ __forceinline__ int piece_goff(const PairArgs& a, const TileSrc& t, int P, bool& center) {
     const int pix = P / VPP, v = P - pix * VPP;
