@@ -714,6 +714,56 @@ size_t rc_temporal_desc_size(void);
 int rc_raw_temporal(const void* d_src, const rc_raw_format* fmt, const rc_temporal_desc* desc, const float* d_prev, int prev_pitch_bytes,
                     const float* d_gain, int gain_batch, void* d_dst, int dst_pitch_bytes, int batch, int h, int w, void* stream);
 
+/* ---- motion-compensated temporal noise reduction (ABI 15, additive): rc_raw_temporal against the state displaced by block vectors, and
+ * the 8-bit luma proxy of a mosaic that rc_motion_search finds those vectors on.  On a pan every textured sample of rc_raw_temporal "moves"
+ * and the frame passes unfiltered; with the state moved by its block's vector first, the filter works as on a static scene.
+ * Replaces: a demosaic or an fp32 binning pass, a normalisation and a quantisation in torch to get a plane the matcher can read, and, for the
+ * filter, an index gather of the whole state into an aligned copy (8 bytes per sample on top of a u16 frame's 10) in front of
+ * rc_raw_temporal.  Here one launch for every level of a frame's pyramid and one launch for the filter; rc_motion_search is unchanged and
+ * its vectors are in Bayer cells.  Stateless and capturable; no device buffer of their own.
+ *
+ * rc_raw_motion_pyramid.  src: B frames of a mosaic (2h, 2w) as rc_raw_temporal reads them (fmt: storage, cfa, line_bytes, width, black,
+ * white); the fp32 state of the filter is the RC_RAW_F32 storage.  d_levels: a HOST array of `levels` (1 .. 4) device pointers; level k is
+ * (B, h >> k, w >> k) uint8, contiguous: level 0 holds one code per Bayer cell.  c is the decoded sample as fp32; every product and every
+ * sum is rounded to fp32 on its own.
+ *   level 0      cell (cy, cx): d_pos = c[2cy + (pos >> 1)][2cx + (pos & 1)] - black[pos] for pos = 0 .. 3;  m = ((d0 + d1) + (d2 + d3)) 0.25;
+ *                t = m inv, inv = (float)(1.0 / ((double)white - ((double)b0 + b1 + b2 + b3) / 4)) formed on the host;  with a gain g
+ *                (`gain` when it is not 1, else d_gain[gain_batch == 1 ? 0 : frame]) t = t g;  NaN -> 0, clamp to [0, 1];
+ *                q = (int)rint(65025 t), half to even;  code = floor(sqrt(q)) as an exact integer in 0 .. 255: r = (int)sqrtf((float)q), then
+ *                r - 1 where r r > q, r + 1 where (r + 1)(r + 1) <= q, so no rounding of the float square root matters.  The square root is
+ *                deliberate: linear sensor codes put the shadows into a handful of 8-bit levels, and it makes shot noise roughly uniform
+ *                over the range.
+ *   level k+1    pixel (x, y) = (a + b + c + d + 2) >> 2 over level k's pixels (2x .. 2x+1, 2y .. 2y+1): rc_motion_pyramid's rule; a trailing
+ *                odd row or column of level k feeds nothing.
+ * One launch reads every sample once and writes every element of every level.  The gain is what rc_raw_temporal applies to its state: the
+ * proxy of a state taken with gain g matches the proxy of the frame across an exposure step (the black level is not re-added: the proxy
+ * has none).  Device gain values are not checked (any code, no fault).
+ * Null d_src / fmt / d_levels or a null level pointer, an unknown storage or cfa, line_bytes shorter than a row or no multiple of the sample
+ * size, fmt->width other than 0 or 2w, a RAW10 width not divisible by 4, a source misaligned for its sample (MIPI: 4 bytes), a black level
+ * that is not finite, a white level that is not finite or not above the mean black level, a gain given both ways (gain != 1 and d_gain), a
+ * host gain <= 0 or not finite, gain_batch other than 1 or batch (0 without d_gain), d_gain not 4-byte aligned, levels outside 1 .. 4, an
+ * empty coarsest level, a frame of 2 GiB or more, non-zero reserved, more than 65535 frames: RC_ERR_INVALID before any launch. */
+int rc_raw_motion_pyramid(const void* d_src, const rc_raw_format* fmt, float gain, const float* d_gain, int gain_batch, int levels,
+                          void* const* d_levels, int batch, int h, int w, void* stream);
+
+/* rc_raw_temporal_mc.  Every argument up to w is rc_raw_temporal's and means what it means there.  d_vec: (B, by, bx, 4) int32, 16-byte
+ * aligned -- what rc_motion_search wrote at level 0 of the two proxies; slots 0 and 1 (dx, dy) are used, in Bayer cells: the content of a
+ * cell of the frame sits at (cx + dx, cy + dy) of the state.  block: 8, 16 or 32 cells per node and axis; by, bx >= 1 (a grid short of the
+ * frame is continued by its last row and column, one beyond it is not read there).  One step goes in front of rc_raw_temporal's 1 - 7, which
+ * stay word for word with this s:
+ *   0'. displaced state   cy = y >> 1, cx = x >> 1; the node is (min(cy / block, by-1), min(cx / block, bx-1)); (dx, dy) are its slots 0 and
+ *                1, each clamped to [-32768, 32767] (device data is never trusted);
+ *                s = prev[2 clamp(cy + dy, 0, h-1) + (y & 1)][2 clamp(cx + dx, 0, w-1) + (x & 1)].
+ * The displacement is in whole cells and the clamp is in cells, so a sample only ever meets a state sample of its own CFA position.  Step
+ * 3's taps use e = |c - p| of each tap's own sample, displaced by that sample's own block.  With RC_TNR_RESET neither d_prev nor d_vec is
+ * read (both may be null).  Hence, exactly: a zero field gives rc_raw_temporal's bits; any field gives the bits of rc_raw_temporal run on a
+ * state gathered by step 0'.  Every index is clamped: no vector makes the kernel read outside its buffers.  One launch, capturable.
+ * Every refusal of rc_raw_temporal, and: a null d_vec without RC_TNR_RESET, d_vec not 16-byte aligned, a block other than 8, 16 or 32,
+ * by or bx < 1: RC_ERR_INVALID before anything is enqueued. */
+int rc_raw_temporal_mc(const void* d_src, const rc_raw_format* fmt, const rc_temporal_desc* desc, const float* d_prev, int prev_pitch_bytes,
+                       const float* d_gain, int gain_batch, void* d_dst, int dst_pitch_bytes, int batch, int h, int w,
+                       const int* d_vec, int by, int bx, int block, void* stream);
+
 /* ---- Quad-Bayer (tetracell) sensors (ABI 15, additive): the new first box of the input side, in front of the defects stage.  Each colour of
  * the Bayer cell covers a 2x2 block of photosites, so the pattern repeats every 4x4; what leaves the stage is an ordinary Bayer mosaic with
  * the same cfa and the same levels.

@@ -300,8 +300,10 @@ def _merge_exposures(net, mosaic, raw_format):
 def _temporal(mosaic, raw_format):
     """raw_format.temporal (a Temporal): ops.raw_temporal (one launch) filters the frame -- repaired and merged by now -- against the last
     filtered mosaic its TemporalState holds, and the result becomes the state: two buffers that swap from call to call.  An empty state, or
-    one of another shape or device, starts over (the result is the decoded frame).  Returns the filtered fp32 mosaic and the format that
-    describes it: storage "float", the same CFA and levels, the calibration kept for the next stage."""
+    one of another shape or device, starts over (the result is the decoded frame, state.field is None).  With Temporal(motion=...) and a
+    state that continues, the block vectors of the frame against the state come first (_temporal_vectors), the filter reads the state
+    displaced by them (still one launch) and state.field keeps them.  Returns the filtered fp32 mosaic and the format that describes it:
+    storage "float", the same CFA and levels, the calibration kept for the next stage."""
     import dataclasses
     h2, w2 = raw_format.validate(mosaic.shape)
     st = raw_format.temporal.state
@@ -310,8 +312,32 @@ def _temporal(mosaic, raw_format):
     out = st._spare
     if out is None or out is prev or tuple(out.shape) != shape or out.device != mosaic.device:
         out = None
-    st.frame, st._spare = ops.raw_temporal(mosaic, raw_format, prev=prev, out=out), prev
+    tm = raw_format.temporal.motion
+    st.field = None
+    if tm is not None and prev is not None:
+        st.field = _temporal_vectors(mosaic, raw_format, prev, st)
+    st.frame, st._spare = ops.raw_temporal(mosaic, raw_format, prev=prev, out=out, vectors=st.field, block=16 if tm is None else tm.block), prev
     return st.frame, dataclasses.replace(raw_format, storage="float", width=None, defects=None, exposures=None, temporal=None)
+
+
+def _temporal_vectors(mosaic, raw_format, prev, st):
+    """Temporal(motion=TemporalMotion(...)) with a state that continues: the block vectors (B,by,bx,4) int32 of the frame against the state,
+    in Bayer cells.  The luma-proxy pyramids of the frame and of the state (ops.raw_motion_pyramid, one launch each, into buffers the
+    TemporalState keeps; the state is read as float storage with the frame's levels and Temporal.gain as its gain), ops.motion_estimate
+    (`levels` launches), and the vectors of blocks with too little texture or too high a cost set to zero on the device: no host sync."""
+    import dataclasses
+    t = raw_format.temporal
+    tm, spec = t.motion, t.motion.spec()
+    b, h2, w2 = prev.shape
+    of_frame, of_state = st.pyramids(spec.level_shapes(b, h2 // 2, w2 // 2), prev)
+    cur = ops.raw_motion_pyramid(mosaic, raw_format, tm.levels, out=of_frame)
+    state_format = dataclasses.replace(raw_format, storage="float", width=None, defects=None, exposures=None)
+    ref = ops.raw_motion_pyramid(prev, state_format, tm.levels, gain=t.gain, out=of_state)
+    field = ops.motion_estimate(cur, ref, spec)
+    v = field.vectors
+    if tm.min_texture > 0 or tm.max_sad is not None:
+        v[..., :2] *= field.valid(tm.min_texture, tm.max_sad)[..., None]
+    return v
 
 
 def _temporal_check(raw_format):

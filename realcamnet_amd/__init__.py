@@ -26,9 +26,9 @@ from .tone import ToneMap  # noqa: F401
 from .defects import DefectMap, Defects  # noqa: F401
 from .calibration import Calibration, GainMap, Pwl  # noqa: F401
 from .exposures import Exposures  # noqa: F401
-from .temporal import Temporal, TemporalState  # noqa: F401
+from .temporal import Temporal, TemporalMotion, TemporalState  # noqa: F401
 from .quad import QuadBayer  # noqa: F401
 
 __all__ = ["networks", "LiteISP", "groupmix", "tcm", "raw2bit", "LiteISPNet", "LiteISPNet_GFM_LSC", "LiteISPNet_GFM_LSC_GMA", "LiteISPNet_LSC",
            "LiteISPNet_GFM", "LiteISPNet_GFMresize", "ISPUNet_GFM_LSC", "ISPUNet_GFM", "ISPUNet_GFM_LFM", "ISPUNet_LSC", "ResUNet", "ISPUNet_GFM_crop", "ISPUNet_GFM_LSC1",
-           "ISPUNet_GFM_LSC_noskip", "GMA_Block", "graphs", "GraphedCall", "RawFormat", "OutFormat", "YuvFrames", "Jpeg", "JpegFrames", "Resize", "Output", "Lut3D", "Warp", "Stats", "FrameStats", "Motion", "MotionField", "MotionState", "Stabilizer", "DefectMap", "Defects", "Calibration", "GainMap", "Pwl", "Exposures", "Temporal", "TemporalState", "Sharpen", "ToneMap", "QuadBayer"]
+           "ISPUNet_GFM_LSC_noskip", "GMA_Block", "graphs", "GraphedCall", "RawFormat", "OutFormat", "YuvFrames", "Jpeg", "JpegFrames", "Resize", "Output", "Lut3D", "Warp", "Stats", "FrameStats", "Motion", "MotionField", "MotionState", "Stabilizer", "DefectMap", "Defects", "Calibration", "GainMap", "Pwl", "Exposures", "Temporal", "TemporalMotion", "TemporalState", "Sharpen", "ToneMap", "QuadBayer"]

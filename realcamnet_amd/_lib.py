@@ -216,6 +216,8 @@ _SIGS = {
     "rc_raw_hdr_merge": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(HdrDesc), _P, _I, _P, _I, _I, _I, _I, _P]),
     "rc_temporal_desc_size": (_SZ, []),
     "rc_raw_temporal": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(TemporalDesc), _P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
+    "rc_raw_motion_pyramid": (C.c_int, [_P, C.POINTER(RawFormatDesc), _F, _P, _I, _I, C.POINTER(_P), _I, _I, _I, _P]),
+    "rc_raw_temporal_mc": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(TemporalDesc), _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     "rc_quad_desc_size": (_SZ, []),
     "rc_raw_quad": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(QuadDesc), _P, _I, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -655,7 +655,8 @@ def raw_hdr_merge(mosaic: torch.Tensor, raw_format, exposures=None) -> torch.Ten
                             exposures.layout == "lines", host_times, list(exposures.knee), [] if exposures.motion is None else list(exposures.motion))
 
 
-def raw_temporal(mosaic: torch.Tensor, raw_format, prev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def raw_temporal(mosaic: torch.Tensor, raw_format, prev: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                 vectors: Optional[torch.Tensor] = None, block: int = 16) -> torch.Tensor:
     """Temporal noise reduction on the mosaic itself, between the repair / merge and the calibration (rc_raw_temporal; the arithmetic is fixed
     in include/realcam_hip.h): a sensor frame as `raw_format` (a RawFormat with `temporal` set) describes it, and `prev`, the last filtered
     mosaic (B,2h,2w) fp32 (None: a reset, the result is the decoded frame) -> the filtered mosaic (B,2h,2w) fp32 in the frame's code units,
@@ -663,7 +664,11 @@ def raw_temporal(mosaic: torch.Tensor, raw_format, prev: Optional[torch.Tensor] 
     that is a multiple of one sample), frames must be whole rows apart.  One launch; with explicit `prev` and `out` nothing is allocated and
     the call is capturable; a gain tensor is read in place by the kernel; nothing is synchronised.  The Temporal's state is not looked at:
     the caller chains prev / out.  raw_format.defects and raw_format.exposures must be None (run those stages first); a Calibration.curve is
-    refused (the noise model needs linear samples).  Non-finite samples or state are outside the contract."""
+    refused (the noise model needs linear samples).  Non-finite samples or state are outside the contract.
+    `vectors` (B,by,bx,4) int32 -- ops.motion_estimate(...).vectors of the frame's and the state's ops.raw_motion_pyramid, one node per
+    `block` x `block` Bayer cells (8, 16 or 32) -- makes the filter read the state displaced by each block's (dx, dy), in whole cells, every
+    index clamped (rc_raw_temporal_mc, still one launch; a zero field gives the same bits as none).  The Temporal's motion is not looked at
+    (but for RawFormat.validate, which refuses a frame too small for it): the caller brings the vectors."""
     from .raw_format import CFAS
     from .temporal import Temporal
     _raw_stages(raw_format, "raw_temporal", ("temporal", "calibration"))
@@ -699,7 +704,62 @@ def raw_temporal(mosaic: torch.Tensor, raw_format, prev: Optional[torch.Tensor] 
         gain = _read_in_place(t.gain, "gain", "raw_temporal", mosaic, "a host number")
     elif t.gain is not None:
         host_gain = [t.gain]
+    if vectors is not None:
+        from .motion import BLOCKS
+        if prev is None:
+            raise ValueError("raw_temporal: vectors displace the state: give prev, or no vectors for a reset")
+        if isinstance(block, bool) or not isinstance(block, int) or block not in BLOCKS:
+            raise ValueError(f"raw_temporal: block must be one of {BLOCKS} (Bayer cells), got {block!r}")
+        if not isinstance(vectors, torch.Tensor):
+            raise TypeError(f"raw_temporal: vectors must be a tensor, got {type(vectors).__name__}")
+        if vectors.dtype != torch.int32 or vectors.dim() != 4 or vectors.shape[0] != shape[0] or vectors.shape[1] < 1 or vectors.shape[2] < 1 \
+                or vectors.shape[3] != 4 or vectors.device != mosaic.device or not vectors.is_contiguous():
+            raise ValueError(f"raw_temporal: vectors must be a contiguous ({shape[0]}, by, bx, 4) int32 tensor on {mosaic.device}, got "
+                             f"{tuple(vectors.shape)} {vectors.dtype} on {vectors.device}")
+        _R.raw_temporal_mc(mosaic, prev, gain, vectors, out, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), list(t.params()),
+                           host_gain, int(block))
+        return out
     _R.raw_temporal(mosaic, prev, gain, out, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), list(t.params()), host_gain)
+    return out
+
+
+def raw_motion_pyramid(mosaic: torch.Tensor, raw_format, levels: int, gain=None, out=None):
+    """A sensor frame as `raw_format` (a RawFormat) describes it -> the pyramid of its luma proxy: a list of `levels` (1 .. 4) uint8 tensors,
+    level k (B, h >> k, w >> k) for a mosaic of (2h, 2w) samples.  Level 0 holds one code per Bayer cell: the square root of the cell's mean
+    over its four samples, each less its black level, normalised by the white level (rc_raw_motion_pyramid; the arithmetic is fixed in
+    include/realcam_hip.h); level k + 1 is the rounded 2 x 2 means of level k.  `gain`: None, one host number (finite and > 0), or a (1,1) /
+    (B,1) fp32 tensor read in place by the kernel -- what Temporal.gain is to the state.  `out`: an optional list of such tensors to write.
+    The levels go into ops.motion_search / ops.motion_estimate, whose vectors are then in cells.  One launch reads the frame once; stateless
+    and capturable.  raw_format.defects and raw_format.exposures must be None (run those stages first); temporal and calibration are not
+    looked at."""
+    from .raw_format import CFAS
+    _raw_stages(raw_format, "raw_motion_pyramid", ("temporal", "calibration"))
+    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= _lib.RC_MOTION_MAX_LEVELS:
+        raise ValueError(f"raw_motion_pyramid: levels must be an int in 1 .. {_lib.RC_MOTION_MAX_LEVELS}, got {levels!r}")
+    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format)
+    b, h, w = mosaic.shape[0], h2 // 2, w2 // 2
+    if (h >> (levels - 1)) < 1 or (w >> (levels - 1)) < 1:
+        raise ValueError(f"raw_motion_pyramid: level {levels - 1} of a frame of {(h, w)} cells is empty")
+    dev_gain, host_gain = None, []
+    if isinstance(gain, torch.Tensor):
+        if gain.dtype != torch.float32 or gain.dim() != 2 or gain.shape[1] != 1 or gain.shape[0] not in (1, b):
+            raise ValueError(f"raw_motion_pyramid: a gain tensor must be (1,1) or ({b},1) fp32, got {tuple(gain.shape)} {gain.dtype}")
+        dev_gain = _read_in_place(gain, "gain", "raw_motion_pyramid", mosaic, "a host number")
+    elif gain is not None:
+        if isinstance(gain, bool) or not isinstance(gain, (int, float)):
+            raise TypeError(f"raw_motion_pyramid: gain must be None, a number or a (B,1) fp32 tensor, got {gain!r}")
+        if not (math.isfinite(gain) and gain > 0.0):
+            raise ValueError(f"raw_motion_pyramid: gain must be finite and > 0, got {gain!r}")
+        host_gain = [float(gain)]
+    shapes = [(b, h >> k, w >> k) for k in range(levels)]
+    if out is None:
+        out = [mosaic.new_empty(s, dtype=torch.uint8) for s in shapes]
+    else:
+        out = list(out)
+        if len(out) != levels or not all(isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and tuple(t.shape) == s and t.device == mosaic.device
+                                         and t.is_contiguous() for t, s in zip(out, shapes)):
+            raise ValueError(f"raw_motion_pyramid: out must be {levels} contiguous uint8 tensors of shapes {shapes} on {mosaic.device}")
+    _R.raw_motion_pyramid(mosaic, dev_gain, out, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), float(raw_format.white_level), host_gain)
     return out
 
 

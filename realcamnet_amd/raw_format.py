@@ -39,7 +39,8 @@ class RawFormat:
                  the linear sensor codes -- after the repair / the merge and in front of the calibration -- against the last filtered
                  frame, which its TemporalState carries from call to call (the B frames of a call are B streams).  The noise model is in
                  this storage's own code units and uses these black levels; a calibration must not carry a curve (the noise model needs
-                 linear samples).
+                 linear samples).  Temporal(motion=TemporalMotion(...)) compensates camera motion: block vectors are estimated on the
+                 mosaic's luma proxy and the filter reads the state displaced by them.
     quad         None, or a QuadBayer: the sensor is Quad-Bayer (tetracell) -- `cfa` then names the colours of the four 2x2 blocks of the 4x4
                  tile (sample (y,x) has colour cfa[2 ((y>>1)&1) + ((x>>1)&1)]) and forward_mosaic first turns the frame into an ordinary
                  Bayer mosaic with this cfa and these levels (ops.raw_quad, one launch: mode "remosaic" at full size, "bin" at half size),

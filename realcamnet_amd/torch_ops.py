@@ -463,6 +463,56 @@ def _temporal_launch(ret, src, prev, gain, out, storage, cfa, width, black, para
 define("raw_temporal(Tensor src, Tensor? prev, Tensor? gain, Tensor(a!) out, int storage, int cfa, int width, float[] black, float[] params, "
        "float[] host_gain) -> Tensor", lambda src, prev, gain, out, storage, cfa, width, black, params, host_gain: out.new_empty((0,)), _temporal_launch)
 
+def _temporal_mc_launch(ret, src, prev, gain, vectors, out, storage, cfa, width, black, params, host_gain, block):
+    if len(params) != 4 or len(host_gain) not in (0, 1) or (gain is not None and host_gain):
+        raise ValueError(f"realcam::raw_temporal_mc: params holds n_abs, n_rel, alpha, ramp, the gain one host number or a tensor; "
+                         f"got {params!r}, {host_gain!r}")
+    b, h2, _ = src.shape
+    if out.dtype != torch.float32 or tuple(out.shape) != (b, h2, width) or prev.dtype != torch.float32 or prev.shape != out.shape:
+        raise ValueError(f"realcam::raw_temporal_mc: prev and out must be ({b}, {h2}, {width}) fp32, got {tuple(prev.shape)} and {tuple(out.shape)}")
+    if vectors.dtype != torch.int32 or vectors.dim() != 4 or vectors.shape[0] != b or vectors.shape[1] < 1 or vectors.shape[2] < 1 or vectors.shape[3] != 4 \
+            or not vectors.is_contiguous():
+        raise ValueError(f"realcam::raw_temporal_mc: vectors must be a contiguous ({b}, by, bx, 4) int32 tensor, got {tuple(vectors.shape)} {vectors.dtype}")
+    src, f = _raw_source(src, storage, cfa, width, black, 0.0)
+    d = _lib.TemporalDesc(flags=_lib.RC_TNR_GAIN if host_gain else 0, noise_abs=float(params[0]), noise_rel=float(params[1]), alpha=float(params[2]),
+                          ramp=float(params[3]), gain=float(host_gain[0]) if host_gain else 0.0)
+    check(lib().rc_raw_temporal_mc(src.data_ptr(), C.byref(f), C.byref(d), prev.data_ptr(), 4 * prev.stride(1), _p(gain), 0 if gain is None else gain.shape[0],
+                                   out.data_ptr(), 4 * out.stride(1), b, h2 // 2, width // 2, vectors.data_ptr(), vectors.shape[1], vectors.shape[2], block,
+                                   _stream()), "rc_raw_temporal_mc")
+
+
+# raw_temporal's arguments with a state (prev is not optional: a reset is raw_temporal's) and vectors (B, by, bx, 4) int32, rc_motion_search's
+# level-0 result in Bayer cells, one node per `block` x `block` cells; out (B, 2h, 2w) fp32 is written -> nothing (an empty tensor)
+define("raw_temporal_mc(Tensor src, Tensor prev, Tensor? gain, Tensor vectors, Tensor(a!) out, int storage, int cfa, int width, float[] black, "
+       "float[] params, float[] host_gain, int block) -> Tensor",
+       lambda src, prev, gain, vectors, out, storage, cfa, width, black, params, host_gain, block: out.new_empty((0,)), _temporal_mc_launch)
+
+
+def _raw_pyramid_launch(ret, src, gain, levels, storage, cfa, width, black, white, host_gain):
+    n = len(levels)
+    if not 1 <= n <= _lib.RC_MOTION_MAX_LEVELS:
+        raise ValueError(f"realcam::raw_motion_pyramid: 1 .. {_lib.RC_MOTION_MAX_LEVELS} levels, got {n}")
+    if len(host_gain) not in (0, 1) or (gain is not None and host_gain):
+        raise ValueError(f"realcam::raw_motion_pyramid: the gain is one host number or a tensor, got {host_gain!r} and a tensor")
+    b, h2, _ = src.shape
+    h, w = h2 // 2, width // 2
+    for k, t in enumerate(levels):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (b, h >> k, w >> k) or not t.is_contiguous():
+            raise ValueError(f"realcam::raw_motion_pyramid: level {k} must be a contiguous {(b, h >> k, w >> k)} uint8 tensor, got {tuple(t.shape)} {t.dtype}")
+    src, f = _raw_source(src, storage, cfa, width, black, white)
+    ptrs = (C.c_void_p * n)(*(t.data_ptr() for t in levels))
+    check(lib().rc_raw_motion_pyramid(src.data_ptr(), C.byref(f), float(host_gain[0]) if host_gain else 1.0, _p(gain), 0 if gain is None else gain.shape[0],
+                                      n, ptrs, b, h, w, _stream()), "rc_raw_motion_pyramid")
+
+
+# src (B, 2h, X) as raw_ingest_fmt takes it; gain (1 or B, 1) fp32 on the device or None (then host_gain holds one number or nothing); levels:
+# the 1 .. 4 uint8 tensors (B, h >> k, w >> k) that are written, every element (the luma proxy of the Bayer cells and its 2 x 2 rounded
+# means) -> nothing (an empty tensor)
+define("raw_motion_pyramid(Tensor src, Tensor? gain, Tensor(a!)[] levels, int storage, int cfa, int width, float[] black, float white, "
+       "float[] host_gain) -> Tensor",
+       lambda src, gain, levels, storage, cfa, width, black, white, host_gain: src.new_empty((0,)), _raw_pyramid_launch)
+
+
 def _quad_alloc(src, storage, cfa, width, mode):
     b, h, _ = src.shape
     if mode == _lib.RC_QUAD_BIN:
