@@ -1,10 +1,8 @@
 // Motion estimation behind the network (include/realcam_hip.h, rc_motion_pyramid and rc_motion_search): hierarchical block matching on the
 // 8-bit luma code of the planar result.  Two kernels; everything after the level-0 codes is integer.
 //
-// motion_pyramid_kernel: one launch, the frame read once.  A lane owns a 4 x 4 tile of pixels: sixteen level-0 bytes, four level-1 bytes,
-// one level-2 byte; a wave is 16 x 4 lanes (64 x 16 pixels), so the level-3 byte of a 2 x 2 group of lanes is two lane exchanges (lane ^ 1,
-// lane ^ 16) and the lane with both bits clear stores it.  A block is four waves side by side (256 x 16 pixels).  Level 0 goes out as one
-// dword per row and lane, level 1 as one 16-bit store per row where the level's rows keep that alignment, bytes otherwise.
+// motion_pyramid_kernel: one launch, the frame read once.  A lane forms the sixteen level-0 codes of its 4 x 4 tile of pixels; the map and
+// the levels' reductions and stores are pyramid_tail.hpp's.
 //
 // motion_search_kernel<N>: one wave per matching block of N x N, four waves (four matching blocks) per workgroup, each with its own LDS.
 //   stage     the block's N x N bytes of `cur`, and the window of `ref` the candidates touch, every index clamped into the plane: rows
@@ -17,14 +15,12 @@
 //   texture   v_sad_u8 of each block dword against itself moved one byte (the last byte against itself: 0) and against the dword below.
 //   winner    every lane packs its candidates' keys (cost, |oy| + |ox|, oy + R, ox + R) into 18 + 5 + 5 + 5 bits and keeps the smallest;
 //             six lane exchanges give the wave's.  Lane 0 stores the four ints as one 16-byte store.
+#include "pyramid_tail.hpp"
 #include "ycc_code.hpp"
 
 namespace rc {
 
 // ---- pyramid ------------------------------------------------------------------------------------------------------------------------------
-constexpr int kPyrWaves = 4, kPyrThreads = 64 * kPyrWaves, kPyrLanesX = 16, kPyrTile = 4;
-constexpr int kPyrBlockW = kPyrWaves * kPyrLanesX * kPyrTile, kPyrBlockH = (64 / kPyrLanesX) * kPyrTile;
-
 struct PyramidArgs {
     uint8_t* lv[RC_MOTION_MAX_LEVELS];
     int levels;
@@ -36,9 +32,8 @@ struct PyramidArgs {
 
 template <typename TI>
 __global__ void __launch_bounds__(kPyrThreads) motion_pyramid_kernel(PyramidArgs a, const TI* __restrict__ src) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, frame = blockIdx.z;
-    const int tx = (blockIdx.x * kPyrWaves + wv) * kPyrLanesX + (lane & (kPyrLanesX - 1));      // the lane's tile: pixels 4 tx .., 4 ty ..
-    const int ty = blockIdx.y * (64 / kPyrLanesX) + (lane >> 4);
+    const int lane = threadIdx.x & 63, frame = blockIdx.z;
+    const int tx = pyramid_tx(lane), ty = pyramid_ty(lane);                                     // the lane's tile: pixels 4 tx .., 4 ty ..
     const int x0 = tx * kPyrTile, y0 = ty * kPyrTile, cnt = a.w - x0;                           // cnt <= 0: the tile is right of the crop
     const size_t plane = (size_t)a.H * a.W;
     const TI* s0 = src + (size_t)frame * 3 * plane + x0;
@@ -63,58 +58,7 @@ __global__ void __launch_bounds__(kPyrThreads) motion_pyramid_kernel(PyramidArgs
             q[r][k] = code(y, 255.f, 0.f, 0.f, 255.f);
         }
     }
-    {   // level 0: (B, h, w)
-        uint8_t* o = a.lv[0] + ((size_t)frame * a.h + y0) * a.w + x0;
-#pragma unroll
-        for (int r = 0; r < kPyrTile; ++r) {
-            if (y0 + r < a.h && cnt > 0) {
-                uint8_t* p = o + (size_t)r * a.w;
-                if (a.vec0 && cnt >= kPyrTile) {
-                    *reinterpret_cast<uint32_t*>(p) = q[r][0] | (q[r][1] << 8) | (q[r][2] << 16) | (q[r][3] << 24);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < kPyrTile; ++k)
-                        if (k < cnt) p[k] = (uint8_t)q[r][k];
-                }
-            }
-        }
-    }
-    if (a.levels < 2) return;
-    uint32_t q1[2][2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int k = 0; k < 2; ++k) q1[r][k] = (q[2 * r][2 * k] + q[2 * r][2 * k + 1] + q[2 * r + 1][2 * k] + q[2 * r + 1][2 * k + 1] + 2u) >> 2;
-    {   // level 1: (B, h >> 1, w >> 1); a pixel that exists has its four sources inside the crop
-        const int h1 = a.h >> 1, w1 = a.w >> 1, c1 = w1 - 2 * tx;
-        uint8_t* o = a.lv[1] + ((size_t)frame * h1 + 2 * ty) * w1 + 2 * tx;
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            if (2 * ty + r < h1 && c1 > 0) {
-                uint8_t* p = o + (size_t)r * w1;
-                if (a.vec1 && c1 >= 2) {
-                    *reinterpret_cast<uint16_t*>(p) = (uint16_t)(q1[r][0] | (q1[r][1] << 8));
-                } else {
-                    p[0] = (uint8_t)q1[r][0];
-                    if (c1 >= 2) p[1] = (uint8_t)q1[r][1];
-                }
-            }
-        }
-    }
-    if (a.levels < 3) return;
-    const uint32_t q2 = (q1[0][0] + q1[0][1] + q1[1][0] + q1[1][1] + 2u) >> 2;
-    {
-        const int h2 = a.h >> 2, w2 = a.w >> 2;
-        if (ty < h2 && tx < w2) a.lv[2][((size_t)frame * h2 + ty) * w2 + tx] = (uint8_t)q2;
-    }
-    if (a.levels < 4) return;                                                                   // wave-uniform: every lane reaches the exchanges
-    uint32_t s = q2 + (uint32_t)__shfl_xor((int)q2, 1);
-    s += (uint32_t)__shfl_xor((int)s, kPyrLanesX);
-    {
-        const int h3 = a.h >> 3, w3 = a.w >> 3;
-        if (!(lane & 1) && !(lane & kPyrLanesX) && (ty >> 1) < h3 && (tx >> 1) < w3)
-            a.lv[3][((size_t)frame * h3 + (ty >> 1)) * w3 + (tx >> 1)] = (uint8_t)((s + 2u) >> 2);
-    }
+    pyramid_tail(a, frame, lane, tx, ty, q);
 }
 
 // ---- search -------------------------------------------------------------------------------------------------------------------------------

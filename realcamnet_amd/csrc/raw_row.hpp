@@ -241,4 +241,18 @@ inline int raw_pitch(const char* who, const char* name, const void* p, int pitch
     return RC_OK;
 }
 
+// A gain given on the host (`host_gain`: it is; `how` names that way in the message) or as (gain_batch) floats on the device, not both.
+inline int raw_gain(const char* who, const char* how, bool host_gain, float host_value, const float* d_gain, int gain_batch, int batch) {
+    const std::string at = std::string(who) + ": ";
+    RC_REQUIRE(!(host_gain && d_gain), at + "the gain is given both ways (" + how + " and d_gain)");
+    if (d_gain) {
+        RC_REQUIRE(gain_batch == 1 || gain_batch == batch, at + "gain_batch must be 1 or the batch");
+        RC_REQUIRE(reinterpret_cast<uintptr_t>(d_gain) % 4 == 0, at + "the gain must be 4-byte aligned");
+    } else {
+        RC_REQUIRE(gain_batch == 0, at + "gain_batch without d_gain must be 0");
+        if (host_gain) RC_REQUIRE(std::isfinite(host_value) && host_value > 0.f, at + "the gain must be finite and > 0");
+    }
+    return RC_OK;
+}
+
 }  // namespace rc

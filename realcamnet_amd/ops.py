@@ -723,6 +723,26 @@ def raw_temporal(mosaic: torch.Tensor, raw_format, prev: Optional[torch.Tensor] 
     return out
 
 
+def _pyramid_out(what, levels, frame=None, out=None):
+    """The two pyramid ops' checks: `levels` is an int in 1 .. 4 (all that is checked before the op has looked at its source); then, with `frame`
+    = (the checked source, h, w of level 0), the coarsest level is not empty and `out` is the levels' tensors, or None: allocated -> out."""
+    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= _lib.RC_MOTION_MAX_LEVELS:
+        raise ValueError(f"{what}: levels must be an int in 1 .. {_lib.RC_MOTION_MAX_LEVELS}, got {levels!r}")
+    if frame is None:
+        return None
+    x, h, w = frame
+    if (h >> (levels - 1)) < 1 or (w >> (levels - 1)) < 1:
+        raise ValueError(f"{what}: level {levels - 1} of a frame of {(h, w)} is empty")
+    shapes = [(x.shape[0], h >> k, w >> k) for k in range(levels)]
+    if out is None:
+        return [x.new_empty(s, dtype=torch.uint8) for s in shapes]
+    out = list(out)
+    if len(out) != levels or not all(isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and tuple(t.shape) == s and t.device == x.device and t.is_contiguous()
+                                     for t, s in zip(out, shapes)):
+        raise ValueError(f"{what}: out must be {levels} contiguous uint8 tensors of shapes {shapes} on {x.device}")
+    return out
+
+
 def raw_motion_pyramid(mosaic: torch.Tensor, raw_format, levels: int, gain=None, out=None):
     """A sensor frame as `raw_format` (a RawFormat) describes it -> the pyramid of its luma proxy: a list of `levels` (1 .. 4) uint8 tensors,
     level k (B, h >> k, w >> k) for a mosaic of (2h, 2w) samples.  Level 0 holds one code per Bayer cell: the square root of the cell's mean
@@ -734,12 +754,10 @@ def raw_motion_pyramid(mosaic: torch.Tensor, raw_format, levels: int, gain=None,
     looked at."""
     from .raw_format import CFAS
     _raw_stages(raw_format, "raw_motion_pyramid", ("temporal", "calibration"))
-    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= _lib.RC_MOTION_MAX_LEVELS:
-        raise ValueError(f"raw_motion_pyramid: levels must be an int in 1 .. {_lib.RC_MOTION_MAX_LEVELS}, got {levels!r}")
+    _pyramid_out("raw_motion_pyramid", levels)
     mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format)
-    b, h, w = mosaic.shape[0], h2 // 2, w2 // 2
-    if (h >> (levels - 1)) < 1 or (w >> (levels - 1)) < 1:
-        raise ValueError(f"raw_motion_pyramid: level {levels - 1} of a frame of {(h, w)} cells is empty")
+    b = mosaic.shape[0]
+    out = _pyramid_out("raw_motion_pyramid", levels, (mosaic, h2 // 2, w2 // 2), out)     # in cells
     dev_gain, host_gain = None, []
     if isinstance(gain, torch.Tensor):
         if gain.dtype != torch.float32 or gain.dim() != 2 or gain.shape[1] != 1 or gain.shape[0] not in (1, b):
@@ -751,14 +769,6 @@ def raw_motion_pyramid(mosaic: torch.Tensor, raw_format, levels: int, gain=None,
         if not (math.isfinite(gain) and gain > 0.0):
             raise ValueError(f"raw_motion_pyramid: gain must be finite and > 0, got {gain!r}")
         host_gain = [float(gain)]
-    shapes = [(b, h >> k, w >> k) for k in range(levels)]
-    if out is None:
-        out = [mosaic.new_empty(s, dtype=torch.uint8) for s in shapes]
-    else:
-        out = list(out)
-        if len(out) != levels or not all(isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and tuple(t.shape) == s and t.device == mosaic.device
-                                         and t.is_contiguous() for t, s in zip(out, shapes)):
-            raise ValueError(f"raw_motion_pyramid: out must be {levels} contiguous uint8 tensors of shapes {shapes} on {mosaic.device}")
     _R.raw_motion_pyramid(mosaic, dev_gain, out, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), float(raw_format.white_level), host_gain)
     return out
 
@@ -1061,23 +1071,13 @@ def motion_pyramid(y: torch.Tensor, levels: int, matrix: str = "bt709", crop_hw:
     is fixed in include/realcam_hip.h).  `out`: an optional list of such tensors to write.  One launch reads the frame once; stateless and
     capturable."""
     from .out_format import MATRICES
-    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= _lib.RC_MOTION_MAX_LEVELS:
-        raise ValueError(f"motion_pyramid: levels must be an int in 1 .. {_lib.RC_MOTION_MAX_LEVELS}, got {levels!r}")
+    _pyramid_out("motion_pyramid", levels)
     if not isinstance(matrix, str) or matrix not in MATRICES:
         raise ValueError(f"motion_pyramid: matrix must be one of {sorted(MATRICES)}, got {matrix!r}")
     y, h, w = _planar_source(y, "motion_pyramid", crop_hw)
     if y.shape[2] * y.shape[3] >= 1 << 29:
         raise ValueError(f"motion_pyramid: a source plane of {tuple(y.shape[2:])} has 2^29 samples or more")
-    if (h >> (levels - 1)) < 1 or (w >> (levels - 1)) < 1:
-        raise ValueError(f"motion_pyramid: level {levels - 1} of a {(h, w)} frame is empty")
-    shapes = [(y.shape[0], h >> k, w >> k) for k in range(levels)]
-    if out is None:
-        out = [y.new_empty(s, dtype=torch.uint8) for s in shapes]
-    else:
-        out = list(out)
-        if len(out) != levels or not all(isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and tuple(t.shape) == s and t.device == y.device and t.is_contiguous()
-                                         for t, s in zip(out, shapes)):
-            raise ValueError(f"motion_pyramid: out must be {levels} contiguous uint8 tensors of shapes {shapes} on {y.device}")
+    out = _pyramid_out("motion_pyramid", levels, (y, h, w), out)
     _R.motion_pyramid(y, out, MATRICES[matrix], h, w)
     return out
 

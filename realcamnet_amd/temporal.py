@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-# The kernel's lane map (csrc/temporal.hip): a lane holds LANE_PX consecutive samples of a row, a wave loads WAVE_SPAN columns and produces
+# The kernel's lane map (csrc/temporal_kernel.hpp): a lane holds LANE_PX consecutive samples of a row, a wave loads WAVE_SPAN columns and produces
 # WAVE_OUT of them (strips overlap by one lane at either end, so strip s starts at column s WAVE_OUT), a block holds BLOCK_STRIPS strips of
 # BLOCK_ROWS rows.  Tests place widths and heights on these seams.
 LANE_PX = 4

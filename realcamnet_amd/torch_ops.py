@@ -440,17 +440,24 @@ def _hdr_launch(out, src, times, storage, cfa, width, black, exposures, lines, h
 define("raw_hdr_merge(Tensor src, Tensor? times, int storage, int cfa, int width, float[] black, int exposures, bool lines, float[] host_times, "
        "float[] knee, float[] motion) -> Tensor", _hdr_alloc, _hdr_launch)
 
-def _temporal_launch(ret, src, prev, gain, out, storage, cfa, width, black, params, host_gain):
+def _temporal_descs(what, src, prev, gain, out, storage, cfa, width, black, params, host_gain):
+    """What the two temporal launches check and build alike -> (src as the library reads it, its RawFormatDesc, the TemporalDesc)."""
     if len(params) != 4 or len(host_gain) not in (0, 1) or (gain is not None and host_gain):
-        raise ValueError(f"realcam::raw_temporal: params holds n_abs, n_rel, alpha, ramp, the gain one host number or a tensor; "
+        raise ValueError(f"realcam::{what}: params holds n_abs, n_rel, alpha, ramp, the gain one host number or a tensor; "
                          f"got {params!r}, {host_gain!r}")
     b, h2, _ = src.shape
     if out.dtype != torch.float32 or tuple(out.shape) != (b, h2, width) or (prev is not None and (prev.dtype != torch.float32 or prev.shape != out.shape)):
-        raise ValueError(f"realcam::raw_temporal: prev and out must be ({b}, {h2}, {width}) fp32, got {None if prev is None else tuple(prev.shape)} and {tuple(out.shape)}")
+        raise ValueError(f"realcam::{what}: prev and out must be ({b}, {h2}, {width}) fp32, got {None if prev is None else tuple(prev.shape)} and {tuple(out.shape)}")
     src, f = _raw_source(src, storage, cfa, width, black, 0.0)
-    d = _lib.TemporalDesc(flags=(_lib.RC_TNR_RESET if prev is None else 0) | (_lib.RC_TNR_GAIN if host_gain and prev is not None else 0),
-                          noise_abs=float(params[0]), noise_rel=float(params[1]), alpha=float(params[2]), ramp=float(params[3]),
-                          gain=float(host_gain[0]) if host_gain and prev is not None else 0.0)
+    host = bool(host_gain) and prev is not None                # a reset takes no gain
+    d = _lib.TemporalDesc(flags=(_lib.RC_TNR_RESET if prev is None else 0) | (_lib.RC_TNR_GAIN if host else 0), noise_abs=float(params[0]),
+                          noise_rel=float(params[1]), alpha=float(params[2]), ramp=float(params[3]), gain=float(host_gain[0]) if host else 0.0)
+    return src, f, d
+
+
+def _temporal_launch(ret, src, prev, gain, out, storage, cfa, width, black, params, host_gain):
+    b, h2, _ = src.shape
+    src, f, d = _temporal_descs("raw_temporal", src, prev, gain, out, storage, cfa, width, black, params, host_gain)
     use_gain = gain is not None and prev is not None           # a reset reads nothing but the frame
     check(lib().rc_raw_temporal(src.data_ptr(), C.byref(f), C.byref(d), _p(prev), 0 if prev is None else 4 * prev.stride(1),
                                 gain.data_ptr() if use_gain else None, gain.shape[0] if use_gain else 0, out.data_ptr(), 4 * out.stride(1),
@@ -464,18 +471,11 @@ define("raw_temporal(Tensor src, Tensor? prev, Tensor? gain, Tensor(a!) out, int
        "float[] host_gain) -> Tensor", lambda src, prev, gain, out, storage, cfa, width, black, params, host_gain: out.new_empty((0,)), _temporal_launch)
 
 def _temporal_mc_launch(ret, src, prev, gain, vectors, out, storage, cfa, width, black, params, host_gain, block):
-    if len(params) != 4 or len(host_gain) not in (0, 1) or (gain is not None and host_gain):
-        raise ValueError(f"realcam::raw_temporal_mc: params holds n_abs, n_rel, alpha, ramp, the gain one host number or a tensor; "
-                         f"got {params!r}, {host_gain!r}")
     b, h2, _ = src.shape
-    if out.dtype != torch.float32 or tuple(out.shape) != (b, h2, width) or prev.dtype != torch.float32 or prev.shape != out.shape:
-        raise ValueError(f"realcam::raw_temporal_mc: prev and out must be ({b}, {h2}, {width}) fp32, got {tuple(prev.shape)} and {tuple(out.shape)}")
     if vectors.dtype != torch.int32 or vectors.dim() != 4 or vectors.shape[0] != b or vectors.shape[1] < 1 or vectors.shape[2] < 1 or vectors.shape[3] != 4 \
             or not vectors.is_contiguous():
         raise ValueError(f"realcam::raw_temporal_mc: vectors must be a contiguous ({b}, by, bx, 4) int32 tensor, got {tuple(vectors.shape)} {vectors.dtype}")
-    src, f = _raw_source(src, storage, cfa, width, black, 0.0)
-    d = _lib.TemporalDesc(flags=_lib.RC_TNR_GAIN if host_gain else 0, noise_abs=float(params[0]), noise_rel=float(params[1]), alpha=float(params[2]),
-                          ramp=float(params[3]), gain=float(host_gain[0]) if host_gain else 0.0)
+    src, f, d = _temporal_descs("raw_temporal_mc", src, prev, gain, out, storage, cfa, width, black, params, host_gain)
     check(lib().rc_raw_temporal_mc(src.data_ptr(), C.byref(f), C.byref(d), prev.data_ptr(), 4 * prev.stride(1), _p(gain), 0 if gain is None else gain.shape[0],
                                    out.data_ptr(), 4 * out.stride(1), b, h2 // 2, width // 2, vectors.data_ptr(), vectors.shape[1], vectors.shape[2], block,
                                    _stream()), "rc_raw_temporal_mc")

@@ -4,6 +4,7 @@ against theory, the branch shares of the GPU branch test's input, validation, th
 bad-argument table, a FakeTensorMode trace and the kernels' resources."""
 import ctypes as C
 import dataclasses
+import re
 
 import numpy as np
 import pytest
@@ -434,9 +435,11 @@ def test_raw_temporal_is_declared_bound_and_exported():
     assert f"#define RC_TNR_RESET {_lib.RC_TNR_RESET}" in header and f"#define RC_TNR_GAIN {_lib.RC_TNR_GAIN}" in header
     t = M.temporal
     assert (t.LANE_PX, t.WAVE_SPAN, t.WAVE_OUT, t.BLOCK_STRIPS, t.BLOCK_ROWS) == (4, 256, 248, 2, 32)
-    src = (_lib.PKG / "csrc" / "temporal.hip").read_text()                         # the constants the GPU tests place their seams on
+    src = (_lib.PKG / "csrc" / "temporal_kernel.hpp").read_text()                  # the constants the GPU tests place their seams on
     assert ("kTnrPx = 4" in src and "kTnrSpan = 64 * kTnrPx" in src and "kTnrOut = kTnrSpan - 2 * kTnrPx" in src and "kTnrRows = 32" in src
             and "kTnrStrips = kTnrWaves / 2" in src and "kTnrWaves = 4" in src)
+    for name in ("temporal.hip", "temporal_mc.hip"):                               # one lane map: neither file defines a constant of its own
+        assert not re.search(r"\bk(Tnr|Tmc)\w* *=[^=]", (_lib.PKG / "csrc" / name).read_text()), name
 
 
 def test_raw_temporal_kernels_exist_and_do_not_spill():

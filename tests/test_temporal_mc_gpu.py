@@ -20,7 +20,7 @@ from realcamnet_amd.calibration import Calibration
 from realcamnet_amd.exposures import Exposures
 from realcamnet_amd.temporal import BLOCK_ROWS, WAVE_OUT, WAVE_SPAN, Temporal, TemporalMotion, TemporalState
 from temporal_ref import F32, blacks_of, branch_shares, restated_temporal
-from test_hdr_gpu import BLACKS, STORAGE_ID, delivered, same
+from test_hdr_gpu import BLACKS, KINDS, STORAGE_ID, delivered, same
 from test_temporal_host import request_of, scale_of, stream_of
 
 DEV = "cuda"
@@ -355,6 +355,36 @@ def test_a_zero_field_gives_the_bits_of_the_filter_without_vectors(hip):
         vec[..., 2:] = 12345                                                       # cost and texture are not looked at
         assert same(ops.raw_temporal(dev, fmt, prev=prev, vectors=vec, block=block), plain), kind
         assert float((plain.cpu() != decoded(src, fields["storage"], fields.get("width"))).float().mean()) > 0.3
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+def test_the_two_fetches_of_the_state_agree_for_every_storage_and_alignment_of_the_state(hip, kind):
+    """The two kernels share one body (csrc/temporal_kernel.hpp) and differ in the fetch of the state alone: with a zero field they give the
+    same bits wherever the state lies.  36 x 262 samples in a batch of 2: a band seam (32 rows), a strip seam (248 columns) and a last lane
+    of two samples; RAW10 needs a width that is 0 mod 4 and takes 260.  The state, as (lead, pad) samples in front of and behind each row:
+    dense; rows of 0 mod 16 bytes on a base of 0 mod 16 (16-byte loads in both kernels); the same 8 bytes on (the plain kernel goes sample by
+    sample, the other loads 16 bytes at 8 mod 16 and 8-byte pairs); 4 bytes on with a pitch of 4 mod 8 (both sample by sample)."""
+    b, h2, w2, block = 2, BLOCK_ROWS + 4, WAVE_OUT + (12 if kind == "mipi10" else 14), 16
+    assert (h2, w2) == (36, 260 if kind == "mipi10" else 262)
+    host, state = stream_of(kind, b, h2, w2, 640, BLACKS[1])
+    src, fields = delivered(kind, host)
+    t, levels = request_of(kind), levels_of(kind, BLACKS[1])
+    fmt = M.RawFormat(black_level=levels, white_level=scale_of(kind), temporal=t, **fields)
+    want = restated_temporal(decoded(src, fields["storage"], fields.get("width")), state, blacks_of(levels, h2, w2), t.params())
+    dev = src.to(DEV)
+    vec = torch.zeros(b, *grid_of(h2, w2, block, "fit"), 4, dtype=torch.int32, device=DEV)
+    seen = set()
+    for lead, pad in ((0, 0), (0, -w2 % 4), (2, -(w2 + 2) % 4), (1, 0)):
+        buf = torch.full((b, h2, lead + w2 + pad), -3.0, device=DEV)
+        prev = buf[..., lead:lead + w2]
+        prev.copy_(state)
+        base, pitch = prev.data_ptr(), 4 * prev.stride(1)
+        seen.add((base % 16, pitch % 16 if base % 8 == 0 else pitch % 8))
+        plain = ops.raw_temporal(dev, fmt, prev=prev)
+        assert torch.equal(ops.raw_temporal(dev, fmt, prev=prev, vectors=vec, block=block), plain), (kind, lead, pad)
+        assert same(plain, want), (kind, lead, pad, (plain.cpu() != want).nonzero()[:8].tolist())
+    assert seen >= {(0, 0), (8, 0), (4, 4)} and (kind == "mipi10" or (0, 8) in seen), seen
 
 
 @pytest.mark.gpu

@@ -6,6 +6,7 @@ the noise and the uncompensated one does not."""
 import ctypes as C
 import dataclasses
 import math
+import re
 
 import numpy as np
 import pytest
@@ -348,9 +349,15 @@ def test_the_entries_are_declared_bound_and_exported_and_the_lane_map_is_tempora
     for op in ("raw_motion_pyramid", "raw_temporal_mc"):
         assert op in M.torch_ops.SCHEMAS and hasattr(torch.ops.realcam, op)
     src = (_lib.PKG / "csrc" / "temporal_mc.hip").read_text()                      # the lane map is temporal.hip's: the GPU tests share its seams
-    assert ("kTmcPx = 4" in src and "kTmcSpan = 64 * kTmcPx" in src and "kTmcOut = kTmcSpan - 2 * kTmcPx" in src and "kTmcRows = 32" in src
-            and "kTmcStrips = kTmcWaves / 2" in src and "kTmcWaves = 4" in src)
-    assert "__shared__" not in src and "atomic" not in src.replace("no atomics", "")
+    shared = (_lib.PKG / "csrc" / "temporal_kernel.hpp").read_text()               # ... as the one set of constants both kernels are built from
+    assert ("kTnrPx = 4" in shared and "kTnrSpan = 64 * kTnrPx" in shared and "kTnrOut = kTnrSpan - 2 * kTnrPx" in shared and "kTnrRows = 32" in shared
+            and "kTnrStrips = kTnrWaves / 2" in shared and "kTnrWaves = 4" in shared)
+    for name in ("temporal.hip", "temporal_mc.hip"):                               # neither file defines a lane-map constant of its own
+        assert not re.search(r"\bk(Tnr|Tmc)\w* *=[^=]", (_lib.PKG / "csrc" / name).read_text()), name
+    tail = (_lib.PKG / "csrc" / "pyramid_tail.hpp").read_text()
+    assert not re.search(r"\bk(Pyr|Rp)\w* *=[^=]", src + (_lib.PKG / "csrc" / "motion.hip").read_text()) and "kPyrTile = 4" in tail      # and one pyramid map
+    for text in (src, shared, tail):
+        assert "__shared__" not in text and "atomic" not in text.replace("no atomics", "")
 
 
 def test_the_kernels_exist_for_every_storage_and_use_no_scratch():
