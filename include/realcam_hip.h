@@ -137,7 +137,19 @@ int rc_rgb_encode(const void* d_src, int src_dtype, void* d_dst, int out_bits, i
 typedef enum rc_yuv_layout {
     RC_YUV_NV12 = 0,   /* uint8: Y plane, then one plane of interleaved Cb,Cr pairs at half size, same pitch */
     RC_YUV_P010 = 1,   /* NV12's planes as uint16, the 10-bit code in the HIGH bits (code << 6); pitch and offsets still in bytes */
-    RC_YUV_I420 = 2    /* uint8: Y, Cb, Cr planes; the chroma pitch is pitch / 2 */
+    RC_YUV_I420 = 2,   /* uint8: Y, Cb, Cr planes; the chroma pitch is pitch / 2 */
+    /* 3..15 are not layouts.  The professional video surfaces (additive; see rc_yuv_encode): */
+    RC_YUV_NV16 = 16,  /* 4:2:2  8 bit: uint8 Y plane, then an interleaved CbCr plane of as many rows, same pitch */
+    RC_YUV_P210 = 17,  /* 4:2:2 10 bit: NV16's planes as uint16, code << 6 */
+    RC_YUV_I422 = 18,  /* 4:2:2  8 bit: uint8 Y, Cb, Cr planes; the chroma pitch is pitch / 2 (yuv422p) */
+    RC_YUV_I210 = 19,  /* 4:2:2 10 bit: I422's planes as uint16, the code in the LOW bits (yuv422p10le) */
+    RC_YUV_I010 = 20,  /* 4:2:0 10 bit: I420's planes as uint16, the code in the LOW bits (yuv420p10le) */
+    RC_YUV_I444 = 21,  /* 4:4:4  8 bit: three uint8 planes, all at `pitch` (yuv444p) */
+    RC_YUV_I410 = 22,  /* 4:4:4 10 bit: the same as uint16, the code in the LOW bits (yuv444p10le) */
+    RC_YUV_YUY2 = 23,  /* 4:2:2  8 bit, one plane: bytes Y0 Cb Y1 Cr per pixel pair */
+    RC_YUV_UYVY = 24,  /* 4:2:2  8 bit, one plane: bytes Cb Y0 Cr Y1 */
+    RC_YUV_Y210 = 25,  /* 4:2:2 10 bit, one plane: YUY2's order as uint16, code << 6 */
+    RC_YUV_V210 = 26   /* 4:2:2 10 bit, one plane: six pixels in four little-endian dwords (below) */
 } rc_yuv_layout;
 typedef enum rc_yuv_matrix { RC_MATRIX_BT601 = 0, RC_MATRIX_BT709 = 1, RC_MATRIX_BT2020 = 2 /* its luma coefficients only: no gamut conversion */ } rc_yuv_matrix;
 typedef enum rc_yuv_range { RC_RANGE_LIMITED = 0, RC_RANGE_FULL = 1 } rc_yuv_range;
@@ -153,7 +165,7 @@ typedef struct rc_out_format {
     int matrix;            /* rc_yuv_matrix */
     int range;             /* rc_yuv_range */
     int siting;            /* rc_chroma_siting */
-    int pitch;             /* bytes from one Y row to the next, >= the row's bytes, a multiple of the sample size (I420: even); 0: exactly the
+    int pitch;             /* bytes from one Y row to the next, >= the row's bytes, a multiple of the sample size (I420: even; V210: 4); 0: exactly the
                               row's bytes.  A multiple of 16 (with 16-byte aligned offsets) takes the 16-byte store path */
     int rows;              /* allocated rows of the Y plane, >= h; 0: h.  A chroma plane has ceil(rows / 2) allocated rows */
     int chroma_offset[2];  /* bytes from the frame's start to the CbCr plane (NV12 / P010) or the Cb and Cr planes (I420); 0: packed behind
@@ -175,7 +187,23 @@ size_t rc_yuv_frame_bytes(const rc_out_format* fmt, int h, int w);
  *   code = clamp(rint(v S + O), lo, hi), round half to even; n = 8 or 10 bits, k = 2^(n-8):
  *     LIMITED  Y: S 219k, O 16k, [16k, 235k]; chroma: S 224k, O 128k, [16k, 240k].  FULL  S 2^n - 1, O 0 (Y) / 2^(n-1) (chroma), [0, 2^n - 1]
  * Every byte of the Y plane's rows x pitch and of the chroma planes' ceil(rows / 2) x pitch that is not a sample is written as zero.
- * Odd h / w, a pitch below the row's bytes, overlapping planes, a misaligned d_dst: RC_ERR_INVALID before any launch. */
+ * Odd h / w, a pitch below the row's bytes, overlapping planes, a misaligned d_dst: RC_ERR_INVALID before any launch.
+ *
+ * The layouts from RC_YUV_NV16 on (4:2:2, 4:4:4, planar 10 bit, packed, V210) share the steps above -- clamp, Y / Cb / Cr, code at
+ * n = 8 or 10 -- and differ in the chroma step and in the storage:
+ *   4:2:2 of the unquantised Cb, Cr, per row, for columns 2i, 2i+1:
+ *     CENTER  (c[2i] + c[2i+1]) 0.5
+ *     LEFT    ((c[x-1] + c[x+1]) + (c[x] + c[x])) 0.25 with x = 2i, x-1 clamped to column 0: the row step t of the 4:2:0 LEFT rule
+ *   4:4:4: no chroma step, `siting` is not used (it must still be a valid value).  I010: the 4:2:0 rule above at n = 10.
+ *   Sizes: I010 needs an even h and w; every 4:2:2 layout an even w, any h; 4:4:4 any size.
+ *   chroma_offset[]: the CbCr plane (NV16 / P210, [1] zero), the Cb and Cr planes (I422 / I210 / I010 / I444 / I410); both zero for the
+ *   one-plane layouts YUY2 / UYVY / Y210 / V210.  A chroma plane of 4:2:2 / 4:4:4 has `rows` allocated rows; the chroma pitch is
+ *   pitch / 2 for I422 / I210 / I010 (pitch a multiple of twice the sample size) and pitch for the others.
+ *   pitch 0 is the tight row: w samples (planar, semi-planar), 2 w samples (YUY2 / UYVY / Y210), ceil(w / 6) 16 bytes (V210).
+ *   V210: each group of six pixels Y0..Y5, Cb0..Cb2, Cr0..Cr2 is four dwords, bits 30-31 zero, the 10-bit codes unshifted:
+ *     w0 = Cb0 | Y0 << 10 | Cr0 << 20;  w1 = Y1 | Cb1 << 10 | Y2 << 20;  w2 = Cr1 | Y3 << 10 | Cb2 << 20;  w3 = Y4 | Cr2 << 10 | Y5 << 20
+ *     The fields of samples a last group does not have are zero.  Any pitch >= ceil(w / 6) 16 that is a multiple of 4 is taken.
+ *   As above, every byte of the allocated rows x pitch of every plane that is not a sample is written as zero by the one launch. */
 int rc_yuv_encode(const void* d_src, int src_dtype, const rc_out_format* fmt, void* d_dst, int batch, int H, int W, int h, int w, void* stream);
 
 /* ---- JPEG out (ABI 15, additive): the same planar result as one baseline JFIF file per frame, coded on the device ------------------------

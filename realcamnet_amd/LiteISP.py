@@ -426,7 +426,7 @@ def _out_bits(out_format):
 
 def _encode(y, bits):
     """out_format: the planar float sRGB (B,3,2h,2w) as it is, interleaved (B,2h,2w,3) uint8 / uint16 (rc_rgb_encode), a YuvFrames
-    holding one Y'CbCr 4:2:0 surface per frame (rc_yuv_encode), a JpegFrames holding one JFIF file per frame (rc_jpeg_encode), a
+    holding one Y'CbCr 4:2:0 / 4:2:2 / 4:4:4 surface per frame (rc_yuv_encode), a JpegFrames holding one JFIF file per frame (rc_jpeg_encode), a
     FrameStats (rc_frame_stats) or a MotionField (_motion)."""
     if bits is None:
         return y
@@ -621,7 +621,7 @@ class _DwtUNet(nn.Module):
         kernel (ops.raw_ingest) also produces cond = bilinear resize of the normalised packed RAW to `cond_hw`.
         raw_format (a RawFormat): the sensor frame's CFA phase, storage (MIPI RAW10 / RAW12 lines: (B,[1,]2h,line_bytes) uint8) and
         per-position levels.  out_format "rgb8" / "rgb16": the result as interleaved (B,2h,2w,3) uint8 / uint16; an OutFormat: a YuvFrames
-        (one NV12 / P010 / I420 encoder surface per frame, and views of its planes); a Stats: a FrameStats (the histograms and the 3A zone
+        (one encoder surface per frame -- NV12 / P010 / I420, or a 4:2:2 / 4:4:4 / planar 10-bit / packed / v210 layout of OutFormat -- and views of its planes); a Stats: a FrameStats (the histograms and the 3A zone
         grid of the result, ops.frame_stats, in place of a picture); a Jpeg: a JpegFrames (one baseline JFIF file per frame, coded on the
         device, ops.jpeg_encode); a Motion: a MotionField (the block motion vectors of the result against the previous call's result, kept in
         the Motion's state; ops.motion_pyramid and ops.motion_estimate, in place of a picture).

@@ -21,6 +21,8 @@ ABI_VERSION = 15
 RC_RAW_F32, RC_RAW_BF16, RC_RAW_U16, RC_RAW_F16, RC_RAW_U8, RC_RAW_MIPI10, RC_RAW_MIPI12 = 0, 1, 2, 3, 4, 5, 6
 RC_CFA_RGGB, RC_CFA_BGGR, RC_CFA_GRBG, RC_CFA_GBRG = 0, 1, 2, 3
 RC_YUV_NV12, RC_YUV_P010, RC_YUV_I420 = 0, 1, 2
+(RC_YUV_NV16, RC_YUV_P210, RC_YUV_I422, RC_YUV_I210, RC_YUV_I010, RC_YUV_I444, RC_YUV_I410, RC_YUV_YUY2, RC_YUV_UYVY, RC_YUV_Y210,
+ RC_YUV_V210) = range(16, 27)            # 3..15 are not layouts
 RC_MATRIX_BT601, RC_MATRIX_BT709, RC_MATRIX_BT2020 = 0, 1, 2
 RC_RANGE_LIMITED, RC_RANGE_FULL = 0, 1
 RC_SITING_LEFT, RC_SITING_CENTER = 0, 1

@@ -8,6 +8,7 @@
 // the order the header states (__fmul_rn / __fadd_rn: no contraction whatever the compile flags say), so the vector path, the
 // element path and a plain elementwise restatement give the same bits.
 #include "ycc_code.hpp"
+#include "yuv_surface.hpp"
 
 namespace rc {
 
@@ -189,7 +190,8 @@ size_t rc_out_format_size(void) { return sizeof(rc_out_format); }
 
 size_t rc_yuv_frame_bytes(const rc_out_format* fmt, int h, int w) {
     YuvPlan p;
-    const char* err = yuv_plan(fmt, h, w, &p);
+    const bool surface = fmt && yuv_surface_layout(fmt->layout);     // the layouts of yuv_surface.hip
+    const char* err = surface ? yuv_surface_plan(fmt, h, w, &p.frame) : yuv_plan(fmt, h, w, &p);
     if (err) {
         fail(RC_ERR_INVALID, std::string("rc_yuv_frame_bytes: ") + err);
         return 0;
@@ -201,6 +203,7 @@ int rc_yuv_encode(const void* d_src, int src_dtype, const rc_out_format* fmt, vo
     RC_REQUIRE(d_src && fmt && d_dst, "rc_yuv_encode: null pointer");
     RgbSide src;
     if (int e = rgb_source("rc_yuv_encode", d_src, src_dtype, batch, H, W, h, w, &src)) return e;
+    if (yuv_surface_layout(fmt->layout)) return yuv_surface_encode(d_src, src_dtype, fmt, d_dst, batch, H, W, h, w, stream);
     YuvPlan p;
     const char* err = yuv_plan(fmt, h, w, &p);
     if (err) return fail(RC_ERR_INVALID, std::string("rc_yuv_encode: ") + err);

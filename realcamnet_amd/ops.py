@@ -800,6 +800,7 @@ def rgb_encode(y: torch.Tensor, bits: int, crop_hw: Optional[Tuple[int, int]] = 
 def yuv_encode(y: torch.Tensor, fmt, crop_hw: Optional[Tuple[int, int]] = None):
     """Planar float result (B,3,H,W), cropped to crop_hw (even), -> a YuvFrames: one Y'CbCr 4:2:0 encoder surface per frame (NV12 / P010 /
     I420 with the format's matrix, range, chroma siting, pitch and height alignment) in one allocation, and views of its planes.
+    The 4:2:2 layouts (nv16, p210, i422, i210, yuy2, uyvy, y210, v210) need only an even width, the 4:4:4 ones (i444, i410) take any size.
     One launch; padding bytes are zero (rc_yuv_encode; the arithmetic is fixed in include/realcam_hip.h)."""
     from .out_format import LAYOUTS, MATRICES, RANGES, SITINGS, OutFormat, YuvFrames
     if not isinstance(fmt, OutFormat):
@@ -812,7 +813,13 @@ def yuv_encode(y: torch.Tensor, fmt, crop_hw: Optional[Tuple[int, int]] = None):
     for p in pl.planes:
         v = buf[:, p.offset // es:(p.offset + p.pitch * p.alloc_rows) // es].unflatten(1, (p.alloc_rows, p.pitch // es))
         v = v[:, :p.rows, :p.valid_bytes // es]
-        views.append(v.unflatten(2, (w // 2, 2)) if p.name == "cbcr" else v)
+        if p.name == "cbcr":
+            v = v.unflatten(2, (w // 2, 2))
+        elif p.name in ("yuyv", "uyvy"):                  # memory order: Y0 Cb Y1 Cr / Cb Y0 Cr Y1 per pixel pair
+            v = v.unflatten(2, (w // 2, 4))
+        elif p.name == "v210":                            # the dwords of each group of six pixels
+            v = v.view(torch.int32).unflatten(2, (-(-w // 6), 4))
+        views.append(v)
     return YuvFrames(buf, tuple(views))
 
 

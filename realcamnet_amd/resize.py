@@ -104,7 +104,7 @@ class Output:
     optional colour look, an optional Sharpen, then its format.
 
     format  None (the planar float tensor), "rgb8" / "rgb16" (interleaved uint8 / uint16), an OutFormat (a YuvFrames), a Jpeg (a JpegFrames:
-            any size, the 4:2:0 evenness rule below is the encoder surfaces' alone) or a Stats (a FrameStats: the statistics of the frame after this output's own warp / resize / look, in place of a picture)
+            any size, the evenness rules below are the encoder surfaces' alone: even height and width for 4:2:0, even width for 4:2:2, none for 4:4:4) or a Stats (a FrameStats: the statistics of the frame after this output's own warp / resize / look, in place of a picture)
             or a Motion (a MotionField: the block motion vectors of that frame against the previous call's, in place of a picture).
     resize  None (the result's own size) or a Resize.
     look    None or a Lut3D, applied after the resize and before the encoder (ops.lut3d; with format None the looked tensor is fp32).
@@ -142,10 +142,13 @@ class Output:
         if tone is not None and not isinstance(tone, ToneMap):
             raise TypeError(f"Output.tone must be None or a ToneMap, got {type(tone).__name__}")
         object.__setattr__(self, "tone", tone)
-        if isinstance(f, OutFormat) and self.resize is not None and (self.resize.size[0] % 2 or self.resize.size[1] % 2):
-            raise ValueError(f"Output: 4:2:0 ({f.layout}) needs an even height and width, Resize.size is {self.resize.size}")
-        if isinstance(f, OutFormat) and self.resize is None and self.warp is not None and (self.warp.size[0] % 2 or self.warp.size[1] % 2):
-            raise ValueError(f"Output: 4:2:0 ({f.layout}) needs an even height and width, Warp.size is {self.warp.size} and no Resize follows it")
+        if isinstance(f, OutFormat) and f.subsampling != "444":          # each layout's own size rule; 4:4:4 takes any size
+            odd = (lambda s: s[0] % 2 or s[1] % 2) if f.subsampling == "420" else (lambda s: s[1] % 2)
+            needs = "4:2:0 ({}) needs an even height and width" if f.subsampling == "420" else "4:2:2 ({}) needs an even width"
+            if self.resize is not None and odd(self.resize.size):
+                raise ValueError(f"Output: {needs.format(f.layout)}, Resize.size is {self.resize.size}")
+            if self.resize is None and self.warp is not None and odd(self.warp.size):
+                raise ValueError(f"Output: {needs.format(f.layout)}, Warp.size is {self.warp.size} and no Resize follows it")
 
     def _key(self):
         return (self.format, self.resize, self.look, self.warp, self.sharpen, self.tone)
