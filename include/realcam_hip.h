@@ -841,6 +841,59 @@ size_t rc_quad_desc_size(void);
 int rc_raw_quad(const void* d_src, const rc_raw_format* fmt, const rc_quad_desc* desc, void* d_dst, int dst_pitch_bytes,
                 int batch, int H, int W, void* stream);
 
+/* ---- RAW-domain 3A statistics (ABI 15, additive): histograms and a zone grid of the sensor mosaic itself, per CFA colour --------------------
+ * What an auto-exposure, auto-white-balance or autofocus loop reads: linear, black-subtracted, in front of every gain (rc_frame_stats measures
+ * the network's result: sRGB-encoded, white-balanced by the gains the loop is looking for, clamped -- a clipped photosite can no longer be
+ * told there).  The tap of forward_mosaic is behind rc_raw_quad / rc_raw_defects / rc_raw_hdr_merge / rc_raw_temporal and in front of
+ * rc_raw_calibrate.
+ * Replaces: rc_raw_calibrate to an fp32 copy of the frame, four strided slices, a bincount per colour and a pooling pass per sum.  Here one
+ * launch over the bytes as delivered. */
+#define RC_RAW_STATS_SLOTS 8
+#define RC_RAW_STATS_MAX_GRID 64
+#define RC_RAW_STATS_MAX_HIST_BITS 10
+typedef struct rc_raw_stats_desc {
+    int roi[4];      /* cy0, cx0, rh, rw in Bayer CELLS; rh = rw = 0: the whole frame */
+    int grid[2];     /* gy, gx zones, 1 .. min(64, rh) and 1 .. min(64, rw) */
+    int bits;        /* 8 .. 16: codes 0 .. S, S = 2^bits - 1 */
+    int hist_bits;   /* 6 .. min(bits, 10): a histogram has 2^hist_bits bins */
+    float top;       /* the sample value that maps to S; > every black level */
+    int sat;         /* 1 .. 2^bits: a cell is saturated if max of its four codes >= sat; 2^bits: none */
+    int dark;        /* -1 .. S: a cell that is not saturated is dark if that max <= dark; -1: none */
+    int reserved[4]; /* zero */
+} rc_raw_stats_desc;
+size_t rc_raw_stats_desc_size(void);
+
+/* d_src: B frames of a mosaic (2h, 2w) as rc_raw_calibrate reads them (fmt: every storage, cfa, line_bytes, width, black; white is not looked
+ * at: `top` takes its place).  The ROI and the zones are in Bayer cells: cell (cy, cx) is the samples (2cy, 2cx), (2cy, 2cx+1), (2cy+1, 2cx),
+ * (2cy+1, 2cx+1), CFA positions pos = 0 .. 3 in that order (black[]'s order).  d_hist (B, 4, 2^hist_bits) and d_zones (B, gy, gx, 8), both
+ * int64, 8-byte aligned.  The colour index c is the packed map's slot order -- 0 R, 1 G of the R row (G1), 2 G of the B row (G2), 3 B; slot c
+ * reads the position of its colour in the cell, as rc_raw_ingest_fmt's packed map does -- which is the order of rc_calib_desc.gains, not the
+ * position order of black[].  Per frame, for the sample p at position pos with slot c:
+ *   1. v = float(p), exact for every storage; NaN counts as 0.
+ *   2. d = v - black[pos];  n = d k[pos], each rounded to fp32 on its own (no fused multiply-add), with
+ *      k[pos] = float(double(S) / (double(top) - double(black[pos]))) formed once on the host;  q = clamp(rint(n), 0, S), round half to even.
+ *      With top - black = S (black 0, white 1023, bits 10) q is the sensor's own code.  No value of p, +-inf included, makes an index leave a
+ *      table: +inf gives S, -inf gives 0.
+ *   3. hist[c][q >> (bits - hist_bits)] += 1 for every sample of the ROI.
+ *   4. cell (cy, cx) has the four codes qR, qG1, qG2, qB and m = max of them: it is saturated if m >= sat; otherwise dark if m <= dark;
+ *      otherwise valid.
+ *   5. g = (qG1 + qG2) >> (bits - 7), 0 .. 255.  Focus f = dx^2 + dy^2, dx = g[cy][min(cx+1, rw-1)] - g[cy][cx], dy = g[min(cy+1, rh-1)][cx]
+ *      - g[cy][cx] (ROI-relative indices): the neighbour is clamped to the ROI, not to the frame.
+ *   6. cell (cy, cx) of the ROI belongs to zone (floor(cy gy / rh), floor(cx gx / rw)), as in rc_frame_stats (zone column i is the columns
+ *      ceil(i rw / gx) .. ceil((i+1) rw / gx) - 1, never empty).  zones[j][i][0..7] = the valid cells; the sums of qR, of qG1, of qG2 and of
+ *      qB over the valid cells; the saturated cells; the dark cells; the sum of f over all cells of the zone.
+ * Everything after step 2 is integer arithmetic: the result does not depend on the order of summation, so it is bit-exact and the same from
+ * run to run although it is accumulated with atomics.  A mosaic holds fewer than 2^31 samples, so fewer than 2^29 cells; a code is at most
+ * 65535 and f at most 2 * 255^2, so every total stays below 2^46.
+ * Every element of both outputs is written: the entry point zeroes them on `stream` itself (the caller does not), then one launch adds.
+ * It keeps no device buffer of its own and is capturable; a graph replay starts from zero again.
+ * Null pointers, an unknown storage or cfa, a bad line_bytes or width, a misaligned source, non-finite black levels, a bad shape (empty, more
+ * than 65535 frames, a mosaic of 2^31 samples or more), bits, hist_bits, sat, dark or grid out of range, a top that is not finite, is at or
+ * below a black level or so close to one that k is not finite, an ROI outside the frame or with one zero side only, non-zero reserved (fmt's
+ * too), outputs not 8-byte aligned: RC_ERR_INVALID before anything is enqueued, with a message naming rc_raw_stats. */
+int rc_raw_stats(const void* d_src, const rc_raw_format* fmt, const rc_raw_stats_desc* desc, void* d_hist, void* d_zones,
+                 int batch, int h, int w, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

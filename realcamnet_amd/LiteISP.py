@@ -370,6 +370,11 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
     calibration.
     raw_format.quad (a QuadBayer): a Quad-Bayer sensor's frame is remosaiced or binned to a Bayer mosaic first (_quad), and everything
     else reads that.  The order is quad, merge (with its per-exposure repair), repair, temporal, calibration, ingest.
+    raw_format.stats (a RawStats): the mosaic that enters the calibration (or the ingest, where there is none) is measured by ops.raw_stats
+    (one launch, no state: allowed under graph capture) in the format the preceding stage left -- the frame as delivered, unpacked uint16
+    behind a repair, fp32 behind a merge or the filter -- and the RawFrameStats of this call is left in net.raw_stats, the way
+    net.defect_counts is.  Nothing else changes.  Other taps are the op on its own; per-exposure statistics are ops.raw_stats on the
+    (B E, 2h, X) view of the frame as delivered.
     A cond the caller supplies is used as it is: it is NOT corrected and NOT calibrated."""
     need_cond = hasattr(net, "classifier") and cond is None and not getattr(net, "cond_from_raw", False)
     if raw_format is not None and raw_format.temporal is not None:
@@ -387,6 +392,10 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
         raw_format = dataclasses.replace(raw_format, storage="float" if raw_format.storage == "float" else "u16", width=None, defects=None)
     if raw_format is not None and raw_format.temporal is not None:
         mosaic, raw_format = _temporal(mosaic, raw_format)
+    if raw_format is not None and raw_format.stats is not None:
+        import dataclasses
+        net.__dict__["raw_stats"] = ops.raw_stats(mosaic, raw_format)
+        raw_format = dataclasses.replace(raw_format, stats=None)
     if raw_format is not None and raw_format.calibration is not None:
         import dataclasses
         mosaic = ops.raw_calibrate(mosaic, raw_format, dtype=torch.float32)

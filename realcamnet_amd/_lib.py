@@ -41,6 +41,7 @@ RC_CALIB_GAINS, RC_CALIB_CLIP, RC_CALIB_MAX_KNOTS = 1, 2, 16
 RC_HDR_MOTION = 1
 RC_TNR_RESET, RC_TNR_GAIN = 1, 2
 RC_QUAD_REMOSAIC, RC_QUAD_BIN = 0, 1
+RC_RAW_STATS_SLOTS, RC_RAW_STATS_MAX_GRID, RC_RAW_STATS_MAX_HIST_BITS = 8, 64, 10
 
 
 class ConvDesc(C.Structure):
@@ -167,6 +168,14 @@ class QuadDesc(C.Structure):
     _fields_ = [("mode", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class RawStatsDesc(C.Structure):
+    """Mirror of `struct rc_raw_stats_desc`."""
+    _fields_ = [
+        ("roi", C.c_int32 * 4), ("grid", C.c_int32 * 2), ("bits", C.c_int32), ("hist_bits", C.c_int32), ("top", C.c_float), ("sat", C.c_int32),
+        ("dark", C.c_int32), ("reserved", C.c_int32 * 4),
+    ]
+
+
 def declared_symbols() -> list[str]:
     """Every function the public header declares (used by the CPU-side ABI test)."""
     text = HEADER.read_text()
@@ -222,6 +231,8 @@ _SIGS = {
     "rc_raw_temporal_mc": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(TemporalDesc), _P, _I, _P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     "rc_quad_desc_size": (_SZ, []),
     "rc_raw_quad": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(QuadDesc), _P, _I, _I, _I, _I, _P]),
+    "rc_raw_stats_desc_size": (_SZ, []),
+    "rc_raw_stats": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(RawStatsDesc), _P, _P, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

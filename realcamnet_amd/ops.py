@@ -628,6 +628,28 @@ def raw_calibrate(mosaic: torch.Tensor, raw_format, calibration=None, dtype: tor
                             [] if calibration.clip is None else list(calibration.clip), dtype)
 
 
+def raw_stats(mosaic: torch.Tensor, raw_format, stats=None):
+    """RAW-domain 3A statistics of the mosaic itself (rc_raw_stats; the arithmetic is fixed in include/realcam_hip.h): a sensor frame as
+    `raw_format` (a RawFormat) describes it -> a RawFrameStats: per CFA colour R, G1, G2, B (Calibration.gains' order) the code histograms
+    (B,4,2**hist_bits) and the 3A zone grid (B,gy,gx,8) of the RawStats `stats` (default: raw_format.stats), int64 on the device.  The codes are
+    linear and black-subtracted with raw_format's black levels, and in front of every gain: raw_format.calibration is not looked at.  The
+    frame is read once by one launch, as delivered (any storage, MIPI lines included); no device state, nothing is synchronised: capturable.
+    raw_format.quad / exposures / defects / temporal must be None: run those ops first and measure what they hand on (forward_mosaic
+    does); per-exposure statistics are this op on the (B E, 2h, X) view of the frames as delivered."""
+    from .raw_format import CFAS
+    from .raw_stats import RawFrameStats, RawStats
+    _raw_stages(raw_format, "raw_stats", ("calibration",))
+    stats = raw_format.stats if stats is None else stats
+    if not isinstance(stats, RawStats):
+        raise TypeError(f"raw_stats: stats must be a RawStats (or raw_format.stats set), got {type(stats).__name__}")
+    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format)
+    roi = stats.check(h2 // 2, w2 // 2)
+    top = stats.top_value(raw_format.white_level, raw_format.blacks())
+    hist, zones = _R.raw_stats(mosaic, storage, CFAS[raw_format.cfa], int(w2), list(raw_format.blacks()), list(roi), stats.grid[0], stats.grid[1],
+                               stats.bits, stats.hist_bits, top, stats.sat_code, stats.dark_code)
+    return RawFrameStats(hist, zones, stats, roi)
+
+
 def raw_hdr_merge(mosaic: torch.Tensor, raw_format, exposures=None) -> torch.Tensor:
     """Multi-exposure HDR merge on the mosaic itself, between the defects stage and the calibration (rc_raw_hdr_merge; the arithmetic is fixed
     in include/realcam_hip.h): the E = 2 .. 4 exposures of each frame as `raw_format` (a RawFormat) describes them -- (B,E,2h,X) for

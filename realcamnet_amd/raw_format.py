@@ -51,6 +51,11 @@ class RawFormat:
     calibration  None, or a Calibration: forward_mosaic then runs ops.raw_calibrate (a linearisation curve, these levels, a flat-field gain
                  map, white-balance gains, a clip) after the defects stage and ingests its fp32 result.  With a curve, black_level and
                  white_level are in the curve's linear units.  A gain map must have the node count the mosaic needs.
+    stats        None, or a RawStats: forward_mosaic measures the mosaic that enters the calibration (or the ingest, where there is none) --
+                 after quad, repair, merge and temporal, in linear black-subtracted codes and in front of the gains -- with ops.raw_stats
+                 (one launch: per CFA colour a code histogram and a 3A zone grid in Bayer cells) and leaves the RawFrameStats in
+                 net.raw_stats.  A measurement changes nothing the other stages do: every other op ignores the field.  The region and
+                 the grid are checked against the cell size (h, w) of what leaves the quad stage; RawStats.top defaults to white_level.
     """
 
     cfa: str = "RGGB"
@@ -60,6 +65,7 @@ class RawFormat:
     white_level: float = 1.0
     quad: Optional[object] = None
     temporal: Optional[object] = None
+    stats: Optional[object] = None
     exposures: Optional[object] = None
     defects: Optional[object] = None
     calibration: Optional[object] = None
@@ -171,6 +177,12 @@ class RawFormat:
             if self.calibration is not None and getattr(self.calibration, "curve", None) is not None:
                 raise ValueError("a Calibration.curve cannot follow temporal: the noise model needs linear samples -- linearise the frame first")
             self.temporal.check(h2, w2, shape[0])
+        if self.stats is not None:
+            from .raw_stats import RawStats
+            if not isinstance(self.stats, RawStats):
+                raise TypeError(f"RawFormat.stats must be None or a RawStats, got {type(self.stats).__name__}")
+            self.stats.check(h2 // 2, w2 // 2)
+            self.stats.top_value(self.white_level, self.blacks())
         if self.calibration is not None:
             from .calibration import Calibration
             if not isinstance(self.calibration, Calibration):

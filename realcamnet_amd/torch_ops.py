@@ -405,6 +405,27 @@ define("raw_calibrate(Tensor src, Tensor? gain_map, Tensor? frame_gains, int sto
        lambda src, gain_map, frame_gains, storage, cfa, width, black, white, curve_x, curve_y, cell, gains, clip, dtype:
        src.new_empty((src.shape[0], src.shape[1], width), dtype=dtype), _calib_launch)
 
+def _raw_stats_alloc(src, storage, cfa, width, black, roi, gy, gx, bits, hist_bits, top, sat, dark):
+    return (src.new_empty((src.shape[0], 4, 1 << hist_bits), dtype=torch.int64), src.new_empty((src.shape[0], gy, gx, _lib.RC_RAW_STATS_SLOTS), dtype=torch.int64))
+
+
+def _raw_stats_launch(outs, src, storage, cfa, width, black, roi, gy, gx, bits, hist_bits, top, sat, dark):
+    hist, zones = outs
+    b, h2, _ = src.shape
+    if len(roi) != 4:
+        raise ValueError(f"realcam::raw_stats: roi must be (cy0, cx0, rh, rw) in cells, got {roi!r}")
+    src, f = _raw_source(src, storage, cfa, width, black, 0.0)
+    d = _lib.RawStatsDesc(roi=(C.c_int32 * 4)(*roi), grid=(C.c_int32 * 2)(gy, gx), bits=bits, hist_bits=hist_bits, top=float(top), sat=sat, dark=dark)
+    check(lib().rc_raw_stats(src.data_ptr(), C.byref(f), C.byref(d), hist.data_ptr(), zones.data_ptr(), b, h2 // 2, width // 2, _stream()), "rc_raw_stats")
+
+
+# src (B, 2h, X) as raw_ingest_fmt takes it -> hist (B,4,2^hist_bits) and zones (B,gy,gx,8), int64: per CFA colour (R, G1, G2, B) the code
+# histograms and the 3A zone grid of the region roi = (cy0, cx0, rh, rw) in Bayer cells; top: the sample value that maps to 2^bits - 1; sat /
+# dark: code thresholds (2^bits / -1: none).  The outputs are not zeroed here: the entry point does that on the stream
+define("raw_stats(Tensor src, int storage, int cfa, int width, float[] black, int[] roi, int gy, int gx, int bits, int hist_bits, float top, "
+       "int sat, int dark) -> (Tensor, Tensor)", _raw_stats_alloc, _raw_stats_launch)
+
+
 def _hdr_alloc(src, times, storage, cfa, width, black, exposures, lines, host_times, knee, motion):
     return src.new_empty((src.shape[0], src.shape[1] // exposures if lines else src.shape[2], width), dtype=torch.float32)
 
