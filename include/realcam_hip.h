@@ -894,6 +894,60 @@ size_t rc_raw_stats_desc_size(void);
 int rc_raw_stats(const void* d_src, const rc_raw_format* fmt, const rc_raw_stats_desc* desc, void* d_hist, void* d_zones,
                  int batch, int h, int w, void* stream);
 
+/* ---- RAW noise measurement (ABI 15, additive): a photon-transfer curve of the sensor mosaic itself, per CFA colour ---------------------------
+ * What the noise models of rc_raw_temporal (noise_abs, noise_rel), rc_raw_defects (hot / cold) and rc_raw_hdr_merge (motion) are calibrated
+ * from: variance against level, taken from the flat parts of ordinary frames.  The region is cut into tiles of T x T Bayer cells; per tile and
+ * colour the energy of the differences of disjoint horizontal pairs is binned by the tile's level, and the low quantile of a level bin's
+ * energies is the energy of its flat tiles (texture only ever adds energy).  The tap of forward_mosaic is behind rc_raw_quad /
+ * rc_raw_defects / rc_raw_hdr_merge and IN FRONT of rc_raw_temporal: behind the filter the noise it is told about is gone.
+ * Replaces: an fp32 copy of the frame, four strided slices, an unfold and a quantile per level bin.  Here one launch over the bytes as
+ * delivered. */
+#define RC_RAW_NOISE_EBINS 320
+#define RC_RAW_NOISE_MAX_LEVEL_BITS 6
+typedef struct rc_raw_noise_desc {
+    int roi[4];      /* cy0, cx0, rh, rw in Bayer CELLS; rh = rw = 0: the whole frame.  cx0 even. */
+    int tile;        /* 4, 8 or 16: a tile is tile x tile cells */
+    int bits;        /* 8 .. 16: S = 2^bits - 1 */
+    int level_bits;  /* 3 .. 6: L = 2^level_bits level bins */
+    float top;       /* the sample value that maps to S; > every black level */
+    int sat;         /* 1 .. S+1: a sample with code >= sat spoils its tile (for its colour); S+1: none */
+    int floor;       /* -S-1 .. S-1: a sample with code <= floor spoils its tile; -S-1: none */
+    int reserved[4]; /* zero */
+} rc_raw_noise_desc;
+size_t rc_raw_noise_desc_size(void);
+
+/* d_src and fmt as rc_raw_stats reads them: B frames of a mosaic (2h, 2w), every storage, any cfa, padded lines, width, black; white is not
+ * looked at: `top` takes its place.  Cells, CFA positions pos = 0 .. 3 (black[]'s order) and the colour index c = 0 R, 1 G1, 2 G2, 3 B (the
+ * packed map's slot order, rc_calib_desc.gains' order) are rc_raw_stats'.  d_hist (B, 4, L, 320) int32, 4-byte aligned; d_level (B, 4, L)
+ * int64, 8-byte aligned; T = tile.  Per frame:
+ *   1. Code.  v = float(p), exact for every storage; NaN counts as 0.  d = v - black[pos];  n = d k[pos], each rounded to fp32 on its own (no
+ *      fused multiply-add), with k[pos] = float(double(S) / (double(top) - double(black[pos]))) formed once on the host exactly as
+ *      rc_raw_stats forms it;  q = clamp(rint(n), -S, S), rint rounding half to even.  The lower clamp is -S, NOT 0: samples below the black
+ *      level are the lower half of the noise at black, and clamping them at 0 would halve the variance of the darkest bin.  +-inf clamp like
+ *      any other value.
+ *   2. Tiles.  Tile (ty, tx) is the cells cy0 + T ty .. + T - 1 by cx0 + T tx .. + T - 1, for ty < rh div T and tx < rw div T; the cells
+ *      beyond the last whole tile are not measured.  Per tile and per CFA position, over that position's T^2 samples:  s1 = sum q;
+ *      m = max q;  n = min q;  e = sum d^2 over the T^2 / 2 DISJOINT horizontal pairs of cells, d = q(y, 2j) - q(y, 2j+1) with tile-relative
+ *      cell columns.  Disjoint pairs make the d independent: on a flat tile with noise variance sigma^2 (in codes), e / (2 sigma^2) is
+ *      chi-squared with T^2 / 2 degrees of freedom.
+ *   3. Validity.  The tile is valid for that colour if m < sat and n > floor.
+ *   4. Level bin.  l = max(s1, 0) >> (2 log2 T + bits - level_bits), so 0 <= l <= L - 1 by construction.
+ *   5. Energy bin, a 3-bit-mantissa code of e:  ebin(e) = e for e < 16;  else, with k = floor(log2 e), ebin(e) = 8 (k - 3) + (e >> (k - 3)).
+ *      e <= 2 T^2 S^2 < 2^41, so ebin <= 311; e needs 64 bits above bits = 12.
+ *   6. Accumulate.  For a valid tile:  hist[c][l][ebin(e)] += 1  and  level[c][l] += s1 (signed).
+ * Everything after step 1 is integer arithmetic: the result does not depend on the order of summation, so it is bit-exact and the same from
+ * run to run although it is accumulated with atomics.  A mosaic holds fewer than 2^31 samples, so a frame has fewer than 2^25 tiles (a
+ * count fits int32) and |sum s1| < 2^29 x 2^16 = 2^45.
+ * Every element of both outputs is written: the entry point zeroes them on `stream` itself (the caller does not), then one launch adds.
+ * It keeps no device buffer of its own and is capturable; a graph replay starts from zero again.
+ * Null pointers, an unknown storage or cfa, a bad line_bytes or width, a misaligned source, non-finite black levels, a bad shape (empty, more
+ * than 65535 frames, a mosaic of 2^31 samples or more), a tile other than 4, 8 or 16, bits, level_bits, sat or floor out of range, a top that
+ * is not finite, is at or below a black level or so close to one that k is not finite, an odd cx0, an ROI outside the frame, with one zero
+ * side only or with fewer than T cell rows or columns, non-zero reserved (fmt's too), d_level not 8-byte or d_hist not 4-byte aligned:
+ * RC_ERR_INVALID before anything is enqueued, with a message naming rc_raw_noise. */
+int rc_raw_noise(const void* d_src, const rc_raw_format* fmt, const rc_raw_noise_desc* desc, void* d_hist, void* d_level,
+                 int batch, int h, int w, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

@@ -375,6 +375,10 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
     behind a repair, fp32 behind a merge or the filter -- and the RawFrameStats of this call is left in net.raw_stats, the way
     net.defect_counts is.  Nothing else changes.  Other taps are the op on its own; per-exposure statistics are ops.raw_stats on the
     (B E, 2h, X) view of the frame as delivered.
+    raw_format.noise (a RawNoise): the mosaic that enters the temporal filter (or, without one, the next stage) is measured by
+    ops.raw_noise (one launch, no state: allowed under graph capture) behind quad, merge and repair and IN FRONT of the filter -- the frame
+    whose noise Temporal.noise describes; behind the filter that noise is gone -- and the RawNoiseStats of this call is left in
+    net.raw_noise.  Nothing else changes.  Per-exposure noise is ops.raw_noise on the (B E, 2h, X) view of the frame as delivered.
     A cond the caller supplies is used as it is: it is NOT corrected and NOT calibrated."""
     need_cond = hasattr(net, "classifier") and cond is None and not getattr(net, "cond_from_raw", False)
     if raw_format is not None and raw_format.temporal is not None:
@@ -390,6 +394,10 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
             fixed, net.__dict__["defect_counts"] = fixed
         mosaic = fixed
         raw_format = dataclasses.replace(raw_format, storage="float" if raw_format.storage == "float" else "u16", width=None, defects=None)
+    if raw_format is not None and raw_format.noise is not None:
+        import dataclasses
+        net.__dict__["raw_noise"] = ops.raw_noise(mosaic, raw_format)
+        raw_format = dataclasses.replace(raw_format, noise=None)
     if raw_format is not None and raw_format.temporal is not None:
         mosaic, raw_format = _temporal(mosaic, raw_format)
     if raw_format is not None and raw_format.stats is not None:

@@ -650,6 +650,32 @@ def raw_stats(mosaic: torch.Tensor, raw_format, stats=None):
     return RawFrameStats(hist, zones, stats, roi)
 
 
+def raw_noise(mosaic: torch.Tensor, raw_format, noise=None):
+    """The noise of the mosaic itself against its level (rc_raw_noise; the arithmetic is fixed in include/realcam_hip.h): a sensor frame as
+    `raw_format` (a RawFormat) describes it -> a RawNoiseStats: per CFA colour R, G1, G2, B (Calibration.gains' order) and level bin the
+    histogram (B,4,L,320) int32 of the pair-difference energies of the tiles of the RawNoise `noise` (default: raw_format.noise), and the
+    sums (B,4,L) int64 of their codes, on the device.  Its helpers turn the tables into a photon-transfer curve (levels, variance), DNG's
+    NoiseProfile (profile) and the (n_abs, n_rel) Temporal takes (temporal_noise), all on the device.  The codes are linear and
+    black-subtracted with raw_format's black levels, signed, and in front of every gain and of the temporal filter: raw_format.calibration
+    and raw_format.temporal are not looked at.  The frame is read once by one launch, as delivered (any storage, MIPI lines included); no
+    device state, nothing is synchronised: capturable.  raw_format.quad / exposures / defects must be None: run those ops first and
+    measure what they hand on (forward_mosaic does); per-exposure noise is this op on the (B E, 2h, X) view of the frames as delivered."""
+    from .raw_format import CFAS, SLOT_POS
+    from .raw_noise import RawNoise, RawNoiseStats
+    _raw_stages(raw_format, "raw_noise", ("calibration", "temporal"))
+    noise = raw_format.noise if noise is None else noise
+    if not isinstance(noise, RawNoise):
+        raise TypeError(f"raw_noise: noise must be a RawNoise (or raw_format.noise set), got {type(noise).__name__}")
+    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format)
+    roi = noise.check(h2 // 2, w2 // 2)
+    blacks = raw_format.blacks()
+    top = noise.top_value(raw_format.white_level, blacks)
+    hist, level = _R.raw_noise(mosaic, storage, CFAS[raw_format.cfa], int(w2), list(blacks), list(roi), noise.tile, noise.bits, noise.level_bits,
+                               top, noise.sat_code, noise.floor_code)
+    S = float(noise.codes - 1)
+    return RawNoiseStats(hist, level, noise, roi, [(top - blacks[pos]) / S for pos in SLOT_POS[raw_format.cfa]])
+
+
 def raw_hdr_merge(mosaic: torch.Tensor, raw_format, exposures=None) -> torch.Tensor:
     """Multi-exposure HDR merge on the mosaic itself, between the defects stage and the calibration (rc_raw_hdr_merge; the arithmetic is fixed
     in include/realcam_hip.h): the E = 2 .. 4 exposures of each frame as `raw_format` (a RawFormat) describes them -- (B,E,2h,X) for

@@ -48,6 +48,12 @@ class RawFormat:
                  4; validate then returns the size of what leaves the stage, and the other stages are checked against it.  It takes no
                  Exposures(layout="lines") (de-interleave first) and no Defects.map (the map addresses photosites that the stage mixes
                  or merges; hot / cold thresholds are fine).
+    noise        None, or a RawNoise: forward_mosaic measures the noise of the mosaic that enters the temporal filter (or the calibration, or
+                 the ingest, where there is none) -- after quad, merge and repair, and IN FRONT of the filter, whose Temporal.noise
+                 describes exactly this frame -- with ops.raw_noise (one launch: per CFA colour and level bin a histogram of tile
+                 energies) and leaves the RawNoiseStats in net.raw_noise; its temporal_noise() is the (n_abs, n_rel) a Temporal takes.
+                 A measurement changes nothing the other stages do: every other op ignores the field.  The region and the tile are
+                 checked against the cell size (h, w) of what leaves the quad stage; RawNoise.top defaults to white_level.
     calibration  None, or a Calibration: forward_mosaic then runs ops.raw_calibrate (a linearisation curve, these levels, a flat-field gain
                  map, white-balance gains, a clip) after the defects stage and ingests its fp32 result.  With a curve, black_level and
                  white_level are in the curve's linear units.  A gain map must have the node count the mosaic needs.
@@ -64,6 +70,7 @@ class RawFormat:
     black_level: Union[float, Tuple[float, float, float, float]] = 0.0
     white_level: float = 1.0
     quad: Optional[object] = None
+    noise: Optional[object] = None
     temporal: Optional[object] = None
     stats: Optional[object] = None
     exposures: Optional[object] = None
@@ -177,6 +184,12 @@ class RawFormat:
             if self.calibration is not None and getattr(self.calibration, "curve", None) is not None:
                 raise ValueError("a Calibration.curve cannot follow temporal: the noise model needs linear samples -- linearise the frame first")
             self.temporal.check(h2, w2, shape[0])
+        if self.noise is not None:
+            from .raw_noise import RawNoise
+            if not isinstance(self.noise, RawNoise):
+                raise TypeError(f"RawFormat.noise must be None or a RawNoise, got {type(self.noise).__name__}")
+            self.noise.check(h2 // 2, w2 // 2)
+            self.noise.top_value(self.white_level, self.blacks())
         if self.stats is not None:
             from .raw_stats import RawStats
             if not isinstance(self.stats, RawStats):

@@ -426,6 +426,29 @@ define("raw_stats(Tensor src, int storage, int cfa, int width, float[] black, in
        "int sat, int dark) -> (Tensor, Tensor)", _raw_stats_alloc, _raw_stats_launch)
 
 
+def _raw_noise_alloc(src, storage, cfa, width, black, roi, tile, bits, level_bits, top, sat, floor):
+    return (src.new_empty((src.shape[0], 4, 1 << level_bits, _lib.RC_RAW_NOISE_EBINS), dtype=torch.int32),
+            src.new_empty((src.shape[0], 4, 1 << level_bits), dtype=torch.int64))
+
+
+def _raw_noise_launch(outs, src, storage, cfa, width, black, roi, tile, bits, level_bits, top, sat, floor):
+    hist, level = outs
+    b, h2, _ = src.shape
+    if len(roi) != 4:
+        raise ValueError(f"realcam::raw_noise: roi must be (cy0, cx0, rh, rw) in cells, got {roi!r}")
+    src, f = _raw_source(src, storage, cfa, width, black, 0.0)
+    d = _lib.RawNoiseDesc(roi=(C.c_int32 * 4)(*roi), tile=tile, bits=bits, level_bits=level_bits, top=float(top), sat=sat, floor=floor)
+    check(lib().rc_raw_noise(src.data_ptr(), C.byref(f), C.byref(d), hist.data_ptr(), level.data_ptr(), b, h2 // 2, width // 2, _stream()), "rc_raw_noise")
+
+
+# src (B, 2h, X) as raw_ingest_fmt takes it -> hist (B,4,L,320) int32 and level (B,4,L) int64, L = 2^level_bits: per CFA colour (R, G1, G2, B)
+# and level bin the energy histogram of the tile x tile-cell tiles of the region roi = (cy0, cx0, rh, rw) in Bayer cells, and the sum of their
+# code sums; top: the sample value that maps to 2^bits - 1; sat / floor: codes that spoil a tile (2^bits / -2^bits: none).  The outputs are
+# not zeroed here: the entry point does that on the stream
+define("raw_noise(Tensor src, int storage, int cfa, int width, float[] black, int[] roi, int tile, int bits, int level_bits, float top, "
+       "int sat, int floor) -> (Tensor, Tensor)", _raw_noise_alloc, _raw_noise_launch)
+
+
 def _hdr_alloc(src, times, storage, cfa, width, black, exposures, lines, host_times, knee, motion):
     return src.new_empty((src.shape[0], src.shape[1] // exposures if lines else src.shape[2], width), dtype=torch.float32)
 
