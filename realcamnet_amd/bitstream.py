@@ -97,6 +97,10 @@ class Tables:
     def __init__(self, cdf: torch.Tensor, sizes: torch.Tensor, offsets: torch.Tensor, device):
         if cdf.numel() == 0:
             raise RuntimeError("entropy model has no CDF tables: call update() (or load a checkpoint that carries them) first")
+        # a row is at least one symbol and the escape (3 entries): a row of 2 has the single frequency 2^16, which the device coder's 16-bit field codes as 0
+        for r, size in enumerate(sizes.reshape(-1).tolist()):
+            if not 3 <= size <= cdf.shape[-1]:
+                raise ValueError(f"CDF row {r} has size {size}: a row holds 3 to {cdf.shape[-1]} (the table's width) entries")
         self.cdf = cdf.to(device=device, dtype=torch.int32).contiguous()
         self.sizes = sizes.to(device=device, dtype=torch.int32).reshape(-1).contiguous()
         self.offsets = offsets.to(device=device, dtype=torch.int32).reshape(-1).contiguous()

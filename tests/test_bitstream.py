@@ -24,7 +24,7 @@ def _symbols(n, t, seed=0, escapes=True):
     rng = np.random.default_rng(seed)
     idx = rng.integers(0, 64, n).astype(np.int32)
     sym = np.round(rng.standard_normal(n) * t["scale_table"].numpy()[idx] * 1.3).astype(np.int32)
-    if escapes:                                                   # far outside the table's support: 4-bit bypass escapes, up to 8 nibbles
+    if escapes:                                                   # far outside the table's support: 4-bit bypass escapes, up to 7 nibbles
         sym[::97] += 3000; sym[5::211] -= 70000; sym[7::1009] = 2 ** 27; sym[11::1013] = -(2 ** 27)
     return sym, idx
 
