@@ -948,6 +948,54 @@ size_t rc_raw_noise_desc_size(void);
 int rc_raw_noise(const void* d_src, const rc_raw_format* fmt, const rc_raw_noise_desc* desc, void* d_hist, void* d_level,
                  int batch, int h, int w, void* stream);
 
+/* ---- lateral chromatic aberration (ABI 15, additive): the R and B samples of the mosaic resampled inside their own colour's plane -- the last
+ * box of the input side, between the calibration and the ingest.
+ * A lens images red and blue at a slightly different magnification than green; towards the corners an edge lands on different photosites in
+ * R, G and B.  The error has to leave the mosaic: once the planes are interpolated together the fringe is part of the picture, and rc_warp
+ * moves the three output planes by one mesh.  DNG carries the calibration as WarpRectilinear radial terms per plane, chart tools as a coarse
+ * grid of shifts; both become the mesh below.
+ * Replaces: unpacking the lines into fp32, two strided slices, two dense grids and two F.grid_sample calls, and a scatter -- five full-frame
+ * passes and two dense grids in HBM.  Here one launch over the bytes as delivered. */
+#define RC_CA_MAX_REACH 8         /* the largest |shift| a mesh may ask for, in samples of a colour's plane */
+typedef struct rc_ca_desc {
+    int interp;            /* RC_WARP_BILINEAR | RC_WARP_BICUBIC */
+    int cell;              /* 8, 16, 32, 64 or 128: a node every `cell` samples of a colour's own h x w plane (every 2 cell mosaic samples) */
+    int reach;             /* 1 .. 8: every shift is clamped into [-reach, reach]; the kernel stages a halo of reach + 2 (bicubic) or + 1 */
+    int reserved[5];       /* zero */
+} rc_ca_desc;
+size_t rc_ca_desc_size(void);
+
+/* d_src: B frames of a mosaic (2h, 2w) as rc_raw_calibrate reads them (fmt: every storage, cfa, line_bytes, width; black and white are not
+ * looked at: the interpolation is linear and R and B each have one black level, so the levels keep their meaning).  d_shift: DEVICE fp32,
+ * 8-byte aligned, (2, Gh, Gw, 2): plane 0 belongs to R, plane 1 to B; node (j, i) of a plane holds (dx, dy) in samples of the colour's own
+ * plane (one unit is two mosaic samples) for plane sample (j cell, i cell); Gh = ceil(h / cell) + 1, Gw = ceil(w / cell) + 1; one mesh serves
+ * every frame.  Nodes need not be finite (step 2).  d_dst: (B, 2h, 2w) fp32, rows dst_pitch_bytes apart (0: dense), frames 2h rows apart.
+ *
+ * c is the decoded sample as fp32 (counts are exact).  Every product, sum and difference is rounded on its own (no fused multiply-add).
+ * A G sample stores c.  The R sample -- and likewise the B sample, with its own mesh plane -- at position (Y, X) of its colour's plane
+ * (mosaic sample (2Y + py, 2X + px), (py, px) the colour's place in the cell), with k = log2(cell):
+ *   1. mesh     j0 = Y >> k, i0 = X >> k; fy = (Y & (cell - 1)) 2^-k, fx = (X & (cell - 1)) 2^-k (exact); with g00, g01, g10, g11 the nodes
+ *               (j0, i0), (j0, i0 + 1), (j0 + 1, i0), (j0 + 1, i0 + 1), per component (dx, then dy):
+ *               top = g00 + fx (g01 - g00);  bot = g10 + fx (g11 - g10);  d = top + fy (bot - top)
+ *               -- rc_raw_calibrate's step 3: a constant mesh shifts by exactly that constant.
+ *   2. guard    NaN -> 0; then d = min(max(d, -float(reach)), float(reach)).  Whatever the device mesh holds -- NaN, +-inf, 1e30 -- no tap
+ *               leaves what the kernel staged.
+ *   3. source   sx = float(X) + dx, sy = float(Y) + dy;  x0 = int(floor(sx)), tx = sx - float(x0);  y0, ty likewise.
+ *   4. taps     offsets and weights are rc_warp's step 4: BILINEAR 0, 1 with 1-t, t; BICUBIC -1, 0, 1, 2 with c2(t+1), c1(t), c1(1-t),
+ *               c2(2-t) and its two polynomials.  A tap outside [0, w) x [0, h) reads the plane sample at the index clamped into the plane.
+ *   5. sums     rc_warp's step 5: per tap row r_k = (..((wx_0 s_k0) + (wx_1 s_k1)) + ..), then o = (..((wy_0 r_0) + (wy_1 r_1)) + ..).
+ *   6. store    fp32.
+ * Consequences: a zero mesh returns the decoded frame exactly (up to the sign of a zero); a mesh of whole numbers returns the shifted plane
+ * exactly wherever no tap was clamped; a zero R plane of the mesh leaves R exact while B moves.  Frames holding NaN / Inf are outside this
+ * contract (no fault, any value).  One launch, capturable; the library keeps no device buffer.
+ * Null pointers, an unknown storage, cfa or interp, a cell outside 8 .. 128, a reach outside 1 .. 8, non-zero reserved (fmt's too),
+ * line_bytes shorter than a row or no multiple of the sample size, fmt->width other than 0 or 2w, a RAW10 width not divisible by 4, a source
+ * misaligned for its sample (MIPI: 4 bytes), a mesh not 8-byte aligned, a dst pitch shorter than a row or no multiple of 4, dst misaligned or
+ * overlapping src, a frame of 2 GiB or more (rows x pitch, either side), h or w above 2^23 (RC_WARP_MAX_DIM), more than 65535 frames:
+ * RC_ERR_INVALID before anything is enqueued. */
+int rc_raw_aberration(const void* d_src, const rc_raw_format* fmt, const rc_ca_desc* desc, const float* d_shift,
+                      float* d_dst, int dst_pitch_bytes, int batch, int h, int w, void* stream);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

@@ -266,7 +266,7 @@ def _quad(mosaic, raw_format):
     Bayer sensor's frame."""
     import dataclasses
     h2, w2 = raw_format.validate(mosaic.shape)                # every refusal, before any launch; the size of what leaves the stage
-    one = dataclasses.replace(raw_format, exposures=None, defects=None, temporal=None, calibration=None)
+    one = dataclasses.replace(raw_format, exposures=None, defects=None, temporal=None, calibration=None, aberration=None)
     if raw_format.exposures is not None:                      # layout "frames": validate refuses "lines"
         b, e = mosaic.shape[0], mosaic.shape[1]
         out = ops.raw_quad(mosaic.reshape((b * e,) + tuple(mosaic.shape[2:])), one).view(b, e, h2, w2)
@@ -286,7 +286,7 @@ def _merge_exposures(net, mosaic, raw_format):
     ex = raw_format.exposures
     if raw_format.defects is not None:
         b, e = mosaic.shape[0], ex.count
-        one = dataclasses.replace(raw_format, exposures=None, calibration=None, temporal=None)
+        one = dataclasses.replace(raw_format, exposures=None, calibration=None, temporal=None, aberration=None)
         fixed = ops.raw_defects(mosaic.reshape((b * e,) + tuple(mosaic.shape[2:])), one)
         if raw_format.defects.counts:
             fixed, counts = fixed
@@ -331,7 +331,7 @@ def _temporal_vectors(mosaic, raw_format, prev, st):
     b, h2, w2 = prev.shape
     of_frame, of_state = st.pyramids(spec.level_shapes(b, h2 // 2, w2 // 2), prev)
     cur = ops.raw_motion_pyramid(mosaic, raw_format, tm.levels, out=of_frame)
-    state_format = dataclasses.replace(raw_format, storage="float", width=None, defects=None, exposures=None)
+    state_format = dataclasses.replace(raw_format, storage="float", width=None, defects=None, exposures=None, aberration=None)
     ref = ops.raw_motion_pyramid(prev, state_format, tm.levels, gain=t.gain, out=of_state)
     field = ops.motion_estimate(cur, ref, spec)
     v = field.vectors
@@ -379,6 +379,10 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
     ops.raw_noise (one launch, no state: allowed under graph capture) behind quad, merge and repair and IN FRONT of the filter -- the frame
     whose noise Temporal.noise describes; behind the filter that noise is gone -- and the RawNoiseStats of this call is left in
     net.raw_noise.  Nothing else changes.  Per-exposure noise is ops.raw_noise on the (B E, 2h, X) view of the frame as delivered.
+    raw_format.aberration (an Aberration): the last box in front of the ingest.  ops.raw_aberration (one launch, no state: allowed under
+    graph capture) resamples the R and B samples of the mosaic the calibration left (or, without one, of the frame as the preceding stage
+    left it) inside their own colour's plane and keeps G; the ingest reads its fp32 result with the same CFA and levels.  The order is
+    quad, merge, repair, noise tap, temporal, stats tap, calibration, aberration, ingest.
     A cond the caller supplies is used as it is: it is NOT corrected and NOT calibrated."""
     need_cond = hasattr(net, "classifier") and cond is None and not getattr(net, "cond_from_raw", False)
     if raw_format is not None and raw_format.temporal is not None:
@@ -408,6 +412,10 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
         import dataclasses
         mosaic = ops.raw_calibrate(mosaic, raw_format, dtype=torch.float32)
         raw_format = dataclasses.replace(raw_format, storage="float", width=None, black_level=0.0, white_level=1.0, defects=None, calibration=None)
+    if raw_format is not None and raw_format.aberration is not None:
+        import dataclasses
+        mosaic = ops.raw_aberration(mosaic, raw_format)
+        raw_format = dataclasses.replace(raw_format, storage="float", width=None, aberration=None)
     if raw_format is not None:
         a, c = ops.raw_ingest(mosaic, dtype=dt, pad_to=pad_to, black_level=black_level, white_level=white_level, cond_hw=cond_hw,
                               raw_format=raw_format)

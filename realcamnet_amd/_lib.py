@@ -43,6 +43,7 @@ RC_TNR_RESET, RC_TNR_GAIN = 1, 2
 RC_QUAD_REMOSAIC, RC_QUAD_BIN = 0, 1
 RC_RAW_STATS_SLOTS, RC_RAW_STATS_MAX_GRID, RC_RAW_STATS_MAX_HIST_BITS = 8, 64, 10
 RC_RAW_NOISE_EBINS, RC_RAW_NOISE_MAX_LEVEL_BITS = 320, 6
+RC_CA_MAX_REACH = 8
 
 
 class ConvDesc(C.Structure):
@@ -185,6 +186,11 @@ class RawNoiseDesc(C.Structure):
     ]
 
 
+class CaDesc(C.Structure):
+    """Mirror of `struct rc_ca_desc`."""
+    _fields_ = [("interp", C.c_int32), ("cell", C.c_int32), ("reach", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 def declared_symbols() -> list[str]:
     """Every function the public header declares (used by the CPU-side ABI test)."""
     text = HEADER.read_text()
@@ -244,6 +250,8 @@ _SIGS = {
     "rc_raw_stats": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(RawStatsDesc), _P, _P, _I, _I, _I, _P]),
     "rc_raw_noise_desc_size": (_SZ, []),
     "rc_raw_noise": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(RawNoiseDesc), _P, _P, _I, _I, _I, _P]),
+    "rc_ca_desc_size": (_SZ, []),
+    "rc_raw_aberration": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(CaDesc), _P, _P, _I, _I, _I, _I, _P]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

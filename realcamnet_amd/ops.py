@@ -481,6 +481,8 @@ _STAGE_REFUSALS = (
     ("defects", "{op} does not correct defects: run ops.raw_defects first, on each exposure where there are several, and hand its result on "
                 "(forward_mosaic does both)"),
     ("calibration", "{op} does not calibrate: run ops.raw_calibrate first and ingest its float result with levels 0 / 1 (forward_mosaic does both)"),
+    ("aberration", "{op} does not correct chromatic aberration: run ops.raw_aberration first (behind ops.raw_calibrate, where the format "
+                   "calibrates) and ingest its float result with aberration=None (forward_mosaic does both)"),
 )
 
 
@@ -560,14 +562,14 @@ def raw_quad(mosaic: torch.Tensor, raw_format, quad=None) -> torch.Tensor:
     import dataclasses
     from .quad import QuadBayer
     from .raw_format import CFAS
-    _raw_stages(raw_format, "raw_quad", ("quad", "defects", "exposures", "temporal", "calibration"))
+    _raw_stages(raw_format, "raw_quad", ("quad", "defects", "exposures", "temporal", "calibration", "aberration"))
     if raw_format.exposures is not None:                        # in front of the merge: its own advice
         raise ValueError("raw_quad reads one exposure: pass Exposures(layout='frames') frames as their (B E, H, X) view, with exposures=None "
                          "(forward_mosaic does)")
     quad = raw_format.quad if quad is None else quad
     if not isinstance(quad, QuadBayer):
         raise ValueError(f"raw_quad: quad must be a QuadBayer (or raw_format.quad set), got {type(quad).__name__}")
-    fmt = dataclasses.replace(raw_format, quad=quad, defects=None, temporal=None, calibration=None)
+    fmt = dataclasses.replace(raw_format, quad=quad, defects=None, temporal=None, calibration=None, aberration=None)
     mosaic, storage, _ = _raw_source(mosaic, fmt)
     width = fmt.width if fmt.packed else mosaic.shape[-1]
     return _R.raw_quad(mosaic, storage, CFAS[fmt.cfa], int(width), quad.code)
@@ -582,7 +584,7 @@ def raw_defects(mosaic: torch.Tensor, raw_format, defects=None):
     synchronised.  Frames holding NaN / Inf are outside the contract."""
     from .defects import Defects
     from .raw_format import CFAS
-    _raw_stages(raw_format, "raw_defects", ("defects", "calibration"))
+    _raw_stages(raw_format, "raw_defects", ("defects", "calibration", "aberration"))
     mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format)
     defects = raw_format.defects if defects is None else defects
     if not isinstance(defects, Defects):
@@ -605,7 +607,7 @@ def raw_calibrate(mosaic: torch.Tensor, raw_format, calibration=None, dtype: tor
     Frames holding NaN / Inf are outside the contract."""
     from .calibration import Calibration
     from .raw_format import CFAS
-    _raw_stages(raw_format, "raw_calibrate", ("calibration",))
+    _raw_stages(raw_format, "raw_calibrate", ("calibration", "aberration"))
     mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format)
     calibration = raw_format.calibration if calibration is None else calibration
     if not isinstance(calibration, Calibration):
@@ -628,6 +630,27 @@ def raw_calibrate(mosaic: torch.Tensor, raw_format, calibration=None, dtype: tor
                             [] if calibration.clip is None else list(calibration.clip), dtype)
 
 
+def raw_aberration(mosaic: torch.Tensor, raw_format, aberration=None) -> torch.Tensor:
+    """Lateral chromatic aberration correction on the mosaic itself, between the calibration and the ingest (rc_raw_aberration; the
+    arithmetic is fixed in include/realcam_hip.h): a sensor frame as `raw_format` (a RawFormat) describes it -> a dense fp32 mosaic
+    (B,2h,2w) whose G samples are the decoded input and whose R and B samples are resampled inside their own colour's h x w plane through
+    the mesh of `aberration` (an Aberration; default: raw_format.aberration), bilinear or bicubic, taps outside the plane clamped.  The
+    levels keep their meaning: ops.raw_ingest of the result with storage "float", aberration=None and the same cfa and levels continues.
+    One launch; the mesh is kept on the device per (Aberration, device); no device state, nothing is synchronised: capturable.  Every
+    earlier stage of the format (quad, exposures, defects, temporal, calibration) must be None: run those ops first.  Frames holding
+    NaN / Inf are outside the contract."""
+    from .aberration import Aberration
+    from .raw_format import CFAS
+    _raw_stages(raw_format, "raw_aberration", ("aberration",))
+    aberration = raw_format.aberration if aberration is None else aberration
+    if not isinstance(aberration, Aberration):
+        raise TypeError(f"raw_aberration: aberration must be an Aberration (or raw_format.aberration set), got {type(aberration).__name__}")
+    mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format)
+    aberration.check(h2, w2)
+    shift = _device_table(mosaic, aberration.shift.shape, torch.float32, aberration.device_shift)
+    return _R.raw_aberration(mosaic, shift, storage, CFAS[raw_format.cfa], int(w2), aberration.code, aberration.cell, aberration.reach)
+
+
 def raw_stats(mosaic: torch.Tensor, raw_format, stats=None):
     """RAW-domain 3A statistics of the mosaic itself (rc_raw_stats; the arithmetic is fixed in include/realcam_hip.h): a sensor frame as
     `raw_format` (a RawFormat) describes it -> a RawFrameStats: per CFA colour R, G1, G2, B (Calibration.gains' order) the code histograms
@@ -638,7 +661,7 @@ def raw_stats(mosaic: torch.Tensor, raw_format, stats=None):
     does); per-exposure statistics are this op on the (B E, 2h, X) view of the frames as delivered."""
     from .raw_format import CFAS
     from .raw_stats import RawFrameStats, RawStats
-    _raw_stages(raw_format, "raw_stats", ("calibration",))
+    _raw_stages(raw_format, "raw_stats", ("calibration", "aberration"))
     stats = raw_format.stats if stats is None else stats
     if not isinstance(stats, RawStats):
         raise TypeError(f"raw_stats: stats must be a RawStats (or raw_format.stats set), got {type(stats).__name__}")
@@ -662,7 +685,7 @@ def raw_noise(mosaic: torch.Tensor, raw_format, noise=None):
     measure what they hand on (forward_mosaic does); per-exposure noise is this op on the (B E, 2h, X) view of the frames as delivered."""
     from .raw_format import CFAS, SLOT_POS
     from .raw_noise import RawNoise, RawNoiseStats
-    _raw_stages(raw_format, "raw_noise", ("calibration", "temporal"))
+    _raw_stages(raw_format, "raw_noise", ("calibration", "temporal", "aberration"))
     noise = raw_format.noise if noise is None else noise
     if not isinstance(noise, RawNoise):
         raise TypeError(f"raw_noise: noise must be a RawNoise (or raw_format.noise set), got {type(noise).__name__}")
@@ -687,7 +710,7 @@ def raw_hdr_merge(mosaic: torch.Tensor, raw_format, exposures=None) -> torch.Ten
     import dataclasses
     from .exposures import Exposures
     from .raw_format import CFAS
-    _raw_stages(raw_format, "raw_hdr_merge", ("exposures", "calibration"))
+    _raw_stages(raw_format, "raw_hdr_merge", ("exposures", "calibration", "aberration"))
     exposures = raw_format.exposures if exposures is None else exposures
     if not isinstance(exposures, Exposures):
         raise TypeError(f"raw_hdr_merge: exposures must be an Exposures (or raw_format.exposures set), got {type(exposures).__name__}")
@@ -719,7 +742,7 @@ def raw_temporal(mosaic: torch.Tensor, raw_format, prev: Optional[torch.Tensor] 
     (but for RawFormat.validate, which refuses a frame too small for it): the caller brings the vectors."""
     from .raw_format import CFAS
     from .temporal import Temporal
-    _raw_stages(raw_format, "raw_temporal", ("temporal", "calibration"))
+    _raw_stages(raw_format, "raw_temporal", ("temporal", "calibration", "aberration"))
     t = raw_format.temporal
     if not isinstance(t, Temporal):
         raise TypeError(f"raw_temporal: raw_format.temporal must be a Temporal, got {type(t).__name__}")
@@ -801,7 +824,7 @@ def raw_motion_pyramid(mosaic: torch.Tensor, raw_format, levels: int, gain=None,
     and capturable.  raw_format.defects and raw_format.exposures must be None (run those stages first); temporal and calibration are not
     looked at."""
     from .raw_format import CFAS
-    _raw_stages(raw_format, "raw_motion_pyramid", ("temporal", "calibration"))
+    _raw_stages(raw_format, "raw_motion_pyramid", ("temporal", "calibration", "aberration"))
     _pyramid_out("raw_motion_pyramid", levels)
     mosaic, storage, (h2, w2) = _raw_source(mosaic, raw_format)
     b = mosaic.shape[0]

@@ -62,6 +62,12 @@ class RawFormat:
                  (one launch: per CFA colour a code histogram and a 3A zone grid in Bayer cells) and leaves the RawFrameStats in
                  net.raw_stats.  A measurement changes nothing the other stages do: every other op ignores the field.  The region and
                  the grid are checked against the cell size (h, w) of what leaves the quad stage; RawStats.top defaults to white_level.
+    aberration   None, or an Aberration: forward_mosaic corrects the lens's lateral chromatic aberration (ops.raw_aberration, one launch)
+                 behind the calibration and in front of the ingest: every R and every B sample is resampled inside its own colour's
+                 h x w plane through a coarse mesh of shifts, G is kept, and the ingest reads the fp32 result with the same CFA and
+                 levels.  Behind the calibration because a curve must be undone before samples are interpolated, and because the gain
+                 map, the temporal state and a Defects.map address photosites.  The mesh must have the node count the mosaic that leaves
+                 the quad stage needs.
     """
 
     cfa: str = "RGGB"
@@ -69,6 +75,7 @@ class RawFormat:
     width: Optional[int] = None
     black_level: Union[float, Tuple[float, float, float, float]] = 0.0
     white_level: float = 1.0
+    aberration: Optional[object] = None
     quad: Optional[object] = None
     noise: Optional[object] = None
     temporal: Optional[object] = None
@@ -201,4 +208,9 @@ class RawFormat:
             if not isinstance(self.calibration, Calibration):
                 raise TypeError(f"RawFormat.calibration must be None or a Calibration, got {type(self.calibration).__name__}")
             self.calibration.check(h2, w2, shape[0])
+        if self.aberration is not None:
+            from .aberration import Aberration
+            if not isinstance(self.aberration, Aberration):
+                raise TypeError(f"RawFormat.aberration must be None or an Aberration, got {type(self.aberration).__name__}")
+            self.aberration.check(h2, w2)
         return h2, w2

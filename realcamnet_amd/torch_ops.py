@@ -449,6 +449,40 @@ define("raw_noise(Tensor src, int storage, int cfa, int width, float[] black, in
        "int sat, int floor) -> (Tensor, Tensor)", _raw_noise_alloc, _raw_noise_launch)
 
 
+def _ca_alloc(src, shift, storage, cfa, width, interp, cell, reach):
+    if src.dim() != 3 or src.shape[1] % 2 or width < 2 or width % 2:
+        raise ValueError(f"realcam::raw_aberration: src must be (B, 2h, X) and width an even mosaic width, got {tuple(src.shape)} and width {width}")
+    if storage in (_lib.RC_RAW_F32, _lib.RC_RAW_BF16, _lib.RC_RAW_F16):
+        want = {_lib.RC_RAW_F32: torch.float32, _lib.RC_RAW_BF16: torch.bfloat16, _lib.RC_RAW_F16: torch.float16}[storage]
+    elif storage == _lib.RC_RAW_U16:
+        want = torch.uint16
+    elif storage in (_lib.RC_RAW_U8, _lib.RC_RAW_MIPI10, _lib.RC_RAW_MIPI12):
+        want = torch.uint8
+    else:
+        raise ValueError(f"realcam::raw_aberration: unknown storage {storage}")
+    if src.dtype != want:
+        raise TypeError(f"realcam::raw_aberration: storage {storage} takes a {want} tensor, got {src.dtype}")
+    if cell not in (8, 16, 32, 64, 128) or not 1 <= reach <= _lib.RC_CA_MAX_REACH or interp not in (_lib.RC_WARP_BILINEAR, _lib.RC_WARP_BICUBIC):
+        raise ValueError(f"realcam::raw_aberration: cell 8 .. 128, reach 1 .. {_lib.RC_CA_MAX_REACH}, interp bilinear or bicubic; got {cell}, {reach}, {interp}")
+    nodes = (2, -(-(src.shape[1] // 2) // cell) + 1, -(-(width // 2) // cell) + 1, 2)
+    if shift.dtype != torch.float32 or tuple(shift.shape) != nodes or not shift.is_contiguous() or shift.device != src.device:
+        raise ValueError(f"realcam::raw_aberration: shift must be a contiguous {nodes} fp32 tensor on the frame's device, got {tuple(shift.shape)} {shift.dtype} on {shift.device}")
+    return src.new_empty((src.shape[0], src.shape[1], width), dtype=torch.float32)
+
+
+def _ca_launch(out, src, shift, storage, cfa, width, interp, cell, reach):
+    b, h2, _ = src.shape
+    src, f = _raw_source(src, storage, cfa, width, [0.0] * 4, 1.0)
+    d = _lib.CaDesc(interp=interp, cell=cell, reach=reach)
+    check(lib().rc_raw_aberration(src.data_ptr(), C.byref(f), C.byref(d), shift.data_ptr(), out.data_ptr(), 0, b, h2 // 2, width // 2, _stream()), "rc_raw_aberration")
+
+
+# src (B, 2h, X) as raw_ingest_fmt takes it; shift (2, Gh, Gw, 2) fp32 on the device: (dx, dy) per node, plane 0 R, plane 1 B, in samples of
+# the colour's own plane; interp: the rc_warp_interp enum; reach: 1 .. 8, the clamp of every shift -> the mosaic (B, 2h, 2w) fp32 with R and
+# B resampled inside their planes and G kept
+define("raw_aberration(Tensor src, Tensor shift, int storage, int cfa, int width, int interp, int cell, int reach) -> Tensor", _ca_alloc, _ca_launch)
+
+
 def _hdr_alloc(src, times, storage, cfa, width, black, exposures, lines, host_times, knee, motion):
     return src.new_empty((src.shape[0], src.shape[1] // exposures if lines else src.shape[2], width), dtype=torch.float32)
 
