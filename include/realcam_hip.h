@@ -996,6 +996,70 @@ size_t rc_ca_desc_size(void);
 int rc_raw_aberration(const void* d_src, const rc_raw_format* fmt, const rc_ca_desc* desc, const float* d_shift,
                       float* d_dst, int dst_pitch_bytes, int batch, int h, int w, void* stream);
 
+/* ---- raw stills (ABI 15, additive): the sensor mosaic as delivered -> one DNG file per frame, coded on the device -----------------------------
+ * The raw file next to rc_jpeg_encode's still: a little-endian TIFF whose one IFD holds the CFA image in tiles, each tile a lossless JPEG
+ * stream (ITU-T T.81 process 14, DNG's Compression 7).  The library knows nothing of TIFF tags: the caller composes the header -- the TIFF
+ * header, IFD 0 and its out-of-line values, header_bytes in all -- and names the two places in it where the TileOffsets and TileByteCounts
+ * arrays (LONG, one entry per tile, raster order) stand; rc_dng_encode copies the header and fills the two arrays.
+ * Replaces: a device-to-host copy of (B, 2h, 2w) uint16 and a host encoder.  Three launches per call and no host sync, as rc_jpeg_encode:
+ * every tile is coded by one wave, twice -- once to count its bytes, once, after a scan of the counts, straight to its place in the file. */
+typedef struct rc_dng_desc {
+    int tile_w, tile_h;    /* in mosaic samples; multiples of 16 in 16 .. 65520 */
+    int components;        /* 2: a tile is a frame of tile_w / 2 columns and 2 components, so a sample is predicted from the sample two to its
+                              left, which has its own colour; 1: tile_w columns of one component */
+    int reserved[5];       /* zero */
+} rc_dng_desc;
+size_t rc_dng_desc_size(void);
+
+typedef struct rc_dng_plan_info {
+    long long tile_header_bytes;   /* SOI .. the end of SOS of a tile (rc_dng_tile_header): 58 + 5 components */
+    long long tiles_x, tiles_y;    /* ceil(w2 / tile_w), ceil(h2 / tile_h) */
+    long long capacity;            /* the default bytes per frame: header_bytes + tiles (tile_header_bytes + 2 + 4 tile_w tile_h).  A sample is
+                                      at most 27 bits, so only a frame full of stuffed 0xFF bytes can exceed it */
+    long long scratch_bytes;       /* per frame of the batch: 4 per tile */
+} rc_dng_plan_info;
+
+/* Host only.  h2, w2: the mosaic's size in samples, both even.  fmt: only its storage is looked at -- RC_RAW_U16, RC_RAW_U8, RC_RAW_MIPI10 or
+ * RC_RAW_MIPI12; a float storage is refused (a DNG holds sensor codes).  header_bytes must be even and at least 8; the two arrays
+ * [offsets_at, offsets_at + 4 tiles) and [counts_at, ...) must start on even offsets, lie inside the header and not overlap; the default
+ * capacity must stay below 2^31 (TIFF offsets are LONG, and a tile's stuffed byte count must fit 32 bits).  RC_ERR_INVALID otherwise. */
+int rc_dng_plan(const rc_dng_desc* desc, const rc_raw_format* fmt, int h2, int w2, long long header_bytes, long long offsets_at, long long counts_at,
+                rc_dng_plan_info* plan);
+/* Host only.  SOI .. the end of SOS of a tile into buf[0 .. cap), *len = tile_header_bytes (the same for every tile of a file). */
+int rc_dng_tile_header(const rc_dng_desc* desc, const rc_raw_format* fmt, uint8_t* buf, size_t cap, size_t* len);
+
+/* d_src: B frames of a mosaic (h2, w2) as rc_raw_stats reads them (fmt: the four integer storages, any cfa -- it is not looked at --
+ * line_bytes, width; black and white are not looked at).  d_header: the caller's header_bytes on the device.  d_scratch: batch *
+ * scratch_bytes, 4-byte aligned, no state between calls.  d_dst: batch * capacity bytes, frame b at b * capacity.  d_lengths (batch) int64:
+ * the bytes each complete file NEEDS, whether or not they fit.  Frame b is d_dst[b capacity .. b capacity + lengths[b]) when lengths[b] <=
+ * capacity; otherwise its `capacity` bytes are unspecified.  Nothing outside a frame's `capacity` bytes is written, whatever the data.
+ * The file, bit for bit:
+ *   layout   the header's bytes, with entry t of the array at offsets_at = the offset of tile t's stream and entry t of the array at
+ *            counts_at = its length, both little-endian LONG; then the tiles' streams in raster order of tiles, each on an even offset: a
+ *            stream of odd length is followed by one zero byte (the last one too; lengths[b] counts it).
+ *   samples  sample (y, x) of the tile grid is the frame's (y', x'): x' = x for x < w2, else w2 - 2 + (x & 1); y' = y for y < h2, else
+ *            h2 - 2 + (y & 1) -- beyond the frame the last sample of the same colour repeats (TIFF tiles are whole).  v is the sample's code
+ *            as stored (rc_raw_storage's bit layouts), an integer below 2^P, P = 8 / 10 / 12 / 16 for U8 / MIPI10 / MIPI12 / U16.
+ *   stream   SOI; SOF3 (Lf = 8 + 3 Nf, precision P, tile_h lines, tile_w / components columns, Nf = components, component c: id c + 1,
+ *            sampling 1x1, Tq 0); one DHT (Lh = 36, class 0, id 0, the table below); SOS (Ls = 6 + 2 Ns, Ns = components, component c:
+ *            id c + 1, tables 0; Ss = 1: predictor 1; Se = 0; Ah = Al = 0); the entropy-coded data; EOI.  No restart markers.
+ *   predict  with n = components, sample (y, x) of a tile is predicted by 2^(P-1) for y = 0 and x < n, by sample (y - 1, x) for y > 0
+ *            and x < n, and by sample (y, x - n) otherwise.
+ *   code     d = (v - prediction) mod 2^16 taken as signed; SSSS = 0 for d = 0, else the bit length of |d| (16 for d = -32768); the
+ *            Huffman code of SSSS, then -- unless SSSS is 0 or 16 -- the low SSSS bits of d (d >= 0) or of d + 2^SSSS - 1 (d < 0).
+ *            Samples in raster order of the tile; bits MSB first; the last byte padded with 1-bits; 0xFF -> 0xFF 0x00.
+ *   table    fixed and canonical, built for the noise of 10 .. 12-bit sensors: BITS = 0,0,5,3,1,1,1,1,1,1,1,1,1,0,0,0; HUFFVAL =
+ *            1,2,3,4,5, 0,6,7, 8,9,10,11,12,13,14,15,16.  The longest code with its extra bits is 12 + 15 = 27 bits.
+ * Null pointers, a float or unknown storage, an unknown cfa, a bad line_bytes or width, a misaligned source, odd or non-positive h2 / w2,
+ * more than 65535 frames, a tile or components outside the limits, non-zero reserved (fmt's too), header_bytes / offsets_at / counts_at
+ * that rc_dng_plan refuses, a capacity below 1 or of 2^32 or more, scratch not 4-byte or lengths not 8-byte aligned: RC_ERR_INVALID before
+ * anything is enqueued, with a message naming rc_dng_encode. */
+int rc_dng_encode(const void* d_src, const rc_raw_format* fmt, const rc_dng_desc* desc, const void* d_header, long long header_bytes,
+                  long long offsets_at, long long counts_at, void* d_scratch, void* d_dst, void* d_lengths, int batch, int h2, int w2,
+                  long long capacity, void* stream);
+/* Measurement only (tools/dng_bench.py times the launches one by one): as rc_debug_jpeg_passes, for rc_dng_encode's three launches. */
+int rc_debug_dng_passes(int mask);
+
 /* ---- layout plumbing at the nn.Module boundary (reference tensors are NCHW) ------------------
  * nchw (B,C,h,w) -> nhwc (B,hp,wp,C) with zero padding (hp>=h, wp>=w) and dtype conversion. */
 int rc_nchw_to_nhwc(const void* d_src, int src_dtype, void* d_dst, int dst_dtype,

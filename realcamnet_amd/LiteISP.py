@@ -8,6 +8,7 @@ front of it (Bayer unshuffle + pad_to_multiple_of_16 + crop), which upstream nev
 """
 from __future__ import annotations
 
+import dataclasses
 from typing import Optional, Sequence
 
 import torch
@@ -264,7 +265,6 @@ def _quad(mosaic, raw_format):
     Exposures(layout="frames"): (B,E,...) viewed as (B E,...) -- into an ordinary Bayer mosaic of the same cfa and levels: remosaiced at full
     size, or binned to half size (fp32).  Returns that mosaic and the format that describes it; every later stage reads it as it would a
     Bayer sensor's frame."""
-    import dataclasses
     h2, w2 = raw_format.validate(mosaic.shape)                # every refusal, before any launch; the size of what leaves the stage
     one = dataclasses.replace(raw_format, exposures=None, defects=None, temporal=None, calibration=None, aberration=None)
     if raw_format.exposures is not None:                      # layout "frames": validate refuses "lines"
@@ -281,7 +281,6 @@ def _merge_exposures(net, mosaic, raw_format):
     exposure (layout "frames": (B,E,...) viewed as (B E,...); net.defect_counts is then (B,E,3)); ops.raw_hdr_merge (one launch) fuses them
     into one linear fp32 mosaic in the shortest exposure's code units.  Returns that mosaic and the format that describes it: storage
     "float", the same CFA and levels, the calibration kept for the next stage."""
-    import dataclasses
     h2, w2 = raw_format.validate(mosaic.shape)                # also: "lines" with defects, a curve with exposures
     ex = raw_format.exposures
     if raw_format.defects is not None:
@@ -304,7 +303,6 @@ def _temporal(mosaic, raw_format):
     state that continues, the block vectors of the frame against the state come first (_temporal_vectors), the filter reads the state
     displaced by them (still one launch) and state.field keeps them.  Returns the filtered fp32 mosaic and the format that describes it:
     storage "float", the same CFA and levels, the calibration kept for the next stage."""
-    import dataclasses
     h2, w2 = raw_format.validate(mosaic.shape)
     st = raw_format.temporal.state
     shape = (mosaic.shape[0], h2, w2)
@@ -325,7 +323,6 @@ def _temporal_vectors(mosaic, raw_format, prev, st):
     in Bayer cells.  The luma-proxy pyramids of the frame and of the state (ops.raw_motion_pyramid, one launch each, into buffers the
     TemporalState keeps; the state is read as float storage with the frame's levels and Temporal.gain as its gain), ops.motion_estimate
     (`levels` launches), and the vectors of blocks with too little texture or too high a cost set to zero on the device: no host sync."""
-    import dataclasses
     t = raw_format.temporal
     tm, spec = t.motion, t.motion.spec()
     b, h2, w2 = prev.shape
@@ -383,7 +380,13 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
     graph capture) resamples the R and B samples of the mosaic the calibration left (or, without one, of the frame as the preceding stage
     left it) inside their own colour's plane and keeps G; the ingest reads its fp32 result with the same CFA and levels.  The order is
     quad, merge, repair, noise tap, temporal, stats tap, calibration, aberration, ingest.
+    raw_format.dng (a Dng): before anything else the mosaic AS DELIVERED is written as one DNG raw still per frame (ops.raw_dng, three
+    launches, no state: allowed under graph capture) and the DngFrames of this call is left in net.raw_dng.  Nothing else changes.  As with
+    net.raw_noise and net.raw_stats, a later call without the field leaves the attribute as it is: it holds the last call that wrote it.
     A cond the caller supplies is used as it is: it is NOT corrected and NOT calibrated."""
+    if raw_format is not None and raw_format.dng is not None:
+        net.__dict__["raw_dng"] = ops.raw_dng(mosaic, raw_format)
+        raw_format = dataclasses.replace(raw_format, dng=None)
     need_cond = hasattr(net, "classifier") and cond is None and not getattr(net, "cond_from_raw", False)
     if raw_format is not None and raw_format.temporal is not None:
         _temporal_check(raw_format)
@@ -392,28 +395,23 @@ def _ingest(net, mosaic, cond, dt, pad_to, black_level, white_level, cond_hw, ra
     if raw_format is not None and raw_format.exposures is not None:
         mosaic, raw_format = _merge_exposures(net, mosaic, raw_format)
     if raw_format is not None and raw_format.defects is not None:
-        import dataclasses
         fixed = ops.raw_defects(mosaic, dataclasses.replace(raw_format, temporal=None))
         if raw_format.defects.counts:
             fixed, net.__dict__["defect_counts"] = fixed
         mosaic = fixed
         raw_format = dataclasses.replace(raw_format, storage="float" if raw_format.storage == "float" else "u16", width=None, defects=None)
     if raw_format is not None and raw_format.noise is not None:
-        import dataclasses
         net.__dict__["raw_noise"] = ops.raw_noise(mosaic, raw_format)
         raw_format = dataclasses.replace(raw_format, noise=None)
     if raw_format is not None and raw_format.temporal is not None:
         mosaic, raw_format = _temporal(mosaic, raw_format)
     if raw_format is not None and raw_format.stats is not None:
-        import dataclasses
         net.__dict__["raw_stats"] = ops.raw_stats(mosaic, raw_format)
         raw_format = dataclasses.replace(raw_format, stats=None)
     if raw_format is not None and raw_format.calibration is not None:
-        import dataclasses
         mosaic = ops.raw_calibrate(mosaic, raw_format, dtype=torch.float32)
         raw_format = dataclasses.replace(raw_format, storage="float", width=None, black_level=0.0, white_level=1.0, defects=None, calibration=None)
     if raw_format is not None and raw_format.aberration is not None:
-        import dataclasses
         mosaic = ops.raw_aberration(mosaic, raw_format)
         raw_format = dataclasses.replace(raw_format, storage="float", width=None, aberration=None)
     if raw_format is not None:

@@ -108,6 +108,17 @@ class JpegPlanInfo(C.Structure):
                 ("capacity", C.c_longlong), ("scratch_bytes", C.c_longlong)]
 
 
+class DngDesc(C.Structure):
+    """Mirror of `struct rc_dng_desc`."""
+    _fields_ = [("tile_w", C.c_int32), ("tile_h", C.c_int32), ("components", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class DngPlanInfo(C.Structure):
+    """Mirror of `struct rc_dng_plan_info`."""
+    _fields_ = [("tile_header_bytes", C.c_longlong), ("tiles_x", C.c_longlong), ("tiles_y", C.c_longlong), ("capacity", C.c_longlong),
+                ("scratch_bytes", C.c_longlong)]
+
+
 class StatsDesc(C.Structure):
     """Mirror of `struct rc_stats_desc`."""
     _fields_ = [
@@ -252,6 +263,12 @@ _SIGS = {
     "rc_raw_noise": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(RawNoiseDesc), _P, _P, _I, _I, _I, _P]),
     "rc_ca_desc_size": (_SZ, []),
     "rc_raw_aberration": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(CaDesc), _P, _P, _I, _I, _I, _I, _P]),
+    "rc_dng_desc_size": (_SZ, []),
+    "rc_dng_plan": (C.c_int, [C.POINTER(DngDesc), C.POINTER(RawFormatDesc), _I, _I, C.c_longlong, C.c_longlong, C.c_longlong, C.POINTER(DngPlanInfo)]),
+    "rc_dng_tile_header": (C.c_int, [C.POINTER(DngDesc), C.POINTER(RawFormatDesc), _P, _SZ, C.POINTER(_SZ)]),
+    "rc_dng_encode": (C.c_int, [_P, C.POINTER(RawFormatDesc), C.POINTER(DngDesc), _P, C.c_longlong, C.c_longlong, C.c_longlong, _P, _P, _P, _I, _I, _I,
+                                C.c_longlong, _P]),
+    "rc_debug_dng_passes": (C.c_int, [_I]),
     "rc_nchw_to_nhwc": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_nhwc_to_nchw": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "rc_conv_packed_bytes": (_SZ, [_I, _I, _I, _I, _I]),

@@ -13,7 +13,7 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 OBJ = PKG / "_build"
 LIB = PKG / "librealcam_hip.so"
-SOURCES = ["lib.hip", "conv.hip", "conv_dispatch.hip", "conv_pair.hip", "wino.hip", "chain.hip", "pointwise.hip", "cond.hip", "gma.hip", "gma_fused.hip", "wmsa.hip", "entropy.hip", "rans.hip", "raw_format.hip", "yuv_encode.hip", "yuv_surface.hip", "jpeg.hip", "resize.hip", "lut3d.hip", "sharpen.hip", "tone.hip", "warp.hip", "frame_stats.hip", "motion.hip", "defects.hip", "calibrate.hip", "hdr_merge.hip", "temporal.hip", "temporal_mc.hip", "quad.hip", "raw_stats.hip", "raw_noise.hip", "aberration.hip"] + sorted(p.name for p in CSRC.glob("conv_inst_*.hip")) + sorted(p.name for p in CSRC.glob("conv32_inst_*.hip"))
+SOURCES = ["lib.hip", "conv.hip", "conv_dispatch.hip", "conv_pair.hip", "wino.hip", "chain.hip", "pointwise.hip", "cond.hip", "gma.hip", "gma_fused.hip", "wmsa.hip", "entropy.hip", "rans.hip", "raw_format.hip", "yuv_encode.hip", "yuv_surface.hip", "jpeg.hip", "resize.hip", "lut3d.hip", "sharpen.hip", "tone.hip", "warp.hip", "frame_stats.hip", "motion.hip", "defects.hip", "calibrate.hip", "hdr_merge.hip", "temporal.hip", "temporal_mc.hip", "quad.hip", "raw_stats.hip", "raw_noise.hip", "aberration.hip", "dng.hip"] + sorted(p.name for p in CSRC.glob("conv_inst_*.hip")) + sorted(p.name for p in CSRC.glob("conv32_inst_*.hip"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
          "-Rpass-analysis=kernel-resource-usage"]          # per-kernel registers / scratch / spills -> _build/resources.json (tests/test_abi_host.py holds the bench path to zero)
 FLAGS += os.environ.get("RC_EXTRA_HIPCC_FLAGS", "").split()   # experiments only

@@ -22,6 +22,7 @@
 // the final offsets.  Every store to the frame is clipped to `capacity`.  No workgroup waits on another.
 #include <atomic>
 
+#include "bitpack.hpp"
 #include "ycc_code.hpp"
 
 namespace rc {
@@ -115,15 +116,6 @@ __device__ __forceinline__ void jpeg_pair(const TI* p, float& a, float& b) {
         const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
         a = lo16<TI>(v); b = hi16<TI>(v);
     }
-}
-
-__device__ __forceinline__ int jpeg_scan_incl(int v, int lane) {     // inclusive prefix sum over the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d);
-        if (lane >= d) v += t;
-    }
-    return v;
 }
 
 template <typename TI, int SUB, bool WRITE>
@@ -255,44 +247,13 @@ __global__ void __launch_bounds__(64) jpeg_interval_kernel(JpegArgs a, const TI*
                 bits = e & 0xffffu;
                 n = (int)(e >> 16);
             }
-            const int incl = jpeg_scan_incl(n, lane);
+            const int incl = wave_scan_incl(n, lane);
             int total = carry + __shfl(incl, 63);
-            if (n) {
-                const int off = carry + incl - n, w = off >> 5, s = off & 31;
-                const uint64_t v = bits << (64 - n), v0 = v >> s;
-                const uint32_t w0 = (uint32_t)(v0 >> 32), w1 = (uint32_t)v0, w2 = s ? (uint32_t)v << (32 - s) : 0u;
-                if (w + 2 < kJpegBitWords) {
-                    if (w0) atomicOr(&bb[w], w0);
-                    if (w1) atomicOr(&bb[w + 1], w1);
-                    if (w2) atomicOr(&bb[w + 2], w2);
-                }
-            }
-            if (m == m_end - 1 && blk == NB - 1 && (total & 7)) {       // the interval ends: pad the last byte with 1-bits
-                const int pad = 8 - (total & 7);
-                if (lane == 0) atomicOr(&bb[total >> 5], ((1u << pad) - 1u) << (32 - (total & 31) - pad));
-                total += pad;
-            }
+            if (n) bits_or(bb, kJpegBitWords, carry + incl - n, bits, n);
+            if (m == m_end - 1 && blk == NB - 1) total = bits_pad_ones(bb, total, lane);      // the interval ends: pad the last byte with 1-bits
             __syncthreads();
-            // ---- stuff and store ----
-            const int nb = total >> 3;
-            for (int j0 = 0; j0 < nb; j0 += 64) {
-                const int j = j0 + lane;
-                const bool act = j < nb;
-                const uint32_t byte = act ? (bb[j >> 2] >> (24 - 8 * (j & 3))) & 0xffu : 0u;
-                const bool ff = byte == 0xffu;
-                const uint64_t fm = __ballot(ff);
-                if (WRITE && act) {
-                    const uint64_t pos = base + out + (uint32_t)lane + (uint32_t)__popcll(fm & below);
-                    if (pos < cap) frame[pos] = (uint8_t)byte;
-                    if (ff && pos + 1 < cap) frame[pos + 1] = 0;
-                }
-                out += (uint32_t)min(64, nb - j0) + (uint32_t)__popcll(fm);
-            }
-            const uint32_t left = (bb[nb >> 2] >> (24 - 8 * (nb & 3))) & 0xffu;        // the incomplete byte (zero bits behind its `carry` bits)
-            __syncthreads();
-            for (int i = lane; i <= (total >> 5) && i < kJpegBitWords; i += 64) bb[i] = i == 0 ? left << 24 : 0u;
-            carry = total & 7;
-            __syncthreads();
+            // ---- stuff and store (bitpack.hpp) ----
+            carry = bits_flush<WRITE>(bb, kJpegBitWords, total, lane, frame, cap, base, out);
         }
     }
     if (!WRITE && lane == 0) scratch[slot] = out;

@@ -699,6 +699,54 @@ def raw_noise(mosaic: torch.Tensor, raw_format, noise=None):
     return RawNoiseStats(hist, level, noise, roi, [(top - blacks[pos]) / S for pos in SLOT_POS[raw_format.cfa]])
 
 
+def dng_header(fmt, h2: int, w2: int, raw_format, device):
+    """Dng.header(h2, w2, raw_format) as a uint8 tensor on `device`: composed on the host and copied once per (size, what the header takes from
+    the RawFormat, device), then kept ON THE Dng ITSELF through `derived` -- a warmed-up ops.raw_dng makes no host-to-device copy.  The tensor
+    lives exactly as long as the Dng: whoever holds the Dng (the closure a captured graph replays, a RawFormat) holds the header its launches
+    read, no other call can free it, and a capture loop that makes a new Dng(datetime=...) per still leaves nothing behind."""
+    import numpy as np
+    device = torch.device(device)
+    key = (int(h2), int(w2), raw_format.storage, raw_format.cfa, raw_format.quad is not None, raw_format.blacks(), float(raw_format.white_level),
+           getattr(raw_format.calibration, "curve", None), fmt.neutral(raw_format), device.type,
+           device.index if device.index is not None else torch.cuda.current_device())
+    return derived(fmt, ("dng_header",) + key, (),
+                   lambda: torch.from_numpy(np.frombuffer(fmt.header(int(h2), int(w2), raw_format), dtype=np.uint8).copy()).to(device))
+
+
+def raw_dng(mosaic: torch.Tensor, raw_format, dng=None):
+    """The raw still of the mosaic itself (rc_dng_encode; the file is fixed bit for bit in include/realcam_hip.h): a sensor frame (B,[1,]2h,X)
+    as `raw_format` (a RawFormat) describes it, AS DELIVERED -> a DngFrames: one DNG file per frame, the samples coded losslessly on the device
+    in tiles (lossless JPEG, predictor 1) behind a TIFF header whose tags come from the format: the CFA phase (a 4x4 pattern with
+    raw_format.quad set), the levels, a Calibration.curve as LinearizationTable, host-number Calibration.gains as AsShotNeutral.  `dng` (a Dng;
+    default: raw_format.dng) names the tile, the components and the tags the format does not know.  Storage u16, u8, mipi10 or mipi12; a
+    float storage is refused.  Three launches, no host sync, no device state: capturable; `lengths` stays on the device until
+    DngFrames.tobytes / files.  No stage of the format runs: the file is the sensor's data and the tags say what to do with it.  With
+    raw_format.exposures the op is refused: write each exposure with this op on the (B E, 2h, X) view of the frames and exposures=None."""
+    import dataclasses
+    from .dng import STORAGE_CODE, Dng, DngFrames
+    from .raw_format import CFAS, RawFormat
+    if not isinstance(raw_format, RawFormat):
+        raise TypeError(f"raw_dng: raw_format must be a RawFormat, got {type(raw_format).__name__}")
+    dng = raw_format.dng if dng is None else dng
+    if not isinstance(dng, Dng):
+        raise TypeError(f"raw_dng: dng must be a Dng (or raw_format.dng set), got {type(dng).__name__}")
+    if raw_format.exposures is not None:
+        raise ValueError("raw_dng writes one exposure per file: raw_format.exposures is set.  Write each exposure with ops.raw_dng on the "
+                         "(B E, 2h, X) view of the frames as delivered, with exposures=None")
+    if raw_format.storage not in STORAGE_CODE:
+        raise ValueError(f"raw_dng: a DNG holds sensor codes: storage must be one of {sorted(STORAGE_CODE)}, got {raw_format.storage!r}")
+    # the frame as delivered: no stage's check applies (a quad frame keeps its own size)
+    bare = dataclasses.replace(raw_format, dng=None, quad=None, defects=None, temporal=None, noise=None, stats=None, calibration=None, aberration=None)
+    mosaic, storage, (h2, w2) = _raw_source(mosaic, bare)
+    if raw_format.quad is not None and (h2 % 4 or w2 % 4):
+        raise ValueError(f"raw_dng: a Quad-Bayer frame has a height and width divisible by 4, got ({h2}, {w2})")
+    plan = dng.plan(h2, w2, raw_format)
+    header = _device_table(mosaic, (plan.header_bytes,), torch.uint8, lambda device: dng_header(dng, h2, w2, raw_format, device))
+    buf, lengths = _R.raw_dng(mosaic, header, storage, CFAS[raw_format.cfa], int(w2), dng.tile[0], dng.tile[1], dng.components, plan.offsets_at,
+                              plan.counts_at, plan.capacity)
+    return DngFrames(buf, lengths, dng, (h2, w2))
+
+
 def raw_hdr_merge(mosaic: torch.Tensor, raw_format, exposures=None) -> torch.Tensor:
     """Multi-exposure HDR merge on the mosaic itself, between the defects stage and the calibration (rc_raw_hdr_merge; the arithmetic is fixed
     in include/realcam_hip.h): the E = 2 .. 4 exposures of each frame as `raw_format` (a RawFormat) describes them -- (B,E,2h,X) for

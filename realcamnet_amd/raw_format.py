@@ -68,6 +68,13 @@ class RawFormat:
                  levels.  Behind the calibration because a curve must be undone before samples are interpolated, and because the gain
                  map, the temporal state and a Defects.map address photosites.  The mesh must have the node count the mosaic that leaves
                  the quad stage needs.
+    dng          None, or a Dng: forward_mosaic also writes the mosaic AS DELIVERED -- in front of quad, repair and every other stage -- as one
+                 DNG raw still per frame (ops.raw_dng, three launches, no state: allowed under graph capture) and leaves the DngFrames in
+                 net.raw_dng.  The file is the sensor's data; its tags carry what this format knows: the CFA phase (a 4x4 pattern with quad),
+                 the levels, a Calibration.curve as LinearizationTable, host-number Calibration.gains as AsShotNeutral.  Nothing else
+                 changes: every other op ignores the field.  Storage u16, u8, mipi10 or mipi12 (a DNG holds sensor codes), and no
+                 exposures (write each exposure with ops.raw_dng on the (B E, 2h, X) view).  net.raw_dng holds the last call that wrote
+                 it: a later call without the field leaves it as it is (as net.raw_noise and net.raw_stats).
     """
 
     cfa: str = "RGGB"
@@ -75,6 +82,7 @@ class RawFormat:
     width: Optional[int] = None
     black_level: Union[float, Tuple[float, float, float, float]] = 0.0
     white_level: float = 1.0
+    dng: Optional[object] = None
     aberration: Optional[object] = None
     quad: Optional[object] = None
     noise: Optional[object] = None
@@ -213,4 +221,13 @@ class RawFormat:
             if not isinstance(self.aberration, Aberration):
                 raise TypeError(f"RawFormat.aberration must be None or an Aberration, got {type(self.aberration).__name__}")
             self.aberration.check(h2, w2)
+        if self.dng is not None:
+            from .dng import PRECISION, Dng
+            if not isinstance(self.dng, Dng):
+                raise TypeError(f"RawFormat.dng must be None or a Dng, got {type(self.dng).__name__}")
+            if self.storage not in PRECISION:
+                raise ValueError(f"RawFormat.dng: a DNG holds sensor codes: storage must be one of {sorted(PRECISION)}, got {self.storage!r}")
+            if self.exposures is not None:
+                raise ValueError("RawFormat.dng cannot go with exposures: a file holds one exposure -- write each with ops.raw_dng on the "
+                                 "(B E, 2h, X) view of the frames as delivered, with exposures=None")
         return h2, w2

@@ -449,6 +449,35 @@ define("raw_noise(Tensor src, int storage, int cfa, int width, float[] black, in
        "int sat, int floor) -> (Tensor, Tensor)", _raw_noise_alloc, _raw_noise_launch)
 
 
+def _raw_dng_alloc(src, header, storage, cfa, width, tile_w, tile_h, components, offsets_at, counts_at, capacity):
+    if src.dim() != 3 or src.shape[1] < 2 or src.shape[1] % 2 or width < 2 or width % 2:
+        raise ValueError(f"realcam::raw_dng: src must be (B, 2h, X) and width an even mosaic width, got {tuple(src.shape)} and width {width}")
+    if header.dim() != 1 or capacity < 1:
+        raise ValueError(f"realcam::raw_dng: the header must be 1-D and capacity at least 1, got {tuple(header.shape)} and capacity {capacity}")
+    return src.new_empty((src.shape[0], capacity), dtype=torch.uint8), src.new_empty((src.shape[0],), dtype=torch.int64)
+
+
+def _raw_dng_launch(outs, src, header, storage, cfa, width, tile_w, tile_h, components, offsets_at, counts_at, capacity):
+    buf, lengths = outs
+    b, h2, _ = src.shape
+    src, f = _raw_source(src, storage, cfa, width, [0.0] * 4, 0.0)
+    d = _lib.DngDesc(tile_w=tile_w, tile_h=tile_h, components=components)
+    if header.dtype != torch.uint8 or header.device != src.device or not header.is_contiguous() or header.dim() != 1:
+        raise ValueError(f"realcam::raw_dng: the header must be a contiguous 1-D uint8 tensor on {src.device}")
+    p = _lib.DngPlanInfo()
+    check(lib().rc_dng_plan(C.byref(d), C.byref(f), h2, width, header.numel(), offsets_at, counts_at, C.byref(p)), "rc_dng_plan")
+    scratch = src.new_empty((b, p.scratch_bytes // 4), dtype=torch.int32)              # the tiles' byte counts, then offsets: nothing outlives the call
+    check(lib().rc_dng_encode(src.data_ptr(), C.byref(f), C.byref(d), header.data_ptr(), header.numel(), offsets_at, counts_at, scratch.data_ptr(),
+                              buf.data_ptr(), lengths.data_ptr(), b, h2, width, capacity, _stream()), "rc_dng_encode")
+
+
+# src (B, 2h, X) as raw_ingest_fmt takes it, integer storages only -> (B, capacity) uint8, one DNG file per frame, and (B,) int64, the bytes
+# each file needs; header: the TIFF header and IFD 0 (Dng.header) on the device; offsets_at / counts_at: where its TileOffsets /
+# TileByteCounts arrays stand; tile_w / tile_h / components: the fields of rc_dng_desc
+define("raw_dng(Tensor src, Tensor header, int storage, int cfa, int width, int tile_w, int tile_h, int components, int offsets_at, int counts_at, "
+       "int capacity) -> (Tensor, Tensor)", _raw_dng_alloc, _raw_dng_launch)
+
+
 def _ca_alloc(src, shift, storage, cfa, width, interp, cell, reach):
     if src.dim() != 3 or src.shape[1] % 2 or width < 2 or width % 2:
         raise ValueError(f"realcam::raw_aberration: src must be (B, 2h, X) and width an even mosaic width, got {tuple(src.shape)} and width {width}")
